@@ -6,9 +6,15 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (contract in the task statement).  `roofline` prices the dominant kernel
-(the MFMA implicit-GEMM forward convolution) from HIP events recorded live around its launches in the
-timed steps; `cpu_baseline` times the CPU restatement (oracle/, kind "port") on a bounded sample.
+Rank 0 prints ONE JSON line (contract in the task statement).  A plain run does only what that line's headline
+figure needs: set-up, warm-up, the --steps timed steps, the line.  --full adds the rest: `roofline` prices the
+dominant kernel (the MFMA implicit-GEMM forward convolution) from HIP events recorded live around its launches in
+the timed steps; `cpu_baseline` times the CPU restatement (oracle/, kind "port") on a bounded sample.  Without
+--full both are null.
+
+--dump-outputs DIR writes what the last timed step handed its caller (loss terms, detection-head outputs, updated
+weights, gradients, BatchNorm running statistics) as float32 DIR/<name>.npy, large arrays as a fixed seeded sample:
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -24,6 +30,35 @@ sys.path.insert(0, ROOT)
 ANCHORS = [[(116, 90), (156, 198), (373, 326)], [(30, 61), (62, 45), (59, 119)], [(10, 13), (16, 30), (33, 23)]]
 MFMA_BF16_PEAK_TFLOPS = 2500.0     # dense bf16, MI355X_MICROARCH.md
 HBM_PEAK_GBS = 8000.0
+DUMP_SAMPLE = 1 << 21              # --dump-outputs: elements kept of a larger array (8 MB in float32; the bs-32 / 640-px step dumps ~40 MB)
+
+
+def step_outputs(eng, out12):
+    """name -> tensor: what a caller of the timed step holds after it - the criterion's out12 (loss, sub_losses[6], stats[5]), the three
+    detection-head outputs of the forward (NCHW), and the engine state the step updated (weights after the SGD step, their gradients,
+    BatchNorm running statistics)."""
+    arrays = {"loss": out12}
+    for k, h in enumerate(eng._last_plan.head_outputs()):
+        arrays[f"head{k}"] = h
+    arrays["weights"] = eng.flat_w
+    arrays["grads"] = eng.flat_g
+    for stat in ("running_mean", "running_var"):
+        arrays["bn_" + stat] = torch.cat([v for k, v in eng.buffers.items() if k.endswith("." + stat)])
+    return arrays
+
+
+def dump_outputs(path, arrays, sample=DUMP_SAMPLE):
+    """Write every array flattened (C order of its logical shape) as float32 <path>/<name>.npy.  An array of more than `sample` elements is
+    reduced to `sample` of them at sorted positions drawn without replacement from a generator seeded by the array's size, so the same
+    shapes give the same positions in every run and every build."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > sample:
+            pos = np.sort(np.random.default_rng(flat.numel()).choice(flat.numel(), sample, replace=False))
+            flat = flat[torch.from_numpy(pos).to(flat.device)]
+        np.save(os.path.join(path, name + ".npy"), flat.float().cpu().numpy())
 
 
 def synth_batch(bs, px, rank, device, m=7, classes=80):
@@ -195,7 +230,12 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--px", type=int, default=640)
     ap.add_argument("--lr", type=float, default=1e-4)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-launch HIP events behind `roofline` (inside the timed "
+                         "steps) and the CPU baseline `cpu_baseline` (after them); without it both are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as float32 DIR/<name>.npy (large arrays: a fixed seeded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--tune-record", default="auto",
                     help="tune record to load (locked) before the plan build: a path, 'none' (time everything on this box), or 'auto' = "
                          "object_detectors_amd/tune_records/yolov3_d53_bs<batch>_<px>_<storage>.json when it exists (the committed step-level record: the "
@@ -204,7 +244,7 @@ def main():
                     help="format of stored activations / gradients / packed weights (fp16: the reference's apex-O2 format, with a loss scale of 1024)")
     ap.add_argument("--atomic-bn-sums", action="store_true",
                     help="A/B: BatchNorm-backward sums ending in fp32 atomics (round 3's form: not reproducible run to run) instead of the fixed-order form")
-    ap.add_argument("--no-events", action="store_true", help="skip the per-launch HIP events (pure timing run)")
+    ap.add_argument("--no-events", action="store_true", help="with --full: skip the per-launch HIP events (pure timing run)")
     ap.add_argument("--event-steps", type=int, default=1,
                     help="timed steps (spread evenly) in which every forward-conv launch is bracketed by HIP events; each event pair "
                          "costs ~6 us of serialisation, so bracketing all 75 launches in all steps would take ~2.5 %% off `value`")
@@ -285,9 +325,9 @@ def main():
 
     # live per-launch events around the dominant kernel (forward conv) — on torch's current stream, which is the
     # stream the plan launches on
-    conv_calls = conv_fwd_flops(plan)
     events = []
-    if not args.no_events:
+    if args.full and not args.no_events:
+        conv_calls = conv_fwd_flops(plan)
         orig_run = plan._run
         idx = {i: fl for i, fl, _n in conv_calls}
 
@@ -343,6 +383,8 @@ def main():
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         in_sync = bool(float(hi - lo) <= 1e-9 * float(hi))
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, step_outputs(eng, out12))
     if rank == 0:
         ms = 1000.0 * elapsed / args.steps
         value = args.batch * world * args.steps / elapsed
@@ -367,7 +409,7 @@ def main():
                        "global_batch": args.batch * world, "parallelism": f"dp{world}"},
             "loss_first": round(loss0, 4), "loss_last": round(loss1, 4), "weights_in_sync_across_ranks": in_sync,
             "roofline": roof,
-            "cpu_baseline": None if args.no_cpu_baseline else cpu_baseline(args.px),
+            "cpu_baseline": cpu_baseline(args.px) if args.full and not args.no_cpu_baseline else None,
         }
         print(json.dumps(line), flush=True)
     if world > 1:
