@@ -39,7 +39,12 @@ int mi355det_debug_set(int key, int value);   /* bring-up / test knobs: key 0 = 
                                                  with per-lane bookkeeping, 2 = stride-2 data gradient as four class launches (tests compare the forms),
                                                  3 = diagnostic build of the phase-staggered conv, 5 = stride-2 data-gradient form, 6 = weight-gradient
                                                  ablations (timing only), 7 = weight-gradient split count for every launch (+ 65536: the 256 x 256
-                                                 phase-staggered kernel; fails for shapes it does not take), 8 = 1: the tuner leaves that kernel out */
+                                                 phase-staggered kernel; fails for shapes it does not take), 8 = 1: the tuner leaves that kernel out,
+                                                 9 = 1: strict mode - a configuration forced through key 0 that the launch would not run (predicate or
+                                                 epilogue of the id fails, wide id on a narrow output or 29 / 30 / 31 on a wide one, unknown id, a route
+                                                 without tile choice: single-launch stride 2, split-K conv_dgrad_ws, the fixed Cin % 64 != 0 tile) and a
+                                                 split count forced through key 7 that is invalid for the pixel count or exceeds the workspace return
+                                                 MI355DET_EINVAL and launch nothing; 0 (default) = they fall back silently (1 / the nearest valid split) */
 int mi355det_debug_ptr(int key, void* ptr);   /* key 0 = device buffer for the diagnostic (phase-stamp) conv build */
 int mi355det_version(void);
 
@@ -343,7 +348,8 @@ typedef struct {
 } mi355det_conv_shape;
 
 /* Forward implicit GEMM: y = conv(x, w) [+ bias]; w packed [cout_pad][k*k*cin] bf16 (K contiguous).
- *   out_f32 != 0: y is fp32 (head conv_out), else bf16.
+ *   out_f32 != 0: y is fp32 (head conv_out), else bf16 (cout % 8 == 0: stored in 8-channel pieces).  Only the cout real channels of
+ *   each pixel are written; pitch padding of x, y and the residual is never read or written.
  *   stats != NULL: per pixel-tile partial sums / sums of squares of y, stats[row][0][c], stats[row][1][c]
  *   (fp32, row pitch 2*cout_pad, plain stores, deterministic) for training BatchNorm. */
 int mi355det_conv_fwd(const mi355det_conv_shape* s, const void* x, const void* w, const float* bias,
@@ -443,8 +449,13 @@ int mi355det_stem_bwd_fused(const float* img, const void* w, const float* scale_
 int mi355det_stem_bwd_finish(const void* w, const float* scale_shift, const float* ag, const float* sums, int64_t count, float* dw,
                              float* dgamma, float* dbeta, void* stream);
 
-/* Data gradient: dx = conv_transpose(dy, w); wt packed for dgrad by mi355det_pack_weights.
- * residual != NULL adds a bf16 tensor (same shape as dx) in the epilogue (residual-block skip). */
+/* Data gradient: dx = conv_transpose(dy, w); wt packed for dgrad by mi355det_pack_weights.  cin % 8 == 0.
+ * residual != NULL adds a bf16 tensor (same shape as dx) in the epilogue (residual-block skip).  Rounding of the residual form, per route:
+ *   implicit-GEMM routes (stride 1, the four stride-2 class launches, the class-concatenated form): dx = r(r(acc) + residual) - the fp32 sum
+ *   is rounded to 16 bits, the residual added in fp32, the result rounded again;
+ *   single-launch stride 2 (3x3, cin 32 / 64, cout 64, even maps, wo % 32 == 0; debug key 2 = 1 turns it off): dx = r(acc + residual) -
+ *   one rounding after the sum and the residual;
+ *   1x1 stride 2: the three parity classes the convolution never reads get the residual (or 0) copied. */
 int mi355det_conv_dgrad(const mi355det_conv_shape* s, const void* dy, const void* wt, void* dx,
                         const void* residual, int32_t residual_ld, void* stream);
 
@@ -452,7 +463,7 @@ int mi355det_conv_dgrad(const mi355det_conv_shape* s, const void* dy, const void
  * loss.backward() in detection/engine.py:49-57).  When the shape has few output pixels and a very deep reduction (stride 1, <= 96 tiles
  * of 128 x 128, k*k*cout >= 8192: the 1204-class RetinaNet head on the small pyramid levels, retinanet.py:75-105) the reduction is split
  * over channel ranges into fp32 partial tiles in `workspace` and added in a fixed order (deterministic; the bf16 rounding happens once,
- * after the sum and the residual).  mi355det_conv_dgrad_workspace returns the bytes that form needs, 0 when it does not apply; with a
+ * after the sum and the residual: dx = r(acc + residual)).  mi355det_conv_dgrad_workspace returns the bytes that form needs, 0 when it does not apply; with a
  * NULL / zero workspace or a shape it does not apply to, conv_dgrad_ws IS conv_dgrad. */
 /* Data gradient with the FrozenBatchNorm2d / ReLU backward of the layer that produced the convolution's input folded into the epilogue
  * (replaces, for a bottleneck's conv1 -> conv2 -> conv3 chain and the head towers, the autograd steps of F.relu and of the frozen affine,

@@ -31,8 +31,9 @@ extern int g_wgrad_force_dbg;
 extern int g_wgrad8_off;
 extern int g_wgrad_ablate;   // wgrad_kernels.hip
 extern int g_dgrad_s2_off;     // dgrad_s2_kernels.hip
+extern int g_conv_strict;      // wgrad_kernels.hip (mi355det_debug_set(9, v))
 int mi355det_internal_dgrad_s2(const mi355det_conv_shape* s, const void* dy, const void* wt, void* dx, const void* residual, int32_t residual_ld,
-                               void* stream);
+                               void* stream, int probe = 0);
 
 namespace {
 
@@ -893,6 +894,15 @@ float time_candidate(F&& fn, hipEvent_t e0, hipEvent_t e1, hipStream_t st, int* 
 }
 
 int g_tune = 0;   // bring-up knob (mi355det_debug_set(0, v)): forces a tile configuration
+
+// strict mode (mi355det_debug_set(9, 1)): a configuration forced through key 0 that this launch would not run is an error, not a launch of
+// another kernel (tests must know which kernel produced the numbers they check)
+int strict_reject(int cfg, const char* why) {
+  char msg[160];
+  snprintf(msg, sizeof(msg), "conv: forced tile configuration %d not taken: %s (strict mode, debug key 9)", cfg, why);
+  return fail(MI355DET_EINVAL, "%s", msg);
+}
+bool strict_forced() { return g_conv_strict && g_tune != 0; }
 TuneMap& g_igemm_tuned = tune_table(TUNE_IGEMM);   // shape key -> configuration found by mi355det_conv_autotune (part of the tune record)
 
 unsigned long long igemm_key(const IgemmParams& p, int epi) {
@@ -947,7 +957,7 @@ int launch_dx(const IgemmParams& p_in, hipStream_t st) {
 //   3: 256x256x64 x2, 8 waves of 128x64, 1 workgroup/CU        4: 128x128x32 x3, 4 waves of 64x64, 3 workgroups/CU
 //   5: 128x128x32 x2 at 4 workgroups/CU                         6: 256x256x64 with LDS-DMA pieces interleaved between MFMAs
 template <int EPI>
-int run_cfg(int cfg, const IgemmParams& p, hipStream_t st) {
+int run_cfg(int cfg, const IgemmParams& p, hipStream_t st, bool strict = false) {
   switch (cfg) {
     case 2: return launch_cfg<2, 2, 8, 4, 32, 2, EPI>(p, st);
     case 3: if (p.CoutPad % 256 == 0) return launch_cfg<2, 4, 8, 4, 64, 2, EPI>(p, st); break;
@@ -985,6 +995,13 @@ int run_cfg(int cfg, const IgemmParams& p, hipStream_t st) {
     case 97: if (EPI == EPI_STATS && dx_applicable(p)) return launch_dx<4, 2, 4, 4, EPI, 3, true>(p, st); break;   // 256x128, 8 waves, ring 3
     default: break;
   }
+  if (strict && cfg != 1) {
+    static const int known[] = {2, 3, 4, 5, 6, 15, 16, 17, 18, 19, 21, 22, 23, 25, 26, 27, 28, 35, 40, 44, 45, 50, 51, 52, 53, 54, 55, 56, 97, 98, 99};
+    bool k = false;
+    for (int c : known) k = k || c == cfg;
+    if (cfg == 29 || cfg == 30 || cfg == 31) return strict_reject(cfg, "a narrow-output id on a launch with a multiple of 128 output channels");
+    return strict_reject(cfg, k ? "its shape or epilogue predicate does not hold for this launch" : "unknown id");
+  }
   return launch_cfg<2, 2, 4, 4, 64, 2, EPI>(p, st);
 }
 
@@ -997,7 +1014,15 @@ int launch_igemm(const IgemmParams& p, hipStream_t st) {
     auto it = g_igemm_tuned.find(igemm_key(p, EPI));
     if (it != g_igemm_tuned.end()) cfg = it->second;
     if (g_tune) cfg = g_tune;
-    return run_cfg<EPI>(cfg, p, st);
+    return run_cfg<EPI>(cfg, p, st, strict_forced());
+  }
+  if (strict_forced()) {
+    const bool nid = g_tune == 29 || g_tune == 30 || g_tune == 31;
+    if (p.CoutPad % 128 == 0) return strict_reject(g_tune, "Cin is not a multiple of 64: the launch takes its fixed 128 x 128 x 32 tile");
+    if (!nid) return strict_reject(g_tune, "a wide-output id on a narrow output (32 / 64 padded channels)");
+    const bool ok = p.CoutPad % 64 == 0 ? (g_tune == 30 ? dx_applicable(p, 64) : g_tune == 31 && dx_applicable(p, 64, 32))
+                                        : p.CoutPad % 32 == 0 && g_tune == 29 && dx_applicable(p, 32);
+    if (!ok) return strict_reject(g_tune, "the narrow shared-pixel-tile kernel does not take this shape");
   }
   if (p.CoutPad % 128 == 0) return launch_cfg<2, 2, 4, 4, 32, 3, EPI>(p, st);
   // narrow outputs (32 / 64 channels: the first layers and their data gradients): one plain tile shape each, or the
@@ -1151,6 +1176,7 @@ int mi355det_debug_set(int key, int value) {
   if (key == 7) g_wgrad_force_dbg = value;       // weight gradient: split count (+ 65536 = the 256 x 256 phase-staggered kernel) for every launch, 0 = tuned
   if (key == 6) g_wgrad_ablate = value;          // weight-gradient ablation builds (timing only): wgrad_kernels.hip
   if (key == 5) g_s2cat_force = value;           // stride-2 data gradient: 1 = class-concatenated form, 0 = four class launches, -1 = tuned choice
+  if (key == 9) g_conv_strict = value;           // 1 = strict: keys 0 and 7 fail (MI355DET_EINVAL) instead of falling back
   return 0;
 }
 
@@ -1177,6 +1203,9 @@ static int conv_fwd_impl(const mi355det_conv_shape* s, const void* x, const void
   if (int e = check_shape(s, "conv_fwd")) return e;
   if (int e = ensure_zero_page()) return e;
   if (cout_pad < s->cout) return fail(MI355DET_EINVAL, "%s: cout_pad < cout", "conv_fwd");
+  // the 16-bit epilogue stores whole 8-channel pieces: with cout % 8 != 0 the last piece would overwrite pitch padding (or, with a dense
+  // pitch, the first channels of the next pixel)
+  if (!out_f32 && (s->cout % 8)) return fail(MI355DET_EINVAL, "%s: 16-bit outputs need cout %% 8 == 0 (got %lld)", "conv_fwd", s->cout);
   IgemmParams p{};
   p.x = (const bf16_t*)x;
   p.w = (const bf16_t*)w;
@@ -1479,8 +1508,11 @@ static int conv_dgrad_impl(const mi355det_conv_shape* s, const void* dy, const v
   if (int e = check_shape(s, "conv_dgrad")) return e;
   if (int e = ensure_zero_page()) return e;
   if (s->cout % 32 != 0) return fail(MI355DET_EINVAL, "%s: Cout (the dgrad reduction dim) must be a multiple of 32 (got %lld)", "conv_dgrad", s->cout);
+  if (s->cin % 8 != 0) return fail(MI355DET_EINVAL, "%s: cin must be a multiple of 8 (the epilogue stores 8-channel pieces; got %lld)", "conv_dgrad", s->cin);
   if (!partials && !g_autotune_mode) {
     // few-channel 3x3 stride-2 layers: all four parity classes in one launch over shared dy tiles (dgrad_s2_kernels.hip)
+    if (strict_forced() && mi355det_internal_dgrad_s2(s, dy, wt, dx, residual, residual_ld, stream, 1))
+      return strict_reject(g_tune, "the shape takes the single-launch stride-2 data gradient");
     const int r = mi355det_internal_dgrad_s2(s, dy, wt, dx, residual, residual_ld, stream);
     if (r != 0) return r < 0 ? r : 0;
   }
@@ -1703,6 +1735,7 @@ int mi355det_conv_dgrad_ws(const mi355det_conv_shape* s, const void* dy, const v
                            void* workspace, size_t workspace_bytes, void* stream) {
   const int ks = dgrad_ksplit(s);
   if (ks < 2 || !workspace || g_autotune_mode) return conv_dgrad_impl(s, dy, wt, dx, residual, residual_ld, nullptr, 0, nullptr, 0.f, nullptr, stream);
+  if (strict_forced()) return strict_reject(g_tune, "the shape takes the split-K data gradient, which has a tile of its own");
   if (int e = check_shape(s, "conv_dgrad_ws")) return e;
   if (int e = ensure_zero_page()) return e;
   if (!dy || !wt || !dx) return fail(MI355DET_EINVAL, "%s: null argument", "conv_dgrad_ws");

@@ -241,9 +241,9 @@ int launch(const DgradS2Params& p, int cin, hipStream_t st) {
 
 int g_dgrad_s2_off = 0;   // diagnostic (mi355det_debug_set(2, 1)): always the four class launches (tests compare the two)
 
-// 1 = handled, 0 = shape not covered (caller takes the general path), < 0 = error
+// 1 = handled, 0 = shape not covered (caller takes the general path), < 0 = error; probe != 0: only says whether it would handle the shape
 int mi355det_internal_dgrad_s2(const mi355det_conv_shape* s, const void* dy, const void* wt, void* dx, const void* residual, int32_t residual_ld,
-                               void* stream) {
+                               void* stream, int probe) {
   if (g_dgrad_s2_off || s->ksize != 3 || s->stride != 2 || s->pad != 1 || (s->h & 1) || (s->w & 1)) return 0;
   // Cout 128 (two 64-channel chunks: 74 KB of weights, one workgroup per CU) measured SLOWER than the four class launches
   // (518 vs 485 us on 64->128 @160): only the single-chunk case is dispatched
@@ -253,6 +253,7 @@ int mi355det_internal_dgrad_s2(const mi355det_conv_shape* s, const void* dy, con
   const int tp = nch == 1 ? (s->wo % 64 == 0 ? 64 : (s->wo % 32 == 0 ? 32 : 0)) : (s->wo % 32 == 0 ? 32 : 0);
   if (!tp) return 0;
   if ((long long)s->n * s->ho * s->wo * s->out_ld * 2 >= 0x7FFFFFF0ll) return 0;   // 31-bit byte offsets into dy
+  if (probe) return s->cout / 64 == 1 ? 1 : 0;
   DgradS2Params p{};
   p.dy = (const bf16_t*)dy;
   p.w = (const bf16_t*)wt;

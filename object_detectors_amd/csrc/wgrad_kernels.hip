@@ -55,6 +55,7 @@ struct WgradParams {
 
 int g_wgrad_ablate = 0;    // diagnostic (mi355det_debug_set(6, v)): WgradParams::ablate
 int g_wgrad_general = 0;   // diagnostic (mi355det_debug_set(1, v)): 1 = always the per-lane bookkeeping form (tests compare the two)
+int g_conv_strict = 0;     // mi355det_debug_set(9, 1): a forced tile configuration (key 0) or split count (key 7) the launch would not honour is an error
 int g_wgrad_force_dbg = 0; // diagnostic (mi355det_debug_set(7, v)): split count (+ 65536: the 256 x 256 phase-staggered kernel) for every launch; 0 = tuned
 int g_wgrad8_off = 0;      // diagnostic (mi355det_debug_set(8, v)): 1 = the tuner does not time the 256 x 256 phase-staggered kernel (same-box A/B of the two kernels)
 
@@ -1119,6 +1120,14 @@ int mi355det_conv_wgrad(const mi355det_conv_shape* s, const void* x, const void*
       form8 = (it->second & WG_FORM8) != 0;
     }
     const int force = g_wgrad_force > 0 ? g_wgrad_force : g_wgrad_force_dbg;
+    if (g_conv_strict && g_wgrad_force <= 0 && g_wgrad_force_dbg > 0) {      // strict mode: the forced split is launched as it is or not at all
+      const int sp = g_wgrad_force_dbg & (WG_FORM8 - 1);
+      const size_t need = (size_t)sp * tiles * WG_TILE * WG_TILE * sizeof(float);
+      if (!split_valid(p.M, sp))
+        return fail(MI355DET_EINVAL, "%s: forced split count %lld is not valid for %lld pixels (strict mode, debug key 9)", "conv_wgrad", sp, p.M);
+      if (sp > 1 && (!workspace || need > workspace_bytes))
+        return fail(MI355DET_EINVAL, "%s: forced split count %lld needs %lld workspace bytes (strict mode, debug key 9)", "conv_wgrad", sp, (long long)need);
+    }
     if (force > 0 && split_valid(p.M, force & (WG_FORM8 - 1))) {
       splits = force & (WG_FORM8 - 1);
       form8 = (force & WG_FORM8) != 0;
@@ -1165,6 +1174,8 @@ int mi355det_conv_wgrad(const mi355det_conv_shape* s, const void* x, const void*
   const bool fits =
                     ((long long)s->n * p.H * p.W + (long long)p.pad * (p.W + 1)) * p.ldx * 2 < 0x7FFFFFF0ll &&
                     (long long)chunk * p.lddy * 2 < 0x7FFFFFF0ll;
+  if (form8 && !fits && g_conv_strict && g_wgrad_force <= 0 && (g_wgrad_force_dbg & WG_FORM8))
+    return fail(MI355DET_EINVAL, "%s: the forced phase-staggered kernel does not fit the 31-bit offsets of this shape (strict mode, debug key 9)", "conv_wgrad");
   if (form8 && fits) {
     const int tiles8 = ((p.Cout + W8_TILE - 1) / W8_TILE) * ((p.NP + W8_TILE - 1) / W8_TILE);
     static DeviceOnce attr8;
