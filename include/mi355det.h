@@ -673,6 +673,54 @@ int mi355det_coco_rows(const float* boxes, int32_t box_ld, const float* labels_f
                        int64_t k, float inp_dim, float img_h, float img_w, int32_t scale, int32_t label_mode, float* bbox_xywh,
                        float* area, int64_t* category_id, void* stream);
 
+/* ---- Mask R-CNN mask branch (csrc/mask_kernels.hip; tvision/mask_rcnn.py:21-300, tvision/roi_heads.py:99-183,403-537,844-887).  bf16
+ * storage, fp32 arithmetic; the R-CNN path is bf16-only, so these have no fp16 twins.  The ConvTranspose2d(256, 256, 2, stride=2) of the
+ * predictor is the 1x1 convolution 256 -> 1024 of mi355det_conv_fwd_ex / _dgrad_mask / _wgrad (output channel q*256 + co, q = 2*di + dj:
+ * kernel == stride, so output pixel (2i+di, 2j+dj) reads input pixel (i, j) only); its output stays in that sub-pixel order
+ * [R, 14, 14, 4*256] and mask_loss / mask_probs index the 28 x 28 mask through it.
+ *   mask_roi_pool        MultiScaleRoIAlign(['0'..'3'], 14, 2) (roi_heads mask_roi_pool) writing bf16 NHWC [R, ph, pw, C] with pixel pitch
+ *                        out_ld: out == bf16(mi355det_roi_align_nhwc) bit for bit.  Backward (grad_out != NULL, bf16 NHWC with pitch
+ *                        grad_ld): scatters into grad_feats (dense fp32 NHWC, zeroed by the caller) with fp32 atomics, like the box branch.
+ *   mask_targets         project_masks_on_boxes (roi_heads.py:131-144): roi_align(gt_masks[:, None].float(), rois, (m, m), 1.0), sampling -1,
+ *                        aligned False, all images in one launch: rois [R, 5] = (image, box), gt_index [R] = matched gt WITHIN the image,
+ *                        images->masks[b] = uint8 [G_b, h[b], w[b]] (NULL for an image no RoI refers to).  out fp32 [R, m, m].
+ *   mask_loss            maskrcnn_loss (roi_heads.py:147-183) fused with mask_fcn_logits (1x1, 256 -> K) on the label channel only: feat = the
+ *                        deconvolution output after its ReLU (bf16, sub-pixel order, pitch feat_ld >= 1024), w_logits [K, 256] / b_logits [K]
+ *                        fp32, labels [rows] int64, targets [rows, 28, 28].  rows = the bucket (padded), valid = the real positives: rows
+ *                        >= valid get zero gradient.  loss[0] = mean BCE-with-logits over valid*784 elements; dfeat = d loss / d (deconv
+ *                        pre-activation) (its ReLU folded in, bf16, same layout); dw [K, 256] / db [K] / dbias_deconv [256] are fixed-order
+ *                        reductions of per-RoI partials (no atomics, bit-reproducible); every class row is written.  valid == 0: loss 0
+ *                        and zero gradients.  workspace: mi355det_mask_loss_workspace(rows) bytes.
+ *   mask_probs           maskrcnn_inference (roi_heads.py:99-128): probs [rows, 28, 28] = sigmoid of the label channel.
+ *   mask_resize_nearest _resize_image_and_masks, masks part (transform.py:54-60): uint8 [planes, h, w] -> [planes, out_h, out_w], torch's
+ *                        nearest source index (same size: copy; doubling: dst >> 1; else min(floor(dst * (float)in / out), in - 1)).
+ *   paste_masks          paste_masks_in_image (roi_heads.py:517-537): masks fp32 [D, m, m], boxes [D, 4] in the original image; expand_masks
+ *                        (padding) + expand_boxes + int64 truncation + bilinear resize (align_corners False) + clipped paste -> out fp32
+ *                        [D, im_h, im_w], every pixel written once. */
+#define MI355DET_MASK_MAX_IMAGES 64
+typedef struct {
+  const uint8_t* masks[MI355DET_MASK_MAX_IMAGES];
+  int32_t h[MI355DET_MASK_MAX_IMAGES];
+  int32_t w[MI355DET_MASK_MAX_IMAGES];
+  int32_t n_images;
+} mi355det_mask_images;
+int mi355det_mask_roi_pool(const void* const* feats, const int32_t* hs, const int32_t* ws, const int32_t* lds, const float* scales,
+                           int32_t num_levels, const float* rois, int32_t num_rois, int32_t channels, int32_t pooled_h, int32_t pooled_w,
+                           int32_t sampling_ratio, int32_t k_min, int32_t k_max, void* out, int32_t out_ld, const void* grad_out,
+                           int32_t grad_ld, float* const* grad_feats, void* stream);
+int mi355det_mask_targets(const mi355det_mask_images* images, const float* rois, const int64_t* gt_index, int32_t num_rois, int32_t m,
+                          float* out, void* stream);
+size_t mi355det_mask_loss_workspace(int32_t rows);
+int mi355det_mask_loss(const void* feat, int32_t feat_ld, const float* w_logits, const float* b_logits, const int64_t* labels,
+                       const float* targets, int32_t rows, int32_t valid, int32_t num_classes, float* loss, void* dfeat, float* dw,
+                       float* db, float* dbias_deconv, void* workspace, size_t workspace_bytes, void* stream);
+int mi355det_mask_probs(const void* feat, int32_t feat_ld, const float* w_logits, const float* b_logits, const int64_t* labels, int32_t rows,
+                        int32_t num_classes, float* probs, void* stream);
+int mi355det_mask_resize_nearest(const uint8_t* in, int32_t planes, int32_t h, int32_t w, uint8_t* out, int32_t out_h, int32_t out_w,
+                                 void* stream);
+int mi355det_paste_masks(const float* masks, const float* boxes, int32_t num_masks, int32_t m, int32_t padding, int32_t im_h, int32_t im_w,
+                         float* out, void* stream);
+
 /* layout / dtype converters at the module boundary */
 int mi355det_nhwc_to_nchw_f32(const void* x, int x_is_bf16, int32_t x_ld, int32_t n, int32_t c, int32_t h,
                               int32_t w, float* out, void* stream);

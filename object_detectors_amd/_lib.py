@@ -47,6 +47,14 @@ class LevelGrads(C.Structure):
     _fields_ = [("n_levels", i32), ("anchors_per_pixel", i32), ("pixels", i64 * 8), ("grad", vp * 8), ("grad_ld", i32 * 8)]
 
 
+MASK_MAX_IMAGES = 64
+
+
+class MaskImages(C.Structure):
+    """mi355det_mask_images: per-image uint8 instance masks [G_b, h_b, w_b] of a batch (mi355det_mask_targets)."""
+    _fields_ = [("masks", vp * MASK_MAX_IMAGES), ("h", i32 * MASK_MAX_IMAGES), ("w", i32 * MASK_MAX_IMAGES), ("n_images", i32)]
+
+
 class PackItem(C.Structure):
     _fields_ = [("w", vp), ("w_fwd", vp), ("w_dgrad", vp), ("shape", ConvShape), ("cout_pad", i32), ("w_is_ohwi", i32)]
 
@@ -162,6 +170,13 @@ PROTOTYPES = {
     "mi355det_coco_rows": (C.c_int, [vp, i32, vp, vp, i32, i64, f32, f32, f32, i32, i32, vp, vp, vp, vp]),
     "mi355det_fastrcnn_loss_workspace": (sz, [i32]),
     "mi355det_fastrcnn_loss": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "mi355det_mask_roi_pool": (C.c_int, [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, vp]),
+    "mi355det_mask_targets": (C.c_int, [P(MaskImages), vp, vp, i32, i32, vp, vp]),
+    "mi355det_mask_loss_workspace": (sz, [i32]),
+    "mi355det_mask_loss": (C.c_int, [vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "mi355det_mask_probs": (C.c_int, [vp, i32, vp, vp, vp, i32, i32, vp, vp]),
+    "mi355det_mask_resize_nearest": (C.c_int, [vp, i32, i32, i32, vp, i32, i32, vp]),
+    "mi355det_paste_masks": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp, vp]),
 }
 
 def _f16_twins():

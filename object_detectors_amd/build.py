@@ -25,6 +25,7 @@ SOURCES = [
     ("proposal_kernels.hip", ["-ffp-contract=off"]),
     ("frcnn_kernels.hip", ["-ffp-contract=off"]),
     ("transform_kernels.hip", ["-ffp-contract=off"]),
+    ("mask_kernels.hip", ["-ffp-contract=off"]),
     ("resnet_kernels.hip", []),
     ("conv_kernels.hip", []),
     ("igemm8_kernels.hip", []),

@@ -1,0 +1,440 @@
+// Mask branch of Mask R-CNN (tvision/mask_rcnn.py:21-300, tvision/roi_heads.py:99-183,403-537,844-887, the masks parts of
+// tvision/transform.py:26-62,228-247).  bf16 storage, fp32 arithmetic; the R-CNN path is bf16-only, so there are no fp16 twins.
+//
+//   mask_roi_pool        MultiScaleRoIAlign(['0'..'3'], 14, 2) into the conv layout: bf16 NHWC [R, 14, 14, C] with a pixel pitch (the input
+//                        of mask_fcn1).  The forward repeats the arithmetic of roi_align_nhwc_kernel (roi_kernels.hip) operation for operation
+//                        and rounds once: out == bf16(mi355det_roi_align_nhwc).  The backward takes the bf16 NHWC gradient of mask_fcn1's
+//                        data gradient and scatters it with the same fp32 atomics as the box branch.
+//   mask_targets         project_masks_on_boxes: roi_align(gt_masks[:, None].float(), [matched_idx, box], (M, M), 1.0) with torchvision's
+//                        defaults sampling_ratio = -1 (adaptive) and aligned = False, on the uint8 masks of every image in one launch.
+//   mask_loss            mask_fcn_logits (1x1, 256 -> K) restricted to the label channel + binary_cross_entropy_with_logits(mean), fused,
+//                        with every gradient the backward needs; mask_probs is its forward-only form (maskrcnn_inference).
+//   mask_resize_nearest  F.interpolate(mask[:, None].float(), ..., mode='nearest')[:, 0].byte() with torch's source-index rule.
+//   paste_masks          paste_masks_in_image (expand_masks, expand_boxes, per-box bilinear resize, clipped paste), each output pixel once.
+//
+// The ConvTranspose2d(256, 256, 2, stride=2) of the mask predictor has no kernel here: with kernel == stride its output pixel (2i+di, 2j+dj)
+// depends on input pixel (i, j) only, so it IS the 1x1 convolution 256 -> 4*256 of the existing MFMA kernels (conv_fwd_ex / conv_dgrad_mask /
+// conv_wgrad) with output channel q*256 + co, q = 2*di + dj.  Its output stays in that sub-pixel order [R, 14, 14, 4, 256]; mask_loss and
+// mask_probs do the depth-to-space in their indexing (mask branch).
+//
+// Compiled with -ffp-contract=off (build.py): the pooling forward must round exactly like roi_align_nhwc_kernel, and the targets, the nearest
+// index and the paste follow torch's CPU float32 operation order.
+#include "common.h"
+
+using namespace mi355;
+
+namespace {
+
+struct MaskLevels {
+  const bf16_t* feat[4];
+  float* grad[4];
+  int h[4], w[4], ld[4];
+  float scale[4];
+};
+
+struct MaskImages {
+  const uint8_t* masks[MI355DET_MASK_MAX_IMAGES];
+  int h[MI355DET_MASK_MAX_IMAGES], w[MI355DET_MASK_MAX_IMAGES];
+};
+
+__device__ __forceinline__ int mask_map_level(const float4 r, int k_min, int k_max) {
+  const float s = sqrtf((r.z - r.x) * (r.w - r.y));
+  int k = (int)floorf(4.0f + log2f(s / 224.0f) + 1e-6f);
+  k = min(max(k, k_min), k_max);
+  return k - k_min;
+}
+
+// One thread per (RoI, bin, channel), channels innermost: coalesced bf16 reads / writes (forward) and contiguous atomics (backward).
+template <bool BWD>
+__global__ __launch_bounds__(256) void mask_roi_pool_kernel(MaskLevels L, int num_levels, const float* __restrict__ rois, int K, int C, int ph,
+                                                            int pw, int sampling, int k_min, int k_max, bf16_t* __restrict__ out, int out_ld,
+                                                            const bf16_t* __restrict__ gout, int gout_ld) {
+  const long long total = (long long)K * ph * pw * C;
+  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int c = (int)(i % C);
+    const long long pix = i / C;                 // (k * ph + py) * pw + px
+    const int px = (int)(pix % pw);
+    const long long t = pix / pw;
+    const int py = (int)(t % ph), k = (int)(t / ph);
+    const float* r = rois + 5 * (size_t)k;
+    const int b = (int)r[0];
+    const float4 box = make_float4(r[1], r[2], r[3], r[4]);
+    int lv = num_levels > 1 ? mask_map_level(box, k_min, k_max) : 0;
+    int H = L.h[0], W = L.w[0], ld = L.ld[0];
+    float sc = L.scale[0];
+    const bf16_t* f = L.feat[0];
+    float* gf = L.grad[0];
+#pragma unroll
+    for (int q = 1; q < 4; ++q)
+      if (lv == q) {
+        H = L.h[q]; W = L.w[q]; ld = L.ld[q]; sc = L.scale[q]; f = L.feat[q]; gf = L.grad[q];
+      }
+    // aligned = False (MultiScaleRoIAlign): offset 0, RoI sides clamped to >= 1
+    const float x1 = box.x * sc, y1 = box.y * sc, x2 = box.z * sc, y2 = box.w * sc;
+    const float rw = fmaxf(x2 - x1, 1.0f), rh = fmaxf(y2 - y1, 1.0f);
+    const float bh = rh / (float)ph, bw = rw / (float)pw;
+    const int gh = sampling > 0 ? sampling : (int)ceilf(rh / (float)ph), gw = sampling > 0 ? sampling : (int)ceilf(rw / (float)pw);
+    const float cnt = fmaxf((float)(gh * gw), 1.0f);
+    const size_t img = (size_t)b * H * W;
+    float acc = 0.f;
+    const float g = BWD ? bf2f(gout[pix * gout_ld + c]) / cnt : 0.f;
+    for (int iy = 0; iy < gh; ++iy) {
+      float y = y1 + py * bh + ((float)iy + 0.5f) * bh / (float)gh;
+      for (int ix = 0; ix < gw; ++ix) {
+        float x = x1 + px * bw + ((float)ix + 0.5f) * bw / (float)gw;
+        float yy = y;
+        if (yy < -1.0f || yy > (float)H || x < -1.0f || x > (float)W) continue;
+        if (yy <= 0.f) yy = 0.f;
+        if (x <= 0.f) x = 0.f;
+        int yl = (int)yy, xl = (int)x, yh, xh;
+        if (yl >= H - 1) {
+          yh = yl = H - 1;
+          yy = (float)yl;
+        } else yh = yl + 1;
+        if (xl >= W - 1) {
+          xh = xl = W - 1;
+          x = (float)xl;
+        } else xh = xl + 1;
+        const float ly = yy - yl, lx = x - xl, hy = 1.f - ly, hx = 1.f - lx;
+        const size_t p00 = (img + (size_t)yl * W + xl), p01 = (img + (size_t)yl * W + xh), p10 = (img + (size_t)yh * W + xl),
+                     p11 = (img + (size_t)yh * W + xh);
+        if (!BWD) {
+          acc += hy * hx * bf2f(f[p00 * ld + c]) + hy * lx * bf2f(f[p01 * ld + c]) + ly * hx * bf2f(f[p10 * ld + c]) + ly * lx * bf2f(f[p11 * ld + c]);
+        } else {
+          atomicAdd(gf + p00 * C + c, g * hy * hx);
+          atomicAdd(gf + p01 * C + c, g * hy * lx);
+          atomicAdd(gf + p10 * C + c, g * ly * hx);
+          atomicAdd(gf + p11 * C + c, g * ly * lx);
+        }
+      }
+    }
+    if (!BWD) out[pix * out_ld + c] = f2bf(acc / cnt);
+  }
+}
+
+// torchvision roi_align (CPU kernel order) on one uint8 mask plane per RoI: spatial_scale 1, aligned = False, adaptive sampling.
+__global__ __launch_bounds__(256) void mask_targets_kernel(MaskImages I, int n_images, const float* __restrict__ rois,
+                                                           const int64_t* __restrict__ gt_index, int R, int M, float* __restrict__ out) {
+  const long long total = (long long)R * M * M;
+  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int px = (int)(i % M);
+    const int py = (int)((i / M) % M);
+    const int k = (int)(i / ((long long)M * M));
+    const float* r = rois + 5 * (size_t)k;
+    const int b = (int)r[0];
+    if (b < 0 || b >= n_images) {
+      out[i] = 0.f;
+      continue;
+    }
+    const int H = I.h[b], W = I.w[b];
+    const uint8_t* m = I.masks[b] + (size_t)gt_index[k] * H * W;
+    const float x1 = r[1], y1 = r[2], x2 = r[3], y2 = r[4];
+    const float rw = fmaxf(x2 - x1, 1.0f), rh = fmaxf(y2 - y1, 1.0f);
+    const float bh = rh / (float)M, bw = rw / (float)M;
+    const int gh = (int)ceilf(rh / (float)M), gw = (int)ceilf(rw / (float)M);
+    const float cnt = fmaxf((float)(gh * gw), 1.0f);
+    float acc = 0.f;
+    for (int iy = 0; iy < gh; ++iy) {
+      float y = y1 + py * bh + ((float)iy + 0.5f) * bh / (float)gh;
+      for (int ix = 0; ix < gw; ++ix) {
+        float x = x1 + px * bw + ((float)ix + 0.5f) * bw / (float)gw;
+        if (y < -1.0f || y > (float)H || x < -1.0f || x > (float)W) continue;
+        float yy = y <= 0.f ? 0.f : y;
+        if (x <= 0.f) x = 0.f;
+        int yl = (int)yy, xl = (int)x, yh, xh;
+        if (yl >= H - 1) {
+          yh = yl = H - 1;
+          yy = (float)yl;
+        } else yh = yl + 1;
+        if (xl >= W - 1) {
+          xh = xl = W - 1;
+          x = (float)xl;
+        } else xh = xl + 1;
+        const float ly = yy - yl, lx = x - xl, hy = 1.f - ly, hx = 1.f - lx;
+        const float w1 = hy * hx, w2 = hy * lx, w3 = ly * hx, w4 = ly * lx;
+        acc += w1 * (float)m[(size_t)yl * W + xl] + w2 * (float)m[(size_t)yl * W + xh] + w3 * (float)m[(size_t)yh * W + xl] +
+               w4 * (float)m[(size_t)yh * W + xh];
+      }
+    }
+    out[i] = acc / cnt;
+  }
+}
+
+// Fused mask_fcn_logits (label channel only) + BCE-with-logits.  One workgroup (4 waves) per RoI; lane l owns channels 4l..4l+3 of the 256
+// (one 8-byte load per logit and lane), each wave walks 196 of the 784 = 14*14*4 sub-pixels.  F = feat[(r*196 + i*14 + j)*ld + q*256 + c]
+// is the deconvolution output (after its ReLU) in sub-pixel order; its pixel in the 28x28 mask is (2i + di, 2j + dj), q = 2*di + dj.
+//   TRAIN:  loss partial, dF = dlogit * W[label] * (F > 0) (the gradient BEFORE the deconvolution's ReLU, bf16), per-RoI partials of
+//           dW[label] (sum dlogit * F), db[label] (sum dlogit) and of the deconvolution bias (sum over the RoI's dF of its bf16 value).
+//           Rows >= valid (bucket padding) get zero everywhere.
+//   !TRAIN: probs[r][28*28] = sigmoid(logit) (maskrcnn_inference).
+#define MASK_PART 516              // floats per RoI partial: dW[256] | dbias_deconv[256] | db | loss | pad
+template <bool TRAIN>
+__global__ __launch_bounds__(256) void mask_loss_kernel(const bf16_t* __restrict__ feat, int ld, const float* __restrict__ wl,
+                                                        const float* __restrict__ bl, const int64_t* __restrict__ labels, int K, int valid,
+                                                        const float* __restrict__ tgt, float inv_n, bf16_t* __restrict__ dfeat,
+                                                        float* __restrict__ part, float* __restrict__ probs) {
+  __shared__ float red[4][2 * 256 + 2];
+  const int r = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool live = !TRAIN || r < valid;
+  long long lab = labels[r];
+  lab = lab < 0 ? 0 : (lab >= K ? K - 1 : lab);
+  const float4 w = *(const float4*)(wl + lab * 256 + 4 * lane);
+  const float b = bl[lab];
+  float dw[4] = {0.f, 0.f, 0.f, 0.f}, dd[4] = {0.f, 0.f, 0.f, 0.f}, dbs = 0.f, ls = 0.f;
+  for (int s = wave; s < 784; s += 4) {
+    const int p = s >> 2, q = s & 3;                       // p = i*14 + j
+    const size_t off = ((size_t)r * 196 + p) * ld + q * 256 + 4 * lane;
+    const uint2 raw = *(const uint2*)(feat + off);
+    const float f0 = __uint_as_float(raw.x << 16), f1 = __uint_as_float(raw.x & 0xffff0000u);
+    const float f2 = __uint_as_float(raw.y << 16), f3 = __uint_as_float(raw.y & 0xffff0000u);
+    float dot = f0 * w.x + f1 * w.y + f2 * w.z + f3 * w.w;
+    dot = wave_sum(dot);
+    const float x = dot + b;
+    const int oy = 2 * (p / 14) + (q >> 1), ox = 2 * (p % 14) + (q & 1);
+    const float sg = 1.f / (1.f + expf(-x));
+    if (!TRAIN) {
+      if (lane == 0) probs[(size_t)r * 784 + oy * 28 + ox] = sg;
+      continue;
+    }
+    float g = 0.f;
+    if (live) {
+      const float t = tgt[(size_t)r * 784 + oy * 28 + ox];
+      ls += fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
+      g = (sg - t) * inv_n;
+    }
+    const bf16_t g0 = f2bf(f0 > 0.f ? g * w.x : 0.f), g1 = f2bf(f1 > 0.f ? g * w.y : 0.f);
+    const bf16_t g2 = f2bf(f2 > 0.f ? g * w.z : 0.f), g3 = f2bf(f3 > 0.f ? g * w.w : 0.f);
+    uint2 o;
+    o.x = (unsigned)g0 | ((unsigned)g1 << 16);
+    o.y = (unsigned)g2 | ((unsigned)g3 << 16);
+    *(uint2*)(dfeat + off) = o;
+    dw[0] += g * f0; dw[1] += g * f1; dw[2] += g * f2; dw[3] += g * f3;
+    dd[0] += bf2f(g0); dd[1] += bf2f(g1); dd[2] += bf2f(g2); dd[3] += bf2f(g3);
+    dbs += g;
+  }
+  if (!TRAIN) return;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    red[wave][4 * lane + u] = dw[u];
+    red[wave][256 + 4 * lane + u] = dd[u];
+  }
+  if (lane == 0) {
+    red[wave][512] = dbs;
+    red[wave][513] = ls;
+  }
+  __syncthreads();
+  float* pr = part + (size_t)r * MASK_PART;
+  for (int e = threadIdx.x; e < 514; e += 256) pr[e] = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
+}
+
+// Fixed-order reductions of the per-RoI partials: block k < K sums dW / db of the RoIs labelled k in RoI order (segmented sum, every
+// class row written, zeros for absent classes); block K sums the deconvolution bias gradient; block K + 1 the loss.
+__global__ __launch_bounds__(256) void mask_loss_finish_kernel(const float* __restrict__ part, const int64_t* __restrict__ labels, int valid,
+                                                               int K, float inv_n, float* __restrict__ loss, float* __restrict__ dw,
+                                                               float* __restrict__ db, float* __restrict__ dbias) {
+  __shared__ float red[256];
+  const int k = blockIdx.x, t = threadIdx.x;
+  if (k < K) {
+    float a = 0.f, c = 0.f;
+    for (int r = 0; r < valid; ++r) {
+      long long lab = labels[r];
+      lab = lab < 0 ? 0 : (lab >= K ? K - 1 : lab);
+      if (lab != k) continue;
+      a += part[(size_t)r * MASK_PART + t];
+      c += part[(size_t)r * MASK_PART + 512];
+    }
+    if (dw) dw[(size_t)k * 256 + t] = a;
+    if (db && t == 0) db[k] = c;
+  } else if (k == K) {
+    float a = 0.f;
+    for (int r = 0; r < valid; ++r) a += part[(size_t)r * MASK_PART + 256 + t];
+    if (dbias) dbias[t] = a;
+  } else {
+    float a = 0.f;
+    for (int r = t; r < valid; r += 256) a += part[(size_t)r * MASK_PART + 513];
+    red[t] = a;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if (t < s) red[t] += red[t + s];
+      __syncthreads();
+    }
+    if (t == 0) loss[0] = red[0] * inv_n;
+  }
+}
+
+// torch nearest: identical sizes copy, doubling takes dst >> 1, else min(floor(dst * (float)in / out), in - 1) in float32
+__device__ __forceinline__ int nearest_src(int dst, int in, int out) {
+  if (out == in) return dst;
+  if (out == 2 * in) return dst >> 1;
+  const float scale = (float)in / (float)out;
+  return min((int)floorf((float)dst * scale), in - 1);
+}
+
+__global__ __launch_bounds__(256) void mask_resize_nearest_kernel(const uint8_t* __restrict__ in, int planes, int h, int w,
+                                                                  uint8_t* __restrict__ out, int oh, int ow) {
+  const long long total = (long long)planes * oh * ow;
+  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int x = (int)(i % ow);
+    const int y = (int)((i / ow) % oh);
+    const long long p = i / ((long long)ow * oh);
+    out[i] = in[(size_t)p * h * w + (size_t)nearest_src(y, h, oh) * w + nearest_src(x, w, ow)];
+  }
+}
+
+// linear weights of torch's upsample (align_corners = False, no scale given): src = max(scale*(dst+0.5)-0.5, 0), index floor clamped to
+// in-1, lambda clamped to [0,1], the second tap one further unless at the border
+__device__ __forceinline__ void lin_tap(int dst, int in, float scale, int& i0, int& i1, float& l0, float& l1) {
+  float src = scale * ((float)dst + 0.5f) - 0.5f;
+  if (src < 0.f) src = 0.f;
+  i0 = min((int)floorf(src), in - 1);
+  float lam = src - (float)i0;
+  lam = fminf(fmaxf(lam, 0.f), 1.f);
+  i1 = i0 + (i0 < in - 1 ? 1 : 0);
+  l1 = lam;
+  l0 = 1.f - lam;
+}
+
+// paste_masks_in_image for the D detections of one image: out [D, H, W], every pixel written once.
+__global__ __launch_bounds__(256) void paste_masks_kernel(const float* __restrict__ masks, const float* __restrict__ boxes, int D, int M, int pad,
+                                                          int H, int W, float* __restrict__ out) {
+  const long long total = (long long)D * H * W;
+  const int Mp = M + 2 * pad;
+  const float scale = (float)((double)Mp / (double)M);            // expand_masks: float(M + 2*pad) / M, applied to float32 boxes
+  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int x = (int)(i % W);
+    const int y = (int)((i / W) % H);
+    const int d = (int)(i / ((long long)W * H));
+    const float* bx = boxes + 4 * (size_t)d;
+    // expand_boxes, then .to(int64) (truncation)
+    float w_half = (bx[2] - bx[0]) * 0.5f, h_half = (bx[3] - bx[1]) * 0.5f;
+    const float x_c = (bx[2] + bx[0]) * 0.5f, y_c = (bx[3] + bx[1]) * 0.5f;
+    w_half *= scale;
+    h_half *= scale;
+    const long long b0 = (long long)(x_c - w_half), b2 = (long long)(x_c + w_half);
+    const long long b1 = (long long)(y_c - h_half), b3 = (long long)(y_c + h_half);
+    const long long bw = max(b2 - b0 + 1, 1ll), bh = max(b3 - b1 + 1, 1ll);
+    const long long x0 = max(b0, 0ll), x1 = min(b2 + 1, (long long)W), y0 = max(b1, 0ll), y1 = min(b3 + 1, (long long)H);
+    float v = 0.f;
+    if (x >= x0 && x < x1 && y >= y0 && y < y1) {
+      const int iy = (int)(y - b1), ix = (int)(x - b0);
+      int ya, yb, xa, xb;
+      float wy0, wy1, wx0, wx1;
+      lin_tap(iy, Mp, (float)Mp / (float)bh, ya, yb, wy0, wy1);
+      lin_tap(ix, Mp, (float)Mp / (float)bw, xa, xb, wx0, wx1);
+      const float* m = masks + (size_t)d * M * M;
+      auto at = [&](int yy, int xx) -> float {          // the zero-padded (M + 2 pad)^2 mask of expand_masks
+        yy -= pad;
+        xx -= pad;
+        return (yy >= 0 && yy < M && xx >= 0 && xx < M) ? m[yy * M + xx] : 0.f;
+      };
+      const float t0 = at(ya, xa) * wx0 + at(ya, xb) * wx1;
+      const float t1 = at(yb, xa) * wx0 + at(yb, xb) * wx1;
+      v = t0 * wy0 + t1 * wy1;
+    }
+    out[i] = v;
+  }
+}
+
+inline int grid_for(long long total) { return (int)min((long long)256 * 64, max((total + 255) / 256, 1ll)); }
+
+}  // namespace
+
+extern "C" {
+
+int mi355det_mask_roi_pool(const void* const* feats, const int32_t* hs, const int32_t* ws, const int32_t* lds, const float* scales,
+                           int32_t num_levels, const float* rois, int32_t num_rois, int32_t channels, int32_t pooled_h, int32_t pooled_w,
+                           int32_t sampling_ratio, int32_t k_min, int32_t k_max, void* out, int32_t out_ld, const void* grad_out,
+                           int32_t grad_ld, float* const* grad_feats, void* stream) {
+  if (num_levels < 1 || num_levels > 4 || num_rois < 0 || channels <= 0 || pooled_h <= 0 || pooled_w <= 0 || !feats || !hs || !ws || !scales)
+    return fail(MI355DET_EINVAL, "%s: bad arguments", "mask_roi_pool");
+  const bool bwd = grad_out != nullptr;
+  if (bwd != (grad_feats != nullptr) || (!bwd && !out)) return fail(MI355DET_EINVAL, "%s: give out, or grad_out with grad_feats", "mask_roi_pool");
+  if ((!bwd && out_ld < channels) || (bwd && grad_ld < channels)) return fail(MI355DET_EINVAL, "%s: pitch below the channel count", "mask_roi_pool");
+  if (num_rois == 0) return MI355DET_OK;
+  MaskLevels L{};
+  for (int q = 0; q < num_levels; ++q) {
+    L.feat[q] = (const bf16_t*)feats[q];
+    L.grad[q] = bwd ? grad_feats[q] : nullptr;
+    L.h[q] = hs[q];
+    L.w[q] = ws[q];
+    L.ld[q] = lds ? lds[q] : channels;
+    L.scale[q] = scales[q];
+  }
+  const long long total = (long long)num_rois * channels * pooled_h * pooled_w;
+  const int blocks = (int)min((long long)256 * 32, (total + 255) / 256);
+  if (bwd)
+    hipLaunchKernelGGL(mask_roi_pool_kernel<true>, dim3(blocks), dim3(256), 0, S(stream), L, num_levels, rois, num_rois, channels, pooled_h,
+                       pooled_w, sampling_ratio, k_min, k_max, nullptr, 0, (const bf16_t*)grad_out, grad_ld);
+  else
+    hipLaunchKernelGGL(mask_roi_pool_kernel<false>, dim3(blocks), dim3(256), 0, S(stream), L, num_levels, rois, num_rois, channels, pooled_h,
+                       pooled_w, sampling_ratio, k_min, k_max, (bf16_t*)out, out_ld, nullptr, 0);
+  return check_launch("mask_roi_pool");
+}
+
+int mi355det_mask_targets(const mi355det_mask_images* images, const float* rois, const int64_t* gt_index, int32_t num_rois, int32_t m,
+                          float* out, void* stream) {
+  if (!images || images->n_images < 1 || images->n_images > MI355DET_MASK_MAX_IMAGES || num_rois < 0 || m <= 0)
+    return fail(MI355DET_EINVAL, "%s: bad arguments", "mask_targets");
+  if (num_rois == 0) return MI355DET_OK;
+  MaskImages I{};
+  for (int b = 0; b < images->n_images; ++b) {
+    if (images->h[b] <= 0 || images->w[b] <= 0) return fail(MI355DET_EINVAL, "%s: image %lld: bad mask size", "mask_targets", b);
+    I.masks[b] = images->masks[b];
+    I.h[b] = images->h[b];
+    I.w[b] = images->w[b];
+  }
+  const long long total = (long long)num_rois * m * m;
+  hipLaunchKernelGGL(mask_targets_kernel, dim3(grid_for(total)), dim3(256), 0, S(stream), I, images->n_images, rois, gt_index, num_rois, m, out);
+  return check_launch("mask_targets");
+}
+
+size_t mi355det_mask_loss_workspace(int32_t rows) { return rows > 0 ? (size_t)rows * MASK_PART * sizeof(float) : 0; }
+
+int mi355det_mask_loss(const void* feat, int32_t feat_ld, const float* w_logits, const float* b_logits, const int64_t* labels,
+                       const float* targets, int32_t rows, int32_t valid, int32_t num_classes, float* loss, void* dfeat, float* dw,
+                       float* db, float* dbias_deconv, void* workspace, size_t workspace_bytes, void* stream) {
+  if (rows < 0 || valid < 0 || valid > rows || num_classes < 1 || feat_ld < 1024 || feat_ld % 4 || !loss)
+    return fail(MI355DET_EINVAL, "%s: bad arguments", "mask_loss");
+  if (rows > 0 && (!feat || !dfeat || !labels || !targets || !w_logits || !b_logits))
+    return fail(MI355DET_EINVAL, "%s: missing operand", "mask_loss");
+  if (workspace_bytes < mi355det_mask_loss_workspace(rows) || (rows > 0 && !workspace))
+    return fail(MI355DET_EWORKSPACE, "%s: workspace too small", "mask_loss");
+  const float inv_n = valid > 0 ? 1.0f / ((float)valid * 784.0f) : 0.f;
+  if (rows > 0)
+    hipLaunchKernelGGL(mask_loss_kernel<true>, dim3(rows), dim3(256), 0, S(stream), (const bf16_t*)feat, feat_ld, w_logits, b_logits, labels,
+                       num_classes, valid, targets, inv_n, (bf16_t*)dfeat, (float*)workspace, nullptr);
+  // valid == 0: the finish writes loss 0 and zero gradients (roi_heads.py:175-178: mask_logits.sum() * 0)
+  hipLaunchKernelGGL(mask_loss_finish_kernel, dim3(num_classes + 2), dim3(256), 0, S(stream), (const float*)workspace, labels, valid, num_classes,
+                     valid > 0 ? 1.0f / ((float)valid * 784.0f) : 0.f, loss, dw, db, dbias_deconv);
+  return check_launch("mask_loss");
+}
+
+int mi355det_mask_probs(const void* feat, int32_t feat_ld, const float* w_logits, const float* b_logits, const int64_t* labels, int32_t rows,
+                        int32_t num_classes, float* probs, void* stream) {
+  if (rows < 0 || num_classes < 1 || feat_ld < 1024 || feat_ld % 4) return fail(MI355DET_EINVAL, "%s: bad arguments", "mask_probs");
+  if (rows == 0) return MI355DET_OK;
+  if (!feat || !w_logits || !b_logits || !labels || !probs) return fail(MI355DET_EINVAL, "%s: missing operand", "mask_probs");
+  hipLaunchKernelGGL(mask_loss_kernel<false>, dim3(rows), dim3(256), 0, S(stream), (const bf16_t*)feat, feat_ld, w_logits, b_logits, labels,
+                     num_classes, rows, nullptr, 0.f, nullptr, nullptr, probs);
+  return check_launch("mask_probs");
+}
+
+int mi355det_mask_resize_nearest(const uint8_t* in, int32_t planes, int32_t h, int32_t w, uint8_t* out, int32_t out_h, int32_t out_w,
+                                 void* stream) {
+  if (planes < 0 || h <= 0 || w <= 0 || out_h <= 0 || out_w <= 0) return fail(MI355DET_EINVAL, "%s: bad arguments", "mask_resize_nearest");
+  if (planes == 0) return MI355DET_OK;
+  const long long total = (long long)planes * out_h * out_w;
+  hipLaunchKernelGGL(mask_resize_nearest_kernel, dim3(grid_for(total)), dim3(256), 0, S(stream), in, planes, h, w, out, out_h, out_w);
+  return check_launch("mask_resize_nearest");
+}
+
+int mi355det_paste_masks(const float* masks, const float* boxes, int32_t num_masks, int32_t m, int32_t padding, int32_t im_h, int32_t im_w,
+                         float* out, void* stream) {
+  if (num_masks < 0 || m <= 0 || padding < 0 || im_h <= 0 || im_w <= 0) return fail(MI355DET_EINVAL, "%s: bad arguments", "paste_masks");
+  if (num_masks == 0) return MI355DET_OK;
+  const long long total = (long long)num_masks * im_h * im_w;
+  hipLaunchKernelGGL(paste_masks_kernel, dim3(grid_for(total)), dim3(256), 0, S(stream), masks, boxes, num_masks, m, padding, im_h, im_w, out);
+  return check_launch("paste_masks");
+}
+
+}  // extern "C"

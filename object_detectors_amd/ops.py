@@ -495,6 +495,13 @@ def conv_dgrad(shape, dy, w_dgrad, dx, residual=None, residual_ld=0):
           "conv_dgrad")
 
 
+def conv_dgrad_mask(shape, dy, w_dgrad, dx, act, act_ld=None, scale=None, relu=True):
+    """dx = bf16(conv2d_input(dy)) * scale * (act > 0): the data gradient with the ReLU (/ frozen affine) backward of the layer that produced
+    the convolution's input folded in (stride 1)."""
+    check(lib().mi355det_conv_dgrad_mask(C.byref(shape), ptr(dy), ptr(w_dgrad), ptr(dx), ptr(act), int(act_ld or shape.in_ld), ptr(scale),
+                                         int(bool(relu)), stream_ptr()), "conv_dgrad_mask")
+
+
 _WGRAD_WS = {}
 
 
@@ -723,3 +730,121 @@ def fastrcnn_loss(class_logits, box_regression, labels, regression_targets, clas
     check(L.mi355det_fastrcnn_loss(ptr(x), ptr(b), ptr(lab), ptr(tgt), ptr(cs), ptr(cw), n, k, FRCNN_LOSS_TYPES[loss_type], ptr(losses), ptr(gl),
                                    ptr(gb), ptr(ws), wsb, stream_ptr()), "fastrcnn_loss")
     return losses, gl, gb
+
+
+# ------------------------------------------------------------------------------------ Mask R-CNN mask branch (csrc/mask_kernels.hip)
+def _level_tables(feats, scales):
+    nl = len(feats)
+    for f in feats:
+        if f.dtype != torch.bfloat16 or f.dim() != 4 or f.stride(3) != 1:
+            raise ValueError("mask_roi_pool expects bf16 [n,h,w,C] tensors with contiguous channels")
+    return (nl, (C.c_void_p * nl)(*[f.data_ptr() for f in feats]), (C.c_int32 * nl)(*[f.shape[1] for f in feats]),
+            (C.c_int32 * nl)(*[f.shape[2] for f in feats]), (C.c_int32 * nl)(*[f.stride(2) for f in feats]),
+            (C.c_float * nl)(*[float(s) for s in scales]))
+
+
+def mask_roi_pool(feats, rois, scales, k_min, k_max, output_size=14, sampling_ratio=2, out=None):
+    """MultiScaleRoIAlign(['0'..'3'], 14, 2) into bf16 NHWC [K, 14, 14, C] (mask_fcn1's input); == bf16(roi_align_nhwc) bit for bit."""
+    rois = _f32c(rois)
+    nl, P, hs, ws, lds, sc = _level_tables(feats, scales)
+    K, Cc = rois.shape[0], feats[0].shape[3]
+    if out is None:
+        out = torch.empty((K, output_size, output_size, Cc), device=rois.device, dtype=torch.bfloat16)
+    check(lib().mi355det_mask_roi_pool(P, hs, ws, lds, sc, nl, ptr(rois), K, Cc, output_size, output_size, int(sampling_ratio), k_min, k_max,
+                                       ptr(out), out.stride(2), None, 0, None, stream_ptr()), "mask_roi_pool")
+    return out
+
+
+def mask_roi_pool_bwd(feats, rois, scales, k_min, k_max, grad, num_rois=None, sampling_ratio=2, grad_feats=None):
+    """Backward of mask_roi_pool: grad bf16 NHWC [K, ph, pw, C] (rows >= num_rois are skipped) -> fp32 NHWC feature gradients (fp32 atomics;
+    accumulated into grad_feats when given)."""
+    rois = _f32c(rois)
+    nl, P, hs, ws, lds, sc = _level_tables(feats, scales)
+    K = rois.shape[0] if num_rois is None else int(num_rois)
+    Cc = feats[0].shape[3]
+    if grad.dtype != torch.bfloat16 or grad.stride(3) != 1:
+        raise ValueError("mask_roi_pool_bwd: grad must be bf16 NHWC with contiguous channels")
+    if grad_feats is None:
+        grad_feats = [torch.zeros((f.shape[0], f.shape[1], f.shape[2], Cc), device=f.device, dtype=torch.float32) for f in feats]
+    G = (C.c_void_p * nl)(*[d.data_ptr() for d in grad_feats])
+    check(lib().mi355det_mask_roi_pool(P, hs, ws, lds, sc, nl, ptr(rois), K, Cc, grad.shape[1], grad.shape[2], int(sampling_ratio), k_min, k_max,
+                                       None, 0, ptr(grad), grad.stride(2), G, stream_ptr()), "mask_roi_pool_bwd")
+    return grad_feats
+
+
+def mask_targets(masks, rois, gt_index, m=28, num_rois=None):
+    """project_masks_on_boxes for a whole batch in one launch: masks = per-image uint8 [G_b, h_b, w_b]; rois [R,5] = (image, box);
+    gt_index [R] int64 = matched gt inside the image -> fp32 [R, m, m] (rows >= num_rois are left unwritten)."""
+    rois = _f32c(rois)
+    if len(masks) > _lib.MASK_MAX_IMAGES:
+        raise ValueError(f"mask_targets: at most {_lib.MASK_MAX_IMAGES} images")
+    imgs = _lib.MaskImages()
+    keep = []
+    for b, mk in enumerate(masks):
+        mk = mk.to(torch.uint8).contiguous()
+        if mk.dim() != 3 or not mk.is_cuda:
+            raise ValueError("mask_targets: masks must be CUDA uint8 [G, h, w] per image")
+        keep.append(mk)
+        imgs.masks[b], imgs.h[b], imgs.w[b] = mk.data_ptr() if mk.numel() else None, mk.shape[1], mk.shape[2]
+    imgs.n_images = len(masks)
+    R = rois.shape[0] if num_rois is None else int(num_rois)
+    out = torch.empty((rois.shape[0], m, m), device=rois.device, dtype=torch.float32)
+    check(lib().mi355det_mask_targets(C.byref(imgs), ptr(rois), ptr(gt_index.to(torch.int64).contiguous()), R, m, ptr(out), stream_ptr()),
+          "mask_targets")
+    return out
+
+
+def mask_loss(feat, w_logits, b_logits, labels, targets, valid, dfeat=None):
+    """maskrcnn_loss fused with mask_fcn_logits on the label channel.  feat: bf16 deconvolution output (after ReLU) [rows, 14, 14, 1024] in
+    sub-pixel order; labels [rows] int64; targets [rows, 28, 28]; valid = real rows (the rest is bucket padding).
+    -> (loss [1], dfeat (gradient before the deconvolution's ReLU), dw [K, 256], db [K], dbias_deconv [256])."""
+    rows = feat.shape[0]
+    K = w_logits.shape[0]
+    ld = feat.stride(2) if feat.dim() == 4 else feat.shape[-1]
+    if feat.dtype != torch.bfloat16 or feat.shape[-1] != 1024 or w_logits.shape[1] != 256:
+        raise ValueError("mask_loss: feat must be bf16 [rows, 14, 14, 1024], w_logits [K, 256]")
+    dev = feat.device
+    wl, bl = _f32c(w_logits), _f32c(b_logits)
+    L = lib()
+    wsb = L.mi355det_mask_loss_workspace(rows)
+    ws = torch.empty(max(wsb, 4), dtype=torch.uint8, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    if dfeat is None:
+        dfeat = torch.empty_like(feat)
+    dw = torch.empty((K, 256), dtype=torch.float32, device=dev)
+    db = torch.empty(K, dtype=torch.float32, device=dev)
+    dbias = torch.empty(256, dtype=torch.float32, device=dev)
+    check(L.mi355det_mask_loss(ptr(feat), ld, ptr(wl), ptr(bl), ptr(labels.to(torch.int64).contiguous()), ptr(_f32c(targets)), rows, int(valid), K,
+                               ptr(loss), ptr(dfeat), ptr(dw), ptr(db), ptr(dbias), ptr(ws), wsb, stream_ptr()), "mask_loss")
+    return loss, dfeat, dw, db, dbias
+
+
+def mask_probs(feat, w_logits, b_logits, labels):
+    """maskrcnn_inference: sigmoid of the label channel of mask_fcn_logits -> fp32 [rows, 28, 28]."""
+    rows = feat.shape[0]
+    ld = feat.stride(2) if feat.dim() == 4 else feat.shape[-1]
+    probs = torch.empty((rows, 28, 28), dtype=torch.float32, device=feat.device)
+    check(lib().mi355det_mask_probs(ptr(feat), ld, ptr(_f32c(w_logits)), ptr(_f32c(b_logits)), ptr(labels.to(torch.int64).contiguous()), rows,
+                                    w_logits.shape[0], ptr(probs), stream_ptr()), "mask_probs")
+    return probs
+
+
+def mask_resize_nearest(masks, size):
+    """F.interpolate(masks[:, None].float(), size, mode='nearest')[:, 0].byte() for uint8 [G, h, w] (transform.py:54-60)."""
+    m = masks.to(torch.uint8).contiguous()
+    if not m.is_cuda:
+        raise ValueError("mask_resize_nearest needs CUDA/HIP tensors (no CPU fallback)")
+    oh, ow = int(size[0]), int(size[1])
+    out = torch.empty((m.shape[0], oh, ow), dtype=torch.uint8, device=m.device)
+    check(lib().mi355det_mask_resize_nearest(ptr(m), m.shape[0], m.shape[1], m.shape[2], ptr(out), oh, ow, stream_ptr()), "mask_resize_nearest")
+    return out
+
+
+def paste_masks(masks, boxes, img_shape, padding=1):
+    """paste_masks_in_image (roi_heads.py:517-537): masks [D, 1, M, M] fp32, boxes [D, 4] -> [D, 1, H, W] fp32."""
+    m = _f32c(masks)
+    D, M = m.shape[0], m.shape[-1]
+    H, W = int(img_shape[0]), int(img_shape[1])
+    out = torch.empty((D, 1, H, W), dtype=torch.float32, device=m.device)
+    check(lib().mi355det_paste_masks(ptr(m), ptr(_f32c(boxes)), D, M, int(padding), H, W, ptr(out), stream_ptr()), "paste_masks")
+    return out

@@ -219,6 +219,7 @@ class FasterRCNN(nn.Module):
         if not self.training and _RPN_FUSED and _ROI_DET_FUSED:
             det = self._detect_padded(out, plan, image_shapes)
             if det is not None:
+                det = self._roi_extra_eval(self.engine.feature_maps_nhwc(4), det, image_shapes)
                 if original_image_sizes is not None:
                     det = self.transform.postprocess(det, image_shapes, original_image_sizes)      # generalized_rcnn.py:110
                 return det
@@ -236,6 +237,7 @@ class FasterRCNN(nn.Module):
                 b, s, l = roi_heads_postprocess_detections(cls, reg, boxes, image_shapes, self.tfidf_post, self.box_score_thresh,
                                                            self.box_nms_thresh, self.box_detections_per_img, self.bbox_reg_weights, self.loss_type)
             det = [{"boxes": bb, "labels": ll, "scores": ss} for bb, ll, ss in zip(b, l, s)]
+            det = self._roi_extra_eval(feats, det, image_shapes)
             if original_image_sizes is not None:
                 det = self.transform.postprocess(det, image_shapes, original_image_sizes)      # generalized_rcnn.py:110
             return det
@@ -265,6 +267,7 @@ class FasterRCNN(nn.Module):
             rpn_losses = self.rpn_targets.losses_prepared(obj, dl, rpn_side)
         losses = {"loss_classifier": loss_cls, "loss_box_reg": loss_box}
         losses.update(rpn_losses)
+        extra_fgrads = self._roi_extra_train(feats, proposals, _mi, labels, targets, image_shapes, fused, losses)
         if obj_grad is not None:
             (loss_cls + loss_box).backward()
         else:
@@ -272,8 +275,19 @@ class FasterRCNN(nn.Module):
             obj_grad, dl_grad = obj.grad, dl.grad
         if getattr(self, "head_grad_sync", None) is not None:     # data parallel: parallel.ParamGradSync over head_parameters(), overlapped with
             self.head_grad_sync.reduce()                          # the whole backbone backward below
-        self.engine.backward(obj_grad, dl_grad, [f.grad for f in feats])
+        fgrads = [f.grad for f in feats]
+        if extra_fgrads is not None:          # fp32 NHWC feature gradients of another RoI branch (Mask R-CNN): summed before the bf16 rounding
+            fgrads = [e if g is None else e.add_(g) for g, e in zip(fgrads, extra_fgrads)]
+        self.engine.backward(obj_grad, dl_grad, fgrads)
         return {k: v.detach() for k, v in losses.items()}
+
+    # ---- extension points of the RoI heads (roi_heads.py:844-887): Faster R-CNN has no further branch
+    def _roi_extra_train(self, feats, proposals, matched_idxs, labels, targets, image_shapes, fused, losses):
+        """Adds its losses to `losses` (gradients already computed) and returns fp32 NHWC feature gradients per level, or None."""
+        return None
+
+    def _roi_extra_eval(self, feats, detections, image_shapes):
+        return detections
 
 
 def fasterrcnn_resnet50_fpn(pretrained=False, progress=True, num_classes=91, pretrained_backbone=False, trainable_backbone_layers=None, tfidf=None,

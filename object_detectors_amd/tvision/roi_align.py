@@ -75,6 +75,18 @@ class MultiScaleRoIAlign(nn.Module):
         k_min, k_max = int(-math.log2(scales[0])), int(-math.log2(scales[-1]))
         return _RoIAlignFn.apply(_rois_tensor(boxes), self.output_size, scales, self.sampling_ratio, False, k_min, k_max, *feats)
 
+    def levels_nhwc(self, feats, image_shapes):
+        """(scales, k_min, k_max) of bf16 NHWC maps [n,h,w,C] (infer_scale + LevelMapper bounds), as forward_nhwc derives them."""
+        max_h = max(s[0] for s in image_shapes)
+        max_w = max(s[1] for s in image_shapes)
+        scales = []
+        for f in feats:
+            sh = 2.0 ** round(math.log2(f.shape[1] / max_h))
+            sw = 2.0 ** round(math.log2(f.shape[2] / max_w))
+            assert sh == sw
+            scales.append(sh)
+        return scales, int(-math.log2(scales[0])), int(-math.log2(scales[-1]))
+
     def forward_nhwc(self, feats, boxes, image_shapes):
         """Same pooling on bf16 NHWC feature maps [n,h,w,C] (list, finest first): no layout conversion, coalesced backward."""
         if len(feats) > 4:

@@ -122,6 +122,7 @@ class RoIHeadTargets:
             num_neg.append(min(cn, bs - npos))
             perm_pos.append(torch.randperm(cp, device=dev))
             perm_neg.append(torch.randperm(cn, device=dev))
+        self.last_num_pos = num_pos                           # host counts of the positives (the mask branch's row count, no extra read)
         rois, out_l, out_m, reg = ops.roi_sample(proposals_pad, meta[:n], gt_all, offs, matched, labels, perm_pos, perm_neg, num_pos, num_neg,
                                                  self.box_coder.weights)
         return rois, out_m, out_l, reg, [a + b for a, b in zip(num_pos, num_neg)]

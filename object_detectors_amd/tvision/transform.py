@@ -39,6 +39,19 @@ def resized_size(h, w, self_min_size, self_max_size):
     return int(math.floor(float(h) * scale)), int(math.floor(float(w) * scale))
 
 
+def mask_resize_nearest(masks, size):
+    """The masks part of `_resize_image_and_masks` (transform.py:54-60): F.interpolate(masks[:, None].float(), scale_factor, nearest,
+    recompute_scale_factor=True)[:, 0].byte() - the output size is the image's (same floor of the double product)."""
+    from ..ops import mask_resize_nearest as _resize
+    return _resize(masks, size)
+
+
+def paste_masks(masks, boxes, img_shape, padding=1):
+    """paste_masks_in_image (roi_heads.py:517-537), all detections of one image in one launch."""
+    from ..ops import paste_masks as _paste
+    return _paste(masks, boxes, img_shape, padding)
+
+
 def resize_boxes(boxes, original_size, new_size):
     """transform.py:279-293."""
     if boxes.numel() == 0:
@@ -100,14 +113,19 @@ class GeneralizedRCNNTransform(torch.nn.Module):
                                              stream_ptr()), "resize_bilinear")
             if targets is not None and targets[i] is not None and "boxes" in targets[i]:
                 targets[i]["boxes"] = resize_boxes(targets[i]["boxes"], (int(img.shape[-2]), int(img.shape[-1])), (oh, ow))
+            if targets is not None and targets[i] is not None and "masks" in targets[i]:      # transform.py:54-60 (nearest, uint8)
+                targets[i]["masks"] = mask_resize_nearest(targets[i]["masks"], (oh, ow))
         return ImageList(batch, sizes), targets
 
     def postprocess(self, result, image_shapes, original_image_sizes):
-        """transform.py:228-247 (boxes only: no mask / keypoint branch on this path)."""
+        """transform.py:228-247 (boxes, and masks when the result has them; no keypoint branch on this path)."""
         if self.training:
             return result
         for i, (pred, im_s, o_im_s) in enumerate(zip(result, image_shapes, original_image_sizes)):
-            result[i]["boxes"] = resize_boxes(pred["boxes"], im_s, o_im_s)
+            boxes = resize_boxes(pred["boxes"], im_s, o_im_s)
+            result[i]["boxes"] = boxes
+            if "masks" in pred:
+                result[i]["masks"] = paste_masks(pred["masks"], boxes, o_im_s)
         return result
 
 
