@@ -118,7 +118,7 @@ class GradSync:
 
     def install(self, plan):
         """Weave bucket all-reduces into a training plan's backward call list (idempotent per plan)."""
-        from .yolo.nets.engine import comm_hook
+        from .plan_core import comm_hook
         if getattr(plan, "_gradsync", None) is self:
             return
         buckets = plan_buckets(plan.bwd_marks, self.flat.numel(), self.bucket_elems)

@@ -18,9 +18,9 @@ import os
 
 import torch
 
-from .. import _lib, ops, tune
+from .. import _lib, ops
 from .._lib import check, lib
-from ..yolo.nets.engine import Act, comm_hook, _vp
+from ..plan_core import Act, BackwardSchedule, GradAccumulator, PlanBase, _vp, build_pack_table, cached_plan, check_images, comm_hook
 from .anchor_utils import AnchorGenerator
 
 LAYERS = [3, 4, 6, 3]
@@ -31,6 +31,7 @@ IMAGE_MEAN = (0.485, 0.456, 0.406)
 IMAGE_STD = (0.229, 0.224, 0.225)
 ANCHOR_SIZES = tuple((x, int(x * 2 ** (1.0 / 3)), int(x * 2 ** (2.0 / 3))) for x in [32, 64, 128, 256, 512])   # retinanet.py:647
 ASPECT_RATIOS = ((0.5, 1.0, 2.0),) * 5
+SIZE_DIVISIBLE = " (GeneralizedRCNNTransform.batch_images size_divisible)"
 
 
 class Conv:
@@ -224,27 +225,13 @@ class RetinaNetEngine:
                 self.affine[s.bn][1].copy_(b - rm * scale)
         self._pack([s for s in self.specs if not s.trainable], need_dgrad=False)
 
-    def _pack_table(self, specs, need_dgrad):
-        L = lib()
-        items = (_lib.PackItem * max(1, len(specs)))()
-        for i, s in enumerate(specs):
-            wf, wd = self.packed[s.name]
-            items[i].w = self.params[s.name + ".weight"].data_ptr()
-            items[i].w_fwd = wf.data_ptr()
-            items[i].w_dgrad = wd.data_ptr() if (need_dgrad and wd is not None) else None
-            items[i].shape = self._shape(s, 1, 8, 8)
-            items[i].cout_pad = ops.cout_pad_of(s.cout)
-            items[i].w_is_ohwi = 1
-        ne, nb = C.c_int32(0), C.c_int32(0)
-        nbytes = L.mi355det_pack_table_bytes(items, len(specs), C.byref(ne), C.byref(nb))
-        host = torch.empty(max(nbytes, 1), dtype=torch.uint8)
-        check(L.mi355det_pack_table_build(items, len(specs), C.c_void_p(host.data_ptr()), nbytes), "pack_table_build")
-        return host.to(self.device), ne.value, nb.value
+    def _pack_shape(self, s):
+        return self._shape(s, 1, 8, 8), ops.cout_pad_of(s.cout)
 
     def _pack(self, specs, need_dgrad):
         if not specs:
             return
-        tab, ne, nb = self._pack_table(specs, need_dgrad)
+        tab, ne, nb = build_pack_table(lib(), self, specs, self._pack_shape, need_dgrad)
         check(lib().mi355det_pack_weights_batched(_vp(tab), ne, nb, C.c_void_p(torch.cuda.current_stream().cuda_stream)), "pack_weights_batched")
         torch.cuda.current_stream().synchronize()      # `tab` is freed on return
 
@@ -253,29 +240,15 @@ class RetinaNetEngine:
 
     def plan(self, n, H, W, training):
         key = (n, H, W, bool(training), bool(self.normalize), torch.cuda.current_stream().cuda_stream)
-        p = self.plans.pop(key, None)
-        if p is None:
-            while len(self.plans) >= self.MAX_PLANS:
-                torch.cuda.current_stream().synchronize()           # nothing of the evicted plan may still be running
-                self.plans.pop(next(iter(self.plans)))
-            # (tune.plan_build: MI355DET_TUNE_LOAD / _SAVE; for N > 1 rank 0's timing choices are broadcast - a collective, so only for training
-            #  plans of an engine with a GradSync attached: plans every rank is known to build)
-            dp = bool(training and getattr(self, "grad_syncs", ()))
-            p = tune.plan_build(lambda: RetinaPlan(self, n, H, W, training, key[-1]), share=None if dp else False)
-            if training:
-                for gs in getattr(self, "grad_syncs", ()):       # parallel.GradSync.attach(): every plan gets the bucket hooks
-                    gs.install(p)
-        self.plans[key] = p                                          # most recently used last
-        return p
+        # (tune.plan_build: MI355DET_TUNE_LOAD / _SAVE; for N > 1 rank 0's timing choices are broadcast - a collective, so only for training
+        #  plans of an engine with a GradSync attached: plans every rank is known to build)
+        dp = bool(training and getattr(self, "grad_syncs", ()))
+        return cached_plan(self, key, lambda: RetinaPlan(self, n, H, W, training, key[-1]), training, dp)
 
     def forward(self, images, training=None):
         """images [n,3,H,W] fp32 in 0..1 (already resized/batched) -> {'cls_logits': [n, sum HWA, K], 'bbox_regression': [n, sum HWA, 4]}."""
         training = self.training if training is None else training
-        if images.dim() != 4 or images.shape[1] != 3 or not images.is_cuda:
-            raise ValueError("expected a CUDA tensor [n,3,H,W]")
-        n, _, H, W = images.shape
-        if H % 32 or W % 32:
-            raise ValueError("input size must be a multiple of 32 (GeneralizedRCNNTransform.batch_images size_divisible)")
+        n, H, W = check_images(images, SIZE_DIVISIBLE)
         p = self.plan(n, H, W, training)
         p.run_forward(images.float().contiguous())
         self._last_plan = p
@@ -296,11 +269,7 @@ class RetinaNetEngine:
         # Everything that depends only on the ground truth is issued BEFORE the network forward: the matching kernels run first on an idle
         # device, and the host-to-device copy of the offsets (stream-ordered: built after the forward it made the host wait for the whole
         # forward, 8 ms at batch 16, and issue the loss and the backward behind it with the device idle for ~1 ms) costs nothing there.
-        if images.dim() != 4 or images.shape[1] != 3 or not images.is_cuda:
-            raise ValueError("expected a CUDA tensor [n,3,H,W]")
-        if images.shape[2] % 32 or images.shape[3] % 32:
-            raise ValueError("input size must be a multiple of 32 (GeneralizedRCNNTransform.batch_images size_divisible)")
-        p = self.plan(images.shape[0], images.shape[2], images.shape[3], True)
+        p = self.plan(*check_images(images, SIZE_DIVISIBLE), True)
         counts = [int(t["boxes"].shape[0]) for t in targets]
         offs_host = torch.tensor([0] + [sum(counts[:i + 1]) for i in range(len(counts))], dtype=torch.int32).pin_memory()
         offs = offs_host.to(self.device, non_blocking=True)
@@ -379,24 +348,14 @@ class FasterRCNNEngine(RetinaNetEngine):
         p.run_backward()
 
 
-class RetinaPlan:
-    """Buffers + prepared call lists for one (batch, H, W, mode)."""
-
+class RetinaPlan(PlanBase):
     def __init__(self, eng, n, H, W, training, stream):
-        self.eng, self.n, self.H, self.W, self.training = eng, n, H, W, training
-        self.stream = C.c_void_p(stream)
-        self.fwd, self.bwd, self.pack = [], [], []
-        self.keep = []
-        self.ops = []
-        self.layers = {}
-        dev, L, bf = eng.device, lib(), torch.bfloat16
+        super().__init__(eng, lib(), n, H, W, training, stream)
+        dev, L, bf = eng.device, self.L, torch.bfloat16
         A, K = eng.na, eng.nc
 
         def new_act(n_, h_, w_, c_, needs_grad):
-            a = Act(torch.zeros((n_, h_, w_, c_), device=dev, dtype=bf), n_, h_, w_, c_, c_)
-            a.needs_grad = needs_grad
-            a.parts = []
-            return a
+            return Act(torch.zeros((n_, h_, w_, c_), device=dev, dtype=bf), n_, h_, w_, c_, c_, needs_grad=needs_grad)
 
         # level geometry first: the heads write into level-concatenated outputs
         def down(v, times):
@@ -536,8 +495,7 @@ class RetinaPlan:
         # ---- weight packing of the trainable convolutions (every step: the optimizer changes the fp32 masters)
         tr = [s for s in eng.specs if s.trainable]
         if tr:
-            self.pack_table, ne, nb = eng._pack_table(tr, need_dgrad=training)
-            self.pack.append((L.mi355det_pack_weights_batched, (_vp(self.pack_table), ne, nb, self.stream)))
+            self.build_pack_table(tr, eng._pack_shape, need_dgrad=training)
         if training:
             self._build_backward()
             self._autotune()
@@ -546,7 +504,7 @@ class RetinaPlan:
 
     # ------------------------------------------------------------------
     def _build_backward(self):
-        eng, L, dev, bf = self.eng, lib(), self.eng.device, torch.bfloat16
+        eng, L, dev, bf = self.eng, self.L, self.eng.device, torch.bfloat16
         A, K, n = eng.na, eng.nc, self.n
         # bf16 head-gradient buffers per level (padded channel pitch), filled from the fp32 loss gradients by cast_rows
         self.head_grads = {}
@@ -563,39 +521,8 @@ class RetinaPlan:
                 if key == "bbox_reg":
                     self.cast_box.append(call)
         dz_elems = max(r["shp"].n * r["shp"].ho * r["shp"].wo * r["shp"].cout for r in self.ops if r["kind"] == "conv")
-        self.dz2 = [torch.zeros(dz_elems, device=dev, dtype=bf) for _ in range(2)]
-        self.side = torch.cuda.Stream(device=dev)
-        side_ptr = C.c_void_p(self.side.cuda_stream)
-        main = torch.cuda.current_stream(dev)
-        wg_done = [None, None]
-        flip = [0]
         ws_need = max(L.mi355det_conv_wgrad_workspace(C.byref(r["shp"])) for r in self.ops if r["kind"] == "conv")
-        self.wgrad_ws = torch.empty(max(ws_need, 16), device=dev, dtype=torch.uint8)
-        ws_ptr, ws_bytes = _vp(self.wgrad_ws), self.wgrad_ws.numel()
-
-        def py(fn, *a):
-            self.bwd.append((comm_hook, (fn,) + a))
-
-        # Every gradient buffer is OWNED by the plan (self.grad_bufs): the call list bakes raw device pointers, and a buffer that was only
-        # reachable through an activation's `parts` queue was freed as soon as the queue handed it to a call (residual of a data gradient,
-        # operand of an add) - the caching allocator then gave the block to whoever asked next (round 4 found the Faster R-CNN box head's
-        # weight packs, created in the first training call, overwritten by every later backward: tests/test_gpu_fullsize_tv.py).
-        self.grad_bufs = []
-
-        def dense(a):
-            g = Act(torch.zeros((a.n, a.h, a.w, a.c), device=dev, dtype=bf), a.n, a.h, a.w, a.c, a.c)
-            self.grad_bufs.append(g.buf)
-            return g
-
-        # ---- gradient bookkeeping: an activation's gradient is the sum of its consumers' contributions; tensors that already
-        #      exist are queued as `parts` so that the first data-gradient GEMM can take one as its epilogue residual
-        def add_tensor(x, t):
-            if not x.needs_grad:
-                return
-            if x.grad_written:
-                self.bwd.append((L.mi355det_add_bf16, (x.grad.ptr, x.grad.ld, t.ptr, t.ld, x.c, x.pixels, x.grad.ptr, x.grad.ld, self.stream)))
-            else:
-                x.parts.append(t)
+        sched = BackwardSchedule(self, dev, bf, dz_elems, ws_need)
 
         # split-K data gradients (few pixels, deep reduction: the LVIS cls_logits on the small levels) share one fp32 workspace; they run
         # one after the other on the main stream
@@ -606,6 +533,8 @@ class RetinaPlan:
             if self.dgrad_ws is not None and L.mi355det_conv_dgrad_workspace(C.byref(shp)):
                 return (L.mi355det_conv_dgrad_ws, (C.byref(shp), dy_ptr, _vp(wd), g.ptr, rptr, rld, _vp(self.dgrad_ws), self.dgrad_ws.numel(), self.stream))
             return (L.mi355det_conv_dgrad, (C.byref(shp), dy_ptr, _vp(wd), g.ptr, rptr, rld, self.stream))
+        acc = GradAccumulator(L, dev, bf, self, dgrad_call)
+        dense, add_tensor, finalize = acc.dense, acc.add_tensor, acc.finalize
 
         # ---- FrozenBN / ReLU backward folded into the data gradient that produces its input (mi355det_conv_dgrad_mask): possible when the
         #      activation has exactly ONE consumer, a stride-1 convolution, and its producer is a plain conv (+affine) (+ReLU) without a
@@ -635,45 +564,12 @@ class RetinaPlan:
             return pr
 
         def add_dgrad(x, shp, dy_ptr, wd):
-            if not x.needs_grad:
-                return
-            if x.grad is None:
-                x.grad = dense(x)
-            g = x.grad
-            pr = mask_fusable(x, shp)
-            if pr is not None:
-                self.bwd.append((L.mi355det_conv_dgrad_mask, (C.byref(shp), dy_ptr, _vp(wd), g.ptr, x.ptr, x.ld, _vp(pr["scale"]), int(pr["spec"].relu),
-                                                              self.stream)))
-                x.grad_written = True
-                pr["dz_fused"] = True                  # x.grad now holds dz of the producer, not the activation gradient
-                return
-            if x.grad_written:
-                self.bwd.append(dgrad_call(shp, dy_ptr, wd, g, g.ptr, g.ld))
-            else:
-                r = x.parts.pop(0) if x.parts else None
-                self.bwd.append(dgrad_call(shp, dy_ptr, wd, g, r.ptr if r else None, r.ld if r else 0))
-                x.grad_written = True
-                while x.parts:
-                    t = x.parts.pop(0)
-                    self.bwd.append((L.mi355det_add_bf16, (g.ptr, g.ld, t.ptr, t.ld, x.c, x.pixels, g.ptr, g.ld, self.stream)))
-
-        def finalize(a):
-            """Gradient of `a` once every consumer has contributed (ops are walked in reverse)."""
-            if a.grad_written:
-                return a.grad
-            if not a.parts:
-                return None
-            if len(a.parts) == 1:
-                a.grad = a.parts.pop(0)          # alias, no copy
-            else:
-                a.grad = dense(a)
-                p0, p1 = a.parts.pop(0), a.parts.pop(0)
-                self.bwd.append((L.mi355det_add_bf16, (p0.ptr, p0.ld, p1.ptr, p1.ld, a.c, a.pixels, a.grad.ptr, a.grad.ld, self.stream)))
-                while a.parts:
-                    t = a.parts.pop(0)
-                    self.bwd.append((L.mi355det_add_bf16, (a.grad.ptr, a.grad.ld, t.ptr, t.ld, a.c, a.pixels, a.grad.ptr, a.grad.ld, self.stream)))
-            a.grad_written = True
-            return a.grad
+            pr = mask_fusable(x, shp) if x.needs_grad else None
+            if pr is None:
+                return acc.add_dgrad(x, shp, dy_ptr, wd)
+            acc.add_dgrad(x, shp, dy_ptr, wd, lambda shp, dy_ptr, wd, g, _rptr, _rld: (
+                L.mi355det_conv_dgrad_mask, (C.byref(shp), dy_ptr, _vp(wd), g.ptr, x.ptr, x.ld, _vp(pr["scale"]), int(pr["spec"].relu), self.stream)))
+            pr["dz_fused"] = True                      # x.grad now holds dz of the producer, not the activation gradient
 
         self.bwd_marks = []
         first_off = {name: o for name, o, _n, _s in eng.param_order}
@@ -706,18 +602,9 @@ class RetinaPlan:
                 if g is None:
                     continue
                 add_tensor(rec["lat"], g)
-                top = rec["top"]
-                if top.needs_grad:
-                    if top.grad is None:
-                        top.grad = dense(top)
-                    acc = top.grad if top.grad_written else (top.parts.pop(0) if top.parts else None)
-                    self.bwd.append((L.mi355det_upsample_nearest_bwd, (g.ptr, g.ld, top.n, top.h, top.w, top.c, g.h, g.w, acc.ptr if acc else None,
-                                                                       acc.ld if acc else 0, top.grad.ptr, top.grad.ld, self.stream)))
-                    top.grad_written = True
-                    while top.parts:
-                        t = top.parts.pop(0)
-                        self.bwd.append((L.mi355det_add_bf16, (top.grad.ptr, top.grad.ld, t.ptr, t.ld, top.c, top.pixels, top.grad.ptr, top.grad.ld,
-                                                               self.stream)))
+                top = rec["top"]          # the upsample backward accumulates like a data gradient: residual in, gradient out
+                acc.add_dgrad(top, None, None, None, lambda _s, _d, _w, gt, rptr, rld: (
+                    L.mi355det_upsample_nearest_bwd, (g.ptr, g.ld, top.n, top.h, top.w, top.c, g.h, g.w, rptr, rld, gt.ptr, gt.ld, self.stream)))
                 continue
             if kind == "relu":
                 g = finalize(rec["a"])
@@ -748,10 +635,7 @@ class RetinaPlan:
                     gm = dense(a) if need_gm else None
                     fresh_dz = None
                     if need_dz:
-                        fresh_dz = flip[0]
-                        flip[0] ^= 1
-                        if wg_done[fresh_dz] is not None:
-                            py(main.wait_event, wg_done[fresh_dz])
+                        fresh_dz = sched.next_dz()
                     dzp = _vp(self.dz2[fresh_dz]) if need_dz else None
                     self.bwd.append((L.mi355det_relu_affine_bwd, (g.ptr, g.ld, None, 0, a.ptr, a.ld, _vp(scale), a.c, a.pixels, int(s.relu), dzp, a.c,
                                                                   gm.ptr if gm else None, gm.ld if gm else 0, self.stream)))
@@ -766,23 +650,13 @@ class RetinaPlan:
                     continue
             rec["dy_ptr"] = dy_ptr
             if s.trainable:
-                ev_dz, ev_wg = torch.cuda.Event(), torch.cuda.Event()
-                py(ev_dz.record, main)
-                py(self.side.wait_event, ev_dz)
-                self.bwd.append((L.mi355det_conv_wgrad, (C.byref(shp), x.ptr, dy_ptr, _vp(eng.grads[name + ".weight"]),
-                                                         _vp(eng.grads[name + ".bias"]) if s.bias else None, ws_ptr, ws_bytes, side_ptr)))
-                py(ev_wg.record, self.side)
-                if fresh_dz is not None:
-                    wg_done[fresh_dz] = ev_wg
+                sched.wgrad(shp, x.ptr, dy_ptr, eng.grads[name + ".weight"], eng.grads[name + ".bias"] if s.bias else None, dz_index=fresh_dz)
             if x.needs_grad:
                 _, wd = eng.packed[name]
                 add_dgrad(x, shp, dy_ptr, wd)
             if s.trainable:
                 self.bwd_marks.append((len(self.bwd), first_off[name + ".weight"]))
-        ev_end = torch.cuda.Event()
-        py(ev_end.record, self.side)
-        py(main.wait_event, ev_end)
-        self.side_stream = self.side
+        sched.close(self)
         # DDP bucket marks (position in self.bwd after which flat_g[offset:] is final).  The head weights are shared by the five
         # levels, so a parameter is final only after the LAST launch that touches it.
         last = {}
@@ -798,55 +672,32 @@ class RetinaPlan:
         """Inference plans time the tile candidates of their forward launches too (the igemm tuning key includes the epilogue and the
         pixel count: an eval plan shares nothing with a training plan of another batch size).  Before: every convolution of a RetinaNet
         inference ran the default 128x128 tile - cls_logits of the 1204-class head 6.6 ms against 4.9 ms tuned."""
-        eng, L = self.eng, lib()
-        img = torch.rand((self.n, 3, self.H, self.W), device=eng.device)
+        img = torch.rand((self.n, 3, self.H, self.W), device=self.eng.device)
         self.fwd[self.img_call][1][0] = C.c_void_p(img.data_ptr())
-        L.mi355det_conv_autotune_mode(1)
-        try:
+        with self.autotuning():
             self._run(self.pack)
             self._run(self.fwd)
-        finally:
-            L.mi355det_conv_autotune_mode(0)
         torch.cuda.synchronize()
 
     def _autotune(self):
-        eng, L = self.eng, lib()
+        eng = self.eng
         img = torch.rand((self.n, 3, self.H, self.W), device=eng.device)
         self.fwd[self.img_call][1][0] = C.c_void_p(img.data_ptr())
         self.glogits.normal_(0, 1e-3)
         self.gbbox.normal_(0, 1e-3)
-        L.mi355det_conv_autotune_mode(1)
-        try:
+        with self.autotuning():
             self._run(self.pack)
             self._run(self.fwd)
             self._run(self.cast)
             self.side.wait_stream(torch.cuda.current_stream())
             self._run(self.bwd)
-        finally:
-            L.mi355det_conv_autotune_mode(0)
         torch.cuda.synchronize()
-        ws_ptr, ws_bytes = _vp(self.wgrad_ws), self.wgrad_ws.numel()
-        for rec in self.ops:
-            if rec["kind"] == "conv" and rec["spec"].trainable and "dy_ptr" in rec:
-                st = L.mi355det_conv_wgrad_autotune(C.byref(rec["shp"]), rec["x"].ptr, rec["dy_ptr"], _vp(eng.grads[rec["name"] + ".weight"]),
-                                                    ws_ptr, ws_bytes, self.stream)
-                if st < 0:
-                    check(st, "conv_wgrad_autotune")
-        torch.cuda.synchronize()
-        eng.flat_g.zero_()
+        self.autotune_wgrads((r["shp"], r["x"].ptr, r["dy_ptr"], eng.grads[r["name"] + ".weight"])
+                             for r in self.ops if r["kind"] == "conv" and r["spec"].trainable and "dy_ptr" in r)
         self.glogits.zero_()
         self.gbbox.zero_()
 
     # ------------------------------------------------------------------
-    def _run(self, calls):
-        for fn, args in calls:
-            if fn is comm_hook:
-                args[0](*args[1:])
-                continue
-            st = fn(*args)
-            if st != 0:
-                check(st, fn.__name__)
-
     def run_forward(self, images):
         self._img = images
         self.fwd[self.img_call][1][0] = C.c_void_p(images.data_ptr())

@@ -17,38 +17,13 @@ import os
 
 import torch
 
-from ... import _lib, ops, tune
-from ..._lib import check, lib
+from ... import _lib, ops
+from ..._lib import lib
+from ...plan_core import Act, BackwardSchedule, GradAccumulator, PlanBase, _vp, cached_plan, check_images, comm_hook  # noqa: F401  (re-exported)
 
 BLOCKS = {"darknet_21": [1, 1, 2, 2, 1], "darknet_53": [1, 2, 8, 8, 4]}
 SLOPE = 0.1
 BN_EPS, BN_MOM = 1e-5, 0.1
-
-
-def _vp(t, byte_off=0):
-    return C.c_void_p(t.data_ptr() + byte_off) if t is not None else None
-
-
-class Act:
-    """A [n,h,w,c] bf16 activation living in (a channel slice of) an NHWC buffer."""
-
-    def __init__(self, buf, n, h, w, c, ld, ch_off=0):
-        self.buf, self.n, self.h, self.w, self.c, self.ld, self.ch_off = buf, n, h, w, c, ld, ch_off
-        self.grad = None
-        self.grad_written = False
-        self.skips = []
-        self.conv_consumers = 0      # convolutions reading this activation (their dgrads all add into its gradient)
-
-    @property
-    def ptr(self):
-        return C.c_void_p(self.buf.data_ptr() + 2 * self.ch_off)
-
-    @property
-    def pixels(self):
-        return self.n * self.h * self.w
-
-    def slice(self, c0, c):
-        return Act(self.buf, self.n, self.h, self.w, c, self.ld, self.ch_off + c0)
 
 
 class ConvSpec:
@@ -328,31 +303,17 @@ class YoloV3Engine:
 
     def plan(self, n, H, W, training):
         key = (n, H, W, bool(training), torch.cuda.current_stream().cuda_stream)
-        p = self.plans.pop(key, None)
-        if p is None:
-            while len(self.plans) >= self.MAX_PLANS:
-                torch.cuda.current_stream().synchronize()           # nothing of the evicted plan may still be running
-                self.plans.pop(next(iter(self.plans)))
-            # (tune.plan_build: MI355DET_TUNE_LOAD / _SAVE, and for N > 1 rank 0's timing choices broadcast to every rank.  The broadcast is a
-            #  collective, so it runs only for plans every rank is known to build: training plans of an engine that takes part in data-parallel
-            #  training - a GradSync is attached or SyncBN is on.  An evaluation loop, or a second engine that one rank builds for itself, may
-            #  exist on a subset of the ranks)
-            dp = bool(training and (self.sync_bn or getattr(self, "grad_syncs", ())))
-            p = tune.plan_build(lambda: Plan(self, n, H, W, training, key[-1]), group=None, share=None if dp else False)
-            if training:
-                for gs in getattr(self, "grad_syncs", ()):       # parallel.GradSync.attach(): every plan gets the bucket hooks
-                    gs.install(p)
-        self.plans[key] = p                                          # most recently used last
-        return p
+        # (tune.plan_build: MI355DET_TUNE_LOAD / _SAVE, and for N > 1 rank 0's timing choices broadcast to every rank.  The broadcast is a
+        #  collective, so it runs only for plans every rank is known to build: training plans of an engine that takes part in data-parallel
+        #  training - a GradSync is attached or SyncBN is on.  An evaluation loop, or a second engine that one rank builds for itself, may
+        #  exist on a subset of the ranks)
+        dp = bool(training and (self.sync_bn or getattr(self, "grad_syncs", ())))
+        return cached_plan(self, key, lambda: Plan(self, n, H, W, training, key[-1]), training, dp)
 
     def forward(self, images, training=None):
         """images [n,3,H,W] fp32 NCHW on the GPU -> (out0,out1,out2) NCHW-shaped fp32 views [n,A*(5+C),h,w]."""
         training = self.training if training is None else training
-        if images.dim() != 4 or images.shape[1] != 3 or not images.is_cuda:
-            raise ValueError("expected a CUDA tensor [n,3,H,W]")
-        n, _, H, W = images.shape
-        if H % 32 or W % 32:
-            raise ValueError("input size must be a multiple of 32")
+        n, H, W = check_images(images)
         p = self.plan(n, H, W, training)
         p.run_forward(images.float().contiguous())
         self._last_plan = p
@@ -379,18 +340,12 @@ class YoloV3Engine:
         p.run_backward()
 
 
-class Plan:
-    """Buffers + prepared call lists for one (batch, H, W, mode)."""
-
+class Plan(PlanBase):
     def __init__(self, eng, n, H, W, training, stream):
-        self.eng, self.n, self.H, self.W, self.training = eng, n, H, W, training
-        self.stream = C.c_void_p(stream)
-        self.fwd, self.bwd, self.pack = [], [], []
+        super().__init__(eng, eng.L, n, H, W, training, stream)
         self.fwd_const = []       # eval mode: folded BatchNorm rows (functions of the parameters only)
         self._const_epoch = -1
-        self.keep = []            # ctypes structs / tensors that must outlive the call lists
         self.dz_elems = 0
-        self.layers = {}
         dev = eng.device
         L = eng.L
         bf = eng.adt
@@ -406,7 +361,6 @@ class Plan:
         self.cat2 = new_act(n, g3[0], g3[1], 384)
         self.heads = [torch.zeros((n, g[0], g[1], eng.head_ld), device=dev, dtype=torch.float32) for g in (g5, g4, g3)]
         self.head_grads = [torch.zeros((n, g[0], g[1], eng.head_ld), device=dev, dtype=bf) for g in (g5, g4, g3)]
-        self.ops = []   # forward-ordered op records for the backward builder
 
         import torch.distributed as dist
         world = dist.get_world_size(eng.process_group) if (eng.sync_bn and training and dist.is_available() and dist.is_initialized()) else 1
@@ -539,23 +493,10 @@ class Plan:
         branch("embedding2", self.cat2, 2)
 
         # ---- weight packing (every step: the optimizer changes the fp32 masters) — one batched launch
-        items = (_lib.PackItem * len(eng.specs))()
-        for i, s in enumerate(eng.specs):
+        def pack_shape(s):
             shp = eng._wshape(s, 1, 8, 8)
-            wf, wd = eng.packed[s.name]
-            need_d = training and wd is not None
-            items[i].w = eng.params[s.name + ".weight"].data_ptr()
-            items[i].w_fwd = wf.data_ptr()
-            items[i].w_dgrad = wd.data_ptr() if need_d else None
-            items[i].shape = shp
-            items[i].cout_pad = ops.cout_pad_of(shp.cout)
-            items[i].w_is_ohwi = 1
-        ne, nb = C.c_int32(0), C.c_int32(0)
-        nbytes = L.mi355det_pack_table_bytes(items, len(eng.specs), C.byref(ne), C.byref(nb))
-        host = torch.empty(nbytes, dtype=torch.uint8)
-        check(L.mi355det_pack_table_build(items, len(eng.specs), C.c_void_p(host.data_ptr()), nbytes), "pack_table_build")
-        self.pack_table = host.to(dev)
-        self.pack.append((L.mi355det_pack_weights_batched, (_vp(self.pack_table), ne.value, nb.value, self.stream)))
+            return shp, ops.cout_pad_of(shp.cout)
+        self.build_pack_table(eng.specs, pack_shape, need_dgrad=training)
         if training:
             self._build_backward()
             self._autotune()
@@ -627,28 +568,16 @@ class Plan:
     def _build_backward(self):
         eng, L, dev = self.eng, self.eng.L, self.eng.device
         bf = eng.adt
-        # two dz buffers (ping-pong) so the weight-gradient GEMM of layer L can run on a SECOND stream while the main
-        # stream already does the BN backward / dgrad of the next layers: wgrad is off the dependency chain
-        # (reduce -> apply -> dgrad), and the HBM-bound BN passes overlap with its MFMA work.
-        self.dz2 = [torch.zeros(self.dz_elems, device=dev, dtype=bf) for _ in range(2)]
-        self.dz = self.dz2[0]
         # BN-backward reduction fused into the producing dgrad's epilogue (mi355det_conv_dgrad_bn): correct and tested, but measured
         # SLOWER end to end in round 1 (849 vs 871 img/s): the z tile is read at the tile's end where nothing hides the HBM latency.
         # Opt-in until the prefetch is moved into the last k-steps.
         self.fuse_bn_reduce = eng.fuse_bn_reduce
-        main = torch.cuda.current_stream(dev)
-        # (one stream for everything was the A/B of round 3: +1.0 ms per step, profiles/r03_ab_results.md)
-        self.side = torch.cuda.Stream(device=dev)
-        side_ptr = C.c_void_p(self.side.cuda_stream)
-        wg_done = [None, None]        # event: last wgrad that read dz2[i]
-        flip = [0]
-
-        def py(fn, *a):
-            self.bwd.append((comm_hook, (fn,) + a))
+        # wgrad is off the dependency chain (reduce -> apply -> dgrad), and the HBM-bound BN passes overlap with its MFMA work
         ws_need = max(L.mi355det_conv_wgrad_workspace(C.byref(r["shp_f"] if r["kind"] == "out" else r["shp"]))
                       for r in self.ops if r["kind"] in ("cbl", "out"))
-        self.wgrad_ws = torch.empty(max(ws_need, 16), device=dev, dtype=torch.uint8)
-        ws_ptr, ws_bytes = _vp(self.wgrad_ws), self.wgrad_ws.numel()
+        sched = BackwardSchedule(self, dev, bf, self.dz_elems, ws_need)
+        self.dz = self.dz2[0]
+        py = sched.py
         nsum = sum(2 * r["shp"].cout for r in self.ops if r["kind"] == "cbl") + 64
         self.sums_all = torch.zeros(nsum, device=dev, dtype=torch.float32)
         sum_off = [0]
@@ -658,38 +587,29 @@ class Plan:
         self.bn_red_ws = torch.zeros(red_need, device=dev, dtype=torch.uint8)
         red_ptr, red_bytes = _vp(self.bn_red_ws), self.bn_red_ws.numel()
 
-        def grad_of(a):
-            if a.grad is None:
-                a.grad = Act(torch.zeros((a.n, a.h, a.w, a.c), device=dev, dtype=bf), a.n, a.h, a.w, a.c, a.c)
-            return a.grad
+        acc = GradAccumulator(L, dev, bf, self, lambda shp, dy_ptr, wd, g, rptr, rld: (
+            L.mi355det_conv_dgrad, (C.byref(shp), dy_ptr, _vp(wd), g.ptr, rptr, rld, self.stream)))
 
         def emit_dgrad(shp, dy_ptr, wd, x):
-            g = grad_of(x)
+            g = acc.grad_of(x)
             if g.ld != shp.in_ld:     # x is a channel slice of a concat buffer; its gradient buffer is dense
                 shp = _lib.ConvShape(shp.n, shp.h, shp.w, shp.cin, shp.ho, shp.wo, shp.cout, shp.ksize, shp.stride, shp.pad, g.ld,
                                      shp.out_ld)
                 self.keep.append(shp)
-            if not x.grad_written:
-                r = x.skips.pop(0) if x.skips else None
-                prod = getattr(x, "producer", None)
-                # this dgrad writes the COMPLETE gradient of a BN+LeakyReLU activation (single conv consumer, at most one skip,
-                # fused as the epilogue residual): start that layer's BatchNorm backward here, while the tile is on chip
-                if prod is not None and prod.get("z") is not None and x.conv_consumers == 1 and not x.skips and self.fuse_bn_reduce:
-                    rows = L.mi355det_conv_dgrad_bn_rows(C.byref(shp))
-                    cpad = ops.pad_to(x.c, 32)
-                    part = torch.zeros((rows + 64, 2, cpad), device=dev, dtype=torch.float32)
-                    prod["bn_partials"] = (part, rows, cpad)
-                    self.bwd.append((L.mi355det_conv_dgrad_bn, (C.byref(shp), dy_ptr, _vp(wd), g.ptr, r.ptr if r else None, r.ld if r else 0,
-                                                                _vp(prod["z"]), x.c, _vp(prod["ss"]), SLOPE, _vp(part), self.stream)))
-                else:
-                    self.bwd.append((L.mi355det_conv_dgrad, (C.byref(shp), dy_ptr, _vp(wd), g.ptr, r.ptr if r else None, r.ld if r else 0,
-                                                             self.stream)))
-                x.grad_written = True
-            else:
-                self.bwd.append((L.mi355det_conv_dgrad, (C.byref(shp), dy_ptr, _vp(wd), g.ptr, g.ptr, g.ld, self.stream)))
-            while x.skips:
-                r = x.skips.pop(0)
-                self.bwd.append((L.mi355det_add_bf16, (g.ptr, g.ld, r.ptr, r.ld, x.c, x.pixels, g.ptr, g.ld, self.stream)))
+            prod, call = getattr(x, "producer", None), None
+            # this dgrad writes the COMPLETE gradient of a BN+LeakyReLU activation (single conv consumer, at most one skip,
+            # fused as the epilogue residual): start that layer's BatchNorm backward here, while the tile is on chip
+            if (not x.grad_written and prod is not None and prod.get("z") is not None and x.conv_consumers == 1 and len(x.parts) <= 1
+                    and self.fuse_bn_reduce):
+                rows = L.mi355det_conv_dgrad_bn_rows(C.byref(shp))
+                cpad = ops.pad_to(x.c, 32)
+                part = torch.zeros((rows + 64, 2, cpad), device=dev, dtype=torch.float32)
+                prod["bn_partials"] = (part, rows, cpad)
+
+                def call(shp, dy_ptr, wd, g, rptr, rld):
+                    return (L.mi355det_conv_dgrad_bn, (C.byref(shp), dy_ptr, _vp(wd), g.ptr, rptr, rld, _vp(prod["z"]), x.c, _vp(prod["ss"]), SLOPE,
+                                                       _vp(part), self.stream))
+            acc.add_dgrad(x, shp, dy_ptr, wd, call)
 
         self.bwd_marks = []      # (index into self.bwd after the layer's calls, lowest flat_g offset completed)
         first_off = {name: o for name, o, _n, _s in eng.param_order}
@@ -700,7 +620,7 @@ class Plan:
                 # BatchNorm backward + weight gradient of the stem from the image and the activation gradient alone: z and dz are
                 # recomputed in registers (two passes: the per-channel sums, then dz straight into the weight-gradient MFMA)
                 name, a, ss, rows, img_call = rec["name"], rec["a"], rec["ss"], rec["rows"], rec["img_call"]
-                assert a.grad is not None and a.grad_written and not a.skips, name
+                assert a.grad is not None and a.grad_written and not a.parts, name
                 g, b = a.grad, bn_name(name)
                 wf, _ = eng.packed[name]
                 sums = self.sums_all[sum_off[0]:sum_off[0] + 64]
@@ -718,40 +638,31 @@ class Plan:
                 self.bwd.append((L.mi355det_stem_bwd_finish, (_vp(wf), _vp(ss), _vp(ag), _vp(sums), self.n * self.H * self.W,
                                                               _vp(eng.grads[name + ".weight"]), _vp(eng.grads[b + ".weight"]),
                                                               _vp(eng.grads[b + ".bias"]), self.stream)))
-                ev_stem = torch.cuda.Event()
-                py(ev_stem.record, main)                  # the stem's gradients come from the main stream: the side stream (last
-                py(self.side.wait_event, ev_stem)         # gradient bucket) must see them
+                sched.publish()        # the stem's gradients come from the main stream: the side stream (last gradient bucket) must see them
             elif rec["kind"] == "out":
                 shp, shp_f, x, k, name = rec["shp"], rec["shp_f"], rec["x"], rec["k"], rec["name"]
                 _, wd = eng.packed[name]
                 dy = _vp(self.head_grads[k])
-                ev = torch.cuda.Event()
-                py(ev.record, main)                       # head gradients ready (criterion ran on the main stream)
-                py(self.side.wait_event, ev)
-                self.bwd.append((L.mi355det_conv_wgrad, (C.byref(shp_f), x.ptr, dy, _vp(eng.grads[name + ".weight"]),
-                                                         _vp(eng.grads[name + ".bias"]), ws_ptr, ws_bytes, side_ptr)))
+                # (behind the head gradients: the criterion ran on the main stream)
+                sched.wgrad(shp_f, x.ptr, dy, eng.grads[name + ".weight"], eng.grads[name + ".bias"], record=False)
                 emit_dgrad(shp, dy, wd, x)
             elif rec["kind"] == "up":
                 x, cat, c_up, skip_to = rec["x"], rec["cat"], rec["c_up"], rec["skip_to"]
                 assert cat.grad is not None and cat.grad_written
                 gup = cat.grad.slice(0, c_up)
-                gx = grad_of(x)
+                gx = acc.grad_of(x)
                 self.bwd.append((L.mi355det_upsample2x_bwd, (gup.ptr, gup.ld, x.n, x.h, x.w, x.c, gx.ptr, gx.ld, self.stream)))
                 x.grad_written = True
-                skip_to.skips.append(cat.grad.slice(c_up, cat.c - c_up))
+                acc.add_tensor(skip_to, cat.grad.slice(c_up, cat.c - c_up))
             else:
                 name, shp, x, a, res, z, ss, pixels = (rec[k] for k in ("name", "shp", "x", "a", "res", "z", "ss", "pixels"))
-                assert a.grad is not None and a.grad_written and not a.skips, name
+                assert a.grad is not None and a.grad_written and not a.parts, name
                 g = a.grad
                 b = bn_name(name)
                 sums = self.sums_all[sum_off[0]:sum_off[0] + 2 * shp.cout]
                 sum_off[0] += 2 * shp.cout
                 if res is not None:
-                    res.skips.append(g)
-                di = flip[0]
-                flip[0] ^= 1
-                dzb = self.dz2[di]
-                rec["dz_index"] = di
+                    acc.add_tensor(res, g)
                 if "bn_partials" in rec:      # the dgrad that produced g already accumulated the per-channel partial sums
                     part, prows, cpad = rec["bn_partials"]
                     self.bwd.append((L.mi355det_bn_bwd_sum_partials, (_vp(part), prows, shp.cout, cpad, _vp(sums), self.stream)))
@@ -763,8 +674,8 @@ class Plan:
                                                                     _vp(sums), self.stream)))
                 if self.sync_world > 1:
                     py(self._sync_avg, sums)              # SyncBN backward: (sum dy, sum dy*xhat) of the global batch
-                if wg_done[di] is not None:
-                    py(main.wait_event, wg_done[di])      # the wgrad that last read this dz buffer has finished
+                di = rec["dz_index"] = sched.next_dz()    # (waits until the wgrad that last read this dz buffer has finished)
+                dzb = self.dz2[di]
                 self.bwd.append((L.mi355det_bn_act_bwd_apply, (g.ptr, g.ld, None, 0, _vp(z), shp.cout, _vp(ss), _vp(sums), None, shp.cout,
                                                                pixels, SLOPE, _vp(dzb), shp.cout, _vp(eng.grads[b + ".weight"]),
                                                                _vp(eng.grads[b + ".bias"]), self.stream)))
@@ -772,82 +683,48 @@ class Plan:
                 # (measured and removed, round 4: the weight gradient started only when its layer's data gradient has finished, so that it runs beside
                 #  the next BatchNorm passes instead of beside the data gradient: 28.17 -> 29.85 ms, profiles/r04_ab_results.md 8 - the two GEMMs
                 #  side by side fill each other's tails; serialised they do not)
-                ev_dz, ev_wg = torch.cuda.Event(), torch.cuda.Event()
-                py(ev_dz.record, main)
-                py(self.side.wait_event, ev_dz)
-                self.bwd.append((L.mi355det_conv_wgrad, (C.byref(shp), x.ptr, _vp(dzb), _vp(eng.grads[name + ".weight"]), None,
-                                                         ws_ptr, ws_bytes, side_ptr)))
-                py(ev_wg.record, self.side)
-                wg_done[di] = ev_wg
+                sched.wgrad(shp, x.ptr, _vp(dzb), eng.grads[name + ".weight"], None, dz_index=di)
                 _, wd = eng.packed[name]
                 emit_dgrad(shp, _vp(dzb), wd, x)
             if rec["kind"] in ("out", "cbl", "stem"):
                 self.bwd_marks.append((len(self.bwd), first_off[rec["name"] + ".weight"]))
-        ev_end = torch.cuda.Event()
-        py(ev_end.record, self.side)
-        py(main.wait_event, ev_end)                       # join: backward is complete on the main stream
-        self.side_stream = self.side
+        sched.close(self)
 
     def _autotune(self):
         """Plan-build time only: let the library time its candidate tile configurations / split counts for every
         conv shape of this plan on the plan's own buffers (mi355det_conv_autotune_mode, _wgrad_autotune)."""
-        eng, L = self.eng, self.eng.L
+        eng = self.eng
         saved = {k: v.clone() for k, v in eng.buffers.items()}
         img = torch.randn((self.n, 3, self.H, self.W), device=eng.device)
         self._set_image(img)
         for g in self.head_grads:
             g.normal_(0, 1e-2)
-        L.mi355det_conv_autotune_mode(1)
-        try:
+        with self.autotuning():
             self._run(self.pack)
             self._run(self.fwd)
             self._run(self.bwd)
-        finally:
-            L.mi355det_conv_autotune_mode(0)
-        ws_ptr, ws_bytes = _vp(self.wgrad_ws), self.wgrad_ws.numel()
-        for rec in self.ops:
-            if rec["kind"] == "cbl":
-                st = L.mi355det_conv_wgrad_autotune(C.byref(rec["shp"]), rec["x"].ptr, _vp(self.dz), _vp(eng.grads[rec["name"] + ".weight"]),
-                                                    ws_ptr, ws_bytes, self.stream)
-            elif rec["kind"] == "out":
-                st = L.mi355det_conv_wgrad_autotune(C.byref(rec["shp_f"]), rec["x"].ptr, _vp(self.head_grads[rec["k"]]),
-                                                    _vp(eng.grads[rec["name"] + ".weight"]), ws_ptr, ws_bytes, self.stream)
-            else:
-                continue
-            if st < 0:
-                check(st, "conv_wgrad_autotune")
-        torch.cuda.synchronize()
+
+        def wgrad_of(r):
+            shp, dy = (r["shp"], self.dz) if r["kind"] == "cbl" else (r["shp_f"], self.head_grads[r["k"]])
+            return shp, r["x"].ptr, _vp(dy), eng.grads[r["name"] + ".weight"]
+        self.autotune_wgrads(wgrad_of(r) for r in self.ops if r["kind"] in ("cbl", "out"))
         for k, v in saved.items():
             eng.buffers[k].copy_(v)
-        eng.flat_g.zero_()
         self.zero_head_grads()
 
     def _autotune_eval(self):
         """Eval plans run the convolutions with the BatchNorm + LeakyReLU (+ residual) epilogue, whose tile choices are keyed separately
         from the training forward's: time the candidates once on this plan's buffers (round 2 ran every eval convolution on the default
         128 x 128 tile: 9.2 ms against 7.0 ms for the same 75 convolutions in the training step)."""
-        L = self.eng.L
         img = torch.randn((self.n, 3, self.H, self.W), device=self.eng.device)
         self._set_image(img)
         self._run(self.pack)
         self._run(self.fwd_const)
-        L.mi355det_conv_autotune_mode(1)
-        try:
+        with self.autotuning():
             self._run(self.fwd)
-        finally:
-            L.mi355det_conv_autotune_mode(0)
         torch.cuda.synchronize()
 
     # ------------------------------------------------------------------
-    def _run(self, calls):
-        for fn, args in calls:
-            if fn is comm_hook:
-                args[0](*args[1:])
-                continue
-            st = fn(*args)
-            if st != 0:
-                check(st, fn.__name__)
-
     def _set_image(self, images):
         """The stem kernels of BOTH directions read the fp32 image: it stays referenced until the next forward."""
         self._img = images
@@ -893,6 +770,3 @@ class Plan:
         self.side.wait_stream(torch.cuda.current_stream())   # zeroed gradients / forward activations visible to the side stream
         self._run(self.bwd)
 
-
-def comm_hook(*a):   # marker: (comm_hook, (callable, *args)) entries run a python callback inside a call list
-    raise RuntimeError("marker only")
