@@ -918,7 +918,7 @@ unsigned long long igemm_key(const IgemmParams& p, int epi) {
 }
 
 // applicability of the dx-reuse kernel: 3x3, unit strides on both sides, taps in three rows of equal dy with dx stepping by +-1
-static bool dx_applicable(const IgemmParams& p, int bn = 128, int bk = 64) {
+static bool dx_applicable(const IgemmParams& p, int bn, int bk) {
   if (p.T != 9 || p.so != 1 || p.sox != 0 || p.sin != 1 || p.oy0 != 0 || p.ox0 != 0) return false;
   if (p.Hin != p.Hout || p.Win != p.Wout || p.MH != p.Hin || p.MW != p.Win) return false;
   if (p.Cin % bk != 0 || p.CoutPad % bn != 0) return false;
@@ -952,148 +952,177 @@ int launch_dx(const IgemmParams& p_in, hipStream_t st) {
   return check_launch("igemm_dx");
 }
 
-// tile configurations for Cout % 128 == 0 and Cin % 64 == 0 (pixels x channels x k-step, ring depth):
-//   1: 128x128x64 x2, 4 waves of 64x64, 2 workgroups/CU        2: 256x128x32 x2, 4 waves of 128x64, 48 KB
-//   3: 256x256x64 x2, 8 waves of 128x64, 1 workgroup/CU        4: 128x128x32 x3, 4 waves of 64x64, 3 workgroups/CU
-//   5: 128x128x32 x2 at 4 workgroups/CU                         6: 256x256x64 with LDS-DMA pieces interleaved between MFMAs
+// ---- the tile configuration table: every id that a tune record, the plan-time tuner or debug key 0 can name has ONE row here, and
+// run_cfg, strict mode and autotune_igemm read nothing else (tests/test_conv_coverage.py parses these rows too).
+enum CfgReq { REQ_WIDE, REQ_DX, REQ_IG8, REQ_NARROW, REQ_NARROW_DX };      // shape requirement of a row: cfg_applies
+typedef int (*LaunchFn)(const IgemmParams&, hipStream_t);
+struct CfgRow {
+  int id;
+  unsigned epis;      // accepted epilogues: bit EPI_*
+  int req, a, b;      // CfgReq and its two numbers
+  bool tuned, solo;   // a candidate of the plan-time tuner / one workgroup per CU (> 64 KB LDS): not tried for data gradients
+  LaunchFn launch;    // null in the table of an epilogue the row does not accept: that kernel is never instantiated
+  bool narrow() const { return req == REQ_NARROW || req == REQ_NARROW_DX; }
+};
+constexpr unsigned eSTATS = 1u << EPI_STATS, eF32 = 1u << EPI_F32, eRES = 1u << EPI_RES, ePLAIN = 1u << EPI_PLAIN, eAFF = 1u << EPI_AFF,
+                   eBNRED = 1u << EPI_BNRED, eALL = eSTATS | eF32 | eRES | ePLAIN | eAFF | eBNRED;
+
+template <int EPI, int ROWS>
+int launch_ig8(const IgemmParams& p, hipStream_t st) { return igemm8_launch(EPI, p, st, ROWS); }
+
+// narrow outputs (32 / 64 channels: the first layers and their data gradients): one plain tile shape each (no choice)
 template <int EPI>
-int run_cfg(int cfg, const IgemmParams& p, hipStream_t st, bool strict = false) {
-  switch (cfg) {
-    case 2: return launch_cfg<2, 2, 8, 4, 32, 2, EPI>(p, st);
-    case 3: if (p.CoutPad % 256 == 0) return launch_cfg<2, 4, 8, 4, 64, 2, EPI>(p, st); break;
-    case 4: return launch_cfg<2, 2, 4, 4, 32, 3, EPI>(p, st);
-    case 5: return launch_cfg<2, 2, 4, 4, 32, 2, EPI, false, false, 4>(p, st);   // 32 KB LDS, <=128 VGPR: 4 workgroups/CU
-    case 6: if (p.CoutPad % 256 == 0) return launch_il<2, 4, 8, 4, 64, EPI, 0>(p, st); break;   // interleaved 256x256x64, 8 waves of 128x64
-    // 50-56: deeper rings, diagnostic (forward only): measured slower than depth 2 once the LDS-DMA really stays in flight
-    case 50: if (EPI == EPI_STATS && p.CoutPad % 256 == 0) return launch_cfg<2, 4, 8, 4, 32, 3, EPI>(p, st); break;   // 256x256x32 ring 3 (96 KB)
-    case 51: if (EPI == EPI_STATS && p.CoutPad % 256 == 0) return launch_cfg<2, 4, 8, 4, 32, 4, EPI>(p, st); break;   // 256x256x32 ring 4 (128 KB)
-    case 52: if (EPI == EPI_STATS) return launch_cfg<2, 2, 8, 4, 32, 3, EPI>(p, st); break;                                     // 256x128x32 ring 3 (72 KB, 2 workgroups/CU)
-    case 53: if (EPI == EPI_STATS) return launch_cfg<2, 2, 8, 4, 32, 4, EPI>(p, st); break;                                     // 256x128x32 ring 4 (96 KB)
-    case 54: if (EPI == EPI_STATS) return launch_cfg<2, 2, 4, 4, 32, 4, EPI>(p, st); break;                                     // 128x128x32 ring 4 (64 KB, 2 workgroups/CU)
-    case 55: if (EPI == EPI_STATS) return launch_cfg<2, 2, 4, 4, 64, 3, EPI>(p, st); break;                                     // 128x128x64 ring 3 (96 KB, 1 workgroup/CU)
-    case 56: if (EPI == EPI_STATS) return launch_cfg<2, 2, 4, 4, 32, 6, EPI>(p, st); break;                                     // 128x128x32 ring 6 (96 KB)
-    case 40: if (igemm8_applicable(p) && (EPI == EPI_STATS || EPI == EPI_PLAIN || EPI == EPI_RES || EPI == EPI_AFF || EPI == EPI_F32)) return igemm8_launch(EPI, p, st); break;   // phase-staggered 256x256x64, 8 waves
-    // 44 / 45: the same kernel on 224 / 208-pixel tiles (tile quantisation: 800 / 400 / 200 tiles of 256 pixels on 256 CUs; a 192-pixel
-    // tile was measured too - 1067 / 534 / 268 tiles need one round more: 3-65 % slower - and removed, profiles/r04_ab_results.md)
-    case 44: if (igemm8_applicable(p) && (EPI == EPI_STATS || EPI == EPI_PLAIN || EPI == EPI_RES || EPI == EPI_AFF)) return igemm8_launch(EPI, p, st, 224); break;
-    case 45: if (igemm8_applicable(p) && (EPI == EPI_STATS || EPI == EPI_PLAIN || EPI == EPI_RES || EPI == EPI_AFF)) return igemm8_launch(EPI, p, st, 208); break;
-    case 15: if (dx_applicable(p)) return launch_dx<2, 2, 4, 4, EPI>(p, st); break;             // 3x3 s1: shared pixel tiles (dx reuse), 128x128
-    case 16: if (dx_applicable(p)) return launch_dx<4, 2, 4, 4, EPI>(p, st); break;             // dx reuse 256x128, 8 waves, 1 workgroup/CU
-    case 17: if (dx_applicable(p) && p.CoutPad % 256 == 0) return launch_dx<2, 4, 4, 4, EPI>(p, st); break;   // dx reuse 128x256, 8 waves
-    case 18: if (dx_applicable(p) && p.CoutPad % 256 == 0) return launch_dx<2, 4, 8, 4, EPI>(p, st); break;   // dx reuse 256x256, 8 waves of 128x64
-    case 19: if (dx_applicable(p)) return launch_dx<2, 2, 8, 4, EPI>(p, st); break;                           // dx reuse 256x128, 4 waves of 128x64
-    case 35: if (dx_applicable(p)) return launch_dx<2, 2, 4, 4, EPI, 2, false, 32>(p, st); break;            // dx reuse 128x128x32: 3 workgroups/CU
-    case 26: if (dx_applicable(p)) return launch_dx<4, 2, 4, 4, EPI, 3>(p, st); break;                        // dx reuse 256x128, 8 waves, weight ring 3
-    case 27: if (dx_applicable(p)) return launch_dx<2, 2, 4, 4, EPI, 3>(p, st); break;                        // dx reuse 128x128, weight ring 3 (1 WG/CU)
-    case 28: if (dx_applicable(p) && p.CoutPad % 256 == 0) return launch_dx<2, 4, 4, 4, EPI, 3>(p, st); break; // dx reuse 128x256, 8 waves, ring 3
-    case 21: if (EPI == EPI_STATS) return launch_cfg<2, 2, 4, 4, 64, 2, EPI, false, false, 0, 1>(p, st); break;   // ablations of cfg 1
-    case 22: if (EPI == EPI_STATS) return launch_cfg<2, 2, 4, 4, 64, 2, EPI, false, false, 0, 2>(p, st); break;
-    case 23: if (EPI == EPI_STATS) return launch_cfg<2, 2, 4, 4, 64, 2, EPI, false, false, 0, 3>(p, st); break;
-    case 25: if (EPI == EPI_STATS) return launch_cfg<2, 2, 4, 4, 64, 2, EPI, false, false, 0, 5>(p, st); break;
-    case 99: if (EPI == EPI_STATS) return launch_cfg<2, 2, 4, 4, 64, 2, EPI, true>(p, st); break;   // phase-stamp diagnostic build
-    case 98: if (EPI == EPI_STATS && dx_applicable(p)) return launch_dx<2, 2, 4, 4, EPI, 2, true>(p, st); break;   // same for the shared-pixel-tile kernel
-    case 97: if (EPI == EPI_STATS && dx_applicable(p)) return launch_dx<4, 2, 4, 4, EPI, 3, true>(p, st); break;   // 256x128, 8 waves, ring 3
-    default: break;
+int launch_narrow(const IgemmParams& p, hipStream_t st) {
+  const bool k64 = p.Cin % 64 == 0;
+  if (p.CoutPad % 64 == 0) return k64 ? launch_cfg<4, 1, 4, 4, 64, 2, EPI>(p, st) : launch_cfg<4, 1, 4, 4, 32, 3, EPI>(p, st);
+  if (p.CoutPad % 32 == 0) return k64 ? launch_cfg<4, 1, 4, 2, 64, 2, EPI>(p, st) : launch_cfg<4, 1, 4, 2, 32, 4, EPI>(p, st);
+  return fail(MI355DET_EINVAL, "%s: padded Cout must be a multiple of 32 (got %lld)", "conv", p.CoutPad);
+}
+
+#define CFG_ROW(id, epis, req, a, b, tuned, solo, ...) \
+  {id, epis, req, a, b, tuned, solo, [] { if constexpr ((((epis) >> EPI) & 1u) != 0) return (LaunchFn)(__VA_ARGS__); else return (LaunchFn) nullptr; }()}
+
+// Rows in the order the tuner tries them (ties go to the earlier row), closed by id -1.  Tiles are pixels x channels x k-step, ring depth.
+template <int EPI>
+const CfgRow* cfg_rows() {
+  static const CfgRow rows[] = {
+    //      id  epilogues                          requirement      a    b  tuned solo  launcher
+    CFG_ROW( 0, eALL,                              REQ_NARROW,      0,   0, 1, 0, launch_narrow<EPI>),                                  // the plain narrow tile
+    CFG_ROW( 1, eALL,                              REQ_WIDE,      128,   0, 1, 0, launch_cfg<2, 2, 4, 4, 64, 2, EPI>),                  // 128x128x64 x2, 4 waves of 64x64, 2 workgroups/CU: the default
+    CFG_ROW( 2, eALL,                              REQ_WIDE,      128,   0, 1, 0, launch_cfg<2, 2, 8, 4, 32, 2, EPI>),                  // 256x128x32 x2, 4 waves of 128x64, 48 KB
+    CFG_ROW( 3, eALL,                              REQ_WIDE,      256,   0, 1, 1, launch_cfg<2, 4, 8, 4, 64, 2, EPI>),                  // 256x256x64 x2, 8 waves of 128x64
+    CFG_ROW( 4, eALL,                              REQ_WIDE,      128,   0, 1, 0, launch_cfg<2, 2, 4, 4, 32, 3, EPI>),                  // 128x128x32 x3, 3 workgroups/CU
+    CFG_ROW( 5, eALL,                              REQ_WIDE,      128,   0, 1, 0, launch_cfg<2, 2, 4, 4, 32, 2, EPI, false, false, 4>), // 128x128x32 x2: 32 KB LDS, <= 128 VGPR, 4 workgroups/CU
+    CFG_ROW( 6, eALL,                              REQ_WIDE,      256,   0, 1, 1, launch_il<2, 4, 8, 4, 64, EPI, 0>),                   // 256x256x64 with LDS-DMA pieces interleaved between MFMAs
+    CFG_ROW(15, eALL,                              REQ_DX,        128,  64, 1, 0, launch_dx<2, 2, 4, 4, EPI>),                          // 3x3 s1: shared pixel tiles (dx reuse), 128x128
+    CFG_ROW(16, eALL,                              REQ_DX,        128,  64, 1, 1, launch_dx<4, 2, 4, 4, EPI>),                          // dx reuse 256x128, 8 waves
+    CFG_ROW(17, eALL,                              REQ_DX,        256,  64, 1, 1, launch_dx<2, 4, 4, 4, EPI>),                          // dx reuse 128x256, 8 waves
+    CFG_ROW(18, eALL,                              REQ_DX,        256,  64, 1, 1, launch_dx<2, 4, 8, 4, EPI>),                          // dx reuse 256x256, 8 waves of 128x64
+    CFG_ROW(19, eALL,                              REQ_DX,        128,  64, 1, 1, launch_dx<2, 2, 8, 4, EPI>),                          // dx reuse 256x128, 4 waves of 128x64
+    CFG_ROW(26, eALL,                              REQ_DX,        128,  64, 1, 1, launch_dx<4, 2, 4, 4, EPI, 3>),                       // dx reuse 256x128, 8 waves, weight ring 3
+    CFG_ROW(27, eALL,                              REQ_DX,        128,  64, 1, 1, launch_dx<2, 2, 4, 4, EPI, 3>),                       // dx reuse 128x128, weight ring 3
+    CFG_ROW(28, eALL,                              REQ_DX,        256,  64, 1, 1, launch_dx<2, 4, 4, 4, EPI, 3>),                       // dx reuse 128x256, 8 waves, ring 3
+    // 40: phase-staggered 256x256x64, 8 waves.  44 / 45: the same kernel on 224 / 208-pixel tiles (tile quantisation: 800 / 400 / 200 tiles of
+    // 256 pixels on 256 CUs; a 192-pixel tile was measured too - 1067 / 534 / 268 tiles need one round more: 3-65 % slower - and removed,
+    // profiles/r04_ab_results.md).  These masks are the one statement of what igemm8_kernels.hip is launched with.
+    CFG_ROW(40, eSTATS | eF32 | eRES | ePLAIN | eAFF,  REQ_IG8,       256,   0, 1, 0, launch_ig8<EPI, 256>),
+    CFG_ROW(44, eSTATS | eRES | ePLAIN | eAFF,         REQ_IG8,       224,   0, 1, 0, launch_ig8<EPI, 224>),
+    CFG_ROW(45, eSTATS | eRES | ePLAIN | eAFF,         REQ_IG8,       208,   0, 1, 0, launch_ig8<EPI, 208>),
+    // narrow outputs: the shared-pixel-tile kernel at 256 x 32 / 256 x 64 (31: its 32-deep k-step for 32 input channels)
+    CFG_ROW(29, eALL,                              REQ_NARROW_DX,  32,  64, 1, 0, launch_dx<4, 1, 4, 2, EPI>),
+    CFG_ROW(30, eALL,                              REQ_NARROW_DX,  64,  64, 1, 0, launch_dx<4, 1, 4, 4, EPI>),
+    CFG_ROW(31, eALL,                              REQ_NARROW_DX,  64,  32, 1, 0, launch_dx<4, 1, 4, 4, EPI, 2, false, 32>),
+    CFG_ROW(35, eALL,                              REQ_DX,        128,  32, 0, 0, launch_dx<2, 2, 4, 4, EPI, 2, false, 32>),            // dx reuse 128x128x32, 3 workgroups/CU: measured slower, not tried
+    // diagnostics (forward with statistics only, never tried).  50-56: deeper rings, measured slower than depth 2 once the LDS-DMA really
+    // stays in flight
+    CFG_ROW(50, eSTATS,                            REQ_WIDE,      256,   0, 0, 0, launch_cfg<2, 4, 8, 4, 32, 3, EPI>),                  // 256x256x32 ring 3 (96 KB)
+    CFG_ROW(51, eSTATS,                            REQ_WIDE,      256,   0, 0, 0, launch_cfg<2, 4, 8, 4, 32, 4, EPI>),                  // 256x256x32 ring 4 (128 KB)
+    CFG_ROW(52, eSTATS,                            REQ_WIDE,      128,   0, 0, 0, launch_cfg<2, 2, 8, 4, 32, 3, EPI>),                  // 256x128x32 ring 3 (72 KB, 2 workgroups/CU)
+    CFG_ROW(53, eSTATS,                            REQ_WIDE,      128,   0, 0, 0, launch_cfg<2, 2, 8, 4, 32, 4, EPI>),                  // 256x128x32 ring 4 (96 KB)
+    CFG_ROW(54, eSTATS,                            REQ_WIDE,      128,   0, 0, 0, launch_cfg<2, 2, 4, 4, 32, 4, EPI>),                  // 128x128x32 ring 4 (64 KB, 2 workgroups/CU)
+    CFG_ROW(55, eSTATS,                            REQ_WIDE,      128,   0, 0, 0, launch_cfg<2, 2, 4, 4, 64, 3, EPI>),                  // 128x128x64 ring 3 (96 KB, 1 workgroup/CU)
+    CFG_ROW(56, eSTATS,                            REQ_WIDE,      128,   0, 0, 0, launch_cfg<2, 2, 4, 4, 32, 6, EPI>),                  // 128x128x32 ring 6 (96 KB)
+    CFG_ROW(21, eSTATS,                            REQ_WIDE,      128,   0, 0, 0, launch_cfg<2, 2, 4, 4, 64, 2, EPI, false, false, 0, 1>),   // ablations of configuration 1
+    CFG_ROW(22, eSTATS,                            REQ_WIDE,      128,   0, 0, 0, launch_cfg<2, 2, 4, 4, 64, 2, EPI, false, false, 0, 2>),
+    CFG_ROW(23, eSTATS,                            REQ_WIDE,      128,   0, 0, 0, launch_cfg<2, 2, 4, 4, 64, 2, EPI, false, false, 0, 3>),
+    CFG_ROW(25, eSTATS,                            REQ_WIDE,      128,   0, 0, 0, launch_cfg<2, 2, 4, 4, 64, 2, EPI, false, false, 0, 5>),
+    CFG_ROW(99, eSTATS,                            REQ_WIDE,      128,   0, 0, 0, launch_cfg<2, 2, 4, 4, 64, 2, EPI, true>),            // phase-stamp build of configuration 1
+    CFG_ROW(98, eSTATS,                            REQ_DX,        128,  64, 0, 0, launch_dx<2, 2, 4, 4, EPI, 2, true>),                 // the same for the shared-pixel-tile kernel
+    CFG_ROW(97, eSTATS,                            REQ_DX,        128,  64, 0, 0, launch_dx<4, 2, 4, 4, EPI, 3, true>),                 // 256x128, 8 waves, ring 3
+    {-1, 0, 0, 0, 0, false, false, nullptr},
+  };
+  return rows;
+}
+
+template <int EPI>
+const CfgRow* find_cfg(int cfg) {
+  for (const CfgRow* r = cfg_rows<EPI>(); r->id >= 0; ++r)
+    if (r->id == cfg) return r;
+  return nullptr;
+}
+
+// does this launch meet the row's shape requirement, and is the row's kernel built for this epilogue?
+bool cfg_applies(const CfgRow& r, const IgemmParams& p) {
+  if (!r.launch) return false;
+  const bool wide = p.CoutPad % 128 == 0 && p.Cin % 64 == 0;
+  switch (r.req) {
+    case REQ_WIDE: return wide && p.CoutPad % r.a == 0;                  // a = 128 or 256 padded channels per tile
+    case REQ_DX: return wide && dx_applicable(p, r.a, r.b);              // shared-pixel-tile kernel: a channels per tile, k-step b
+    case REQ_IG8: return wide && igemm8_applicable(p);                   // phase-staggered kernel on pixel tiles of height a
+    case REQ_NARROW: return p.CoutPad % 128 != 0;                        // the plain narrow tile, the default there
+    case REQ_NARROW_DX: return p.CoutPad % (2 * r.a) != 0 && dx_applicable(p, r.a, r.b);      // exactly a = 64 / 32 channels per tile
   }
-  if (strict && cfg != 1) {
-    static const int known[] = {2, 3, 4, 5, 6, 15, 16, 17, 18, 19, 21, 22, 23, 25, 26, 27, 28, 35, 40, 44, 45, 50, 51, 52, 53, 54, 55, 56, 97, 98, 99};
-    bool k = false;
-    for (int c : known) k = k || c == cfg;
-    if (cfg == 29 || cfg == 30 || cfg == 31) return strict_reject(cfg, "a narrow-output id on a launch with a multiple of 128 output channels");
-    return strict_reject(cfg, k ? "its shape or epilogue predicate does not hold for this launch" : "unknown id");
-  }
-  return launch_cfg<2, 2, 4, 4, 64, 2, EPI>(p, st);
+  return false;
+}
+
+// lookup -> predicate -> launch; an id that does not apply runs the default of the launch's side (wide: 1, narrow: 0)
+template <int EPI>
+int run_cfg(int cfg, const IgemmParams& p, hipStream_t st) {
+  const CfgRow* r = find_cfg<EPI>(cfg);
+  if (!r || !cfg_applies(*r, p)) r = find_cfg<EPI>(p.CoutPad % 128 == 0 ? 1 : 0);
+  return r->launch(p, st);
+}
+
+// strict mode: why forced id `cfg` would not run on this launch (null: it runs)
+template <int EPI>
+const char* strict_why(int cfg, const IgemmParams& p) {
+  const CfgRow* r = find_cfg<EPI>(cfg);
+  const bool wide = p.CoutPad % 128 == 0;
+  if (!r) return "unknown id";
+  if (r->narrow() && wide) return "a narrow-output id on a launch with a multiple of 128 output channels";
+  if (!r->narrow() && !wide) return "a wide-output id on a narrow output (32 / 64 padded channels)";
+  if (cfg_applies(*r, p)) return nullptr;
+  return wide ? "its shape or epilogue predicate does not hold for this launch" : "the narrow shared-pixel-tile kernel does not take this shape";
 }
 
 template <int EPI>
 int launch_igemm(const IgemmParams& p, hipStream_t st) {
   if (p.Cin % 32 != 0) return fail(MI355DET_EINVAL, "%s: Cin must be a multiple of 32 (got %lld)", "conv", p.Cin);
-  const bool k64 = p.Cin % 64 == 0;
-  if (p.CoutPad % 128 == 0 && k64) {
-    int cfg = 1;
-    auto it = g_igemm_tuned.find(igemm_key(p, EPI));
-    if (it != g_igemm_tuned.end()) cfg = it->second;
-    if (g_tune) cfg = g_tune;
-    return run_cfg<EPI>(cfg, p, st, strict_forced());
+  const bool wide = p.CoutPad % 128 == 0;
+  if (wide && p.Cin % 64 != 0) {      // no choice
+    if (strict_forced()) return strict_reject(g_tune, "Cin is not a multiple of 64: the launch takes its fixed 128 x 128 x 32 tile");
+    return launch_cfg<2, 2, 4, 4, 32, 3, EPI>(p, st);
   }
-  if (strict_forced()) {
-    const bool nid = g_tune == 29 || g_tune == 30 || g_tune == 31;
-    if (p.CoutPad % 128 == 0) return strict_reject(g_tune, "Cin is not a multiple of 64: the launch takes its fixed 128 x 128 x 32 tile");
-    if (!nid) return strict_reject(g_tune, "a wide-output id on a narrow output (32 / 64 padded channels)");
-    const bool ok = p.CoutPad % 64 == 0 ? (g_tune == 30 ? dx_applicable(p, 64) : g_tune == 31 && dx_applicable(p, 64, 32))
-                                        : p.CoutPad % 32 == 0 && g_tune == 29 && dx_applicable(p, 32);
-    if (!ok) return strict_reject(g_tune, "the narrow shared-pixel-tile kernel does not take this shape");
-  }
-  if (p.CoutPad % 128 == 0) return launch_cfg<2, 2, 4, 4, 32, 3, EPI>(p, st);
-  // narrow outputs (32 / 64 channels: the first layers and their data gradients): one plain tile shape each, or the
-  // shared-pixel-tile kernel at 256 x 64 / 256 x 32 when the autotuner found it faster
-  int narrow = 0;
-  {
-    auto it = g_igemm_tuned.find(igemm_key(p, EPI));
-    if (it != g_igemm_tuned.end()) narrow = it->second;
-    if (g_tune == 29 || g_tune == 30 || g_tune == 31) narrow = g_tune;
-  }
-  if (p.CoutPad % 64 == 0) {
-    if (narrow == 30 && dx_applicable(p, 64)) return launch_dx<4, 1, 4, 4, EPI>(p, st);
-    if (narrow == 31 && dx_applicable(p, 64, 32)) return launch_dx<4, 1, 4, 4, EPI, 2, false, 32>(p, st);      // 32 input channels: k-step of 32
-    return k64 ? launch_cfg<4, 1, 4, 4, 64, 2, EPI>(p, st) : launch_cfg<4, 1, 4, 4, 32, 3, EPI>(p, st);
-  }
-  if (p.CoutPad % 32 == 0) {
-    if (narrow == 29 && dx_applicable(p, 32)) return launch_dx<4, 1, 4, 2, EPI>(p, st);
-    return k64 ? launch_cfg<4, 1, 4, 2, 64, 2, EPI>(p, st) : launch_cfg<4, 1, 4, 2, 32, 4, EPI>(p, st);
-  }
-  return fail(MI355DET_EINVAL, "%s: padded Cout must be a multiple of 32 (got %lld)", "conv", p.CoutPad);
+  if (strict_forced())
+    if (const char* why = strict_why<EPI>(g_tune, p)) return strict_reject(g_tune, why);
+  int cfg = 0;
+  auto it = g_igemm_tuned.find(igemm_key(p, EPI));
+  if (it != g_igemm_tuned.end()) cfg = it->second;
+  const CfgRow* forced = g_tune ? find_cfg<EPI>(g_tune) : nullptr;
+  if (g_tune && (wide || (forced && forced->narrow()))) cfg = g_tune;      // a wide id forced on a narrow output leaves the tuned choice alone
+  return run_cfg<EPI>(cfg, p, st);
 }
 
-// plan-build helper: time the candidate configurations of one launch and remember the fastest
+// plan-build helper: time the table's candidates for one launch and remember the fastest
 template <int EPI>
 int autotune_igemm(const IgemmParams& p, hipStream_t st) {
   if (tune_locked_has(TUNE_IGEMM, igemm_key(p, EPI))) return launch_igemm<EPI>(p, st);      // the choice came from a tune record: not timed again
-  const bool narrow32 = p.CoutPad % 128 != 0 && p.CoutPad % 64 == 0 && p.Cin % 64 != 0 && dx_applicable(p, 64, 32);      // 32 -> 64 @320
-  if (narrow32 || (p.CoutPad % 128 != 0 && p.Cin % 64 == 0 && (p.CoutPad % 64 == 0 ? dx_applicable(p, 64) : dx_applicable(p, 32)))) {
-    // narrow output: plain tile (id 0) against the shared-pixel-tile kernel (id 30 / 29; 31 = its 32-deep k-step for 32 input channels)
-    const int alt = narrow32 ? 31 : (p.CoutPad % 64 == 0 ? 30 : 29);
-    EventPair ev;
-    if (!ev.ok) return fail(MI355DET_ELAUNCH, "%s: event create failed", "conv_autotune");
-    hipEvent_t e0 = ev.e0, e1 = ev.e1;
-    float best_ms = 1e30f;
-    int best = 0;
-    for (int cfg : {0, alt}) {
-      g_igemm_tuned[igemm_key(p, EPI)] = cfg;
-      int e = 0;
-      const float ms = time_candidate([&] { return launch_igemm<EPI>(p, st); }, e0, e1, st, &e);
-      if (e) return e;
-      if (ms < best_ms) {
-        best_ms = ms;
-        best = cfg;
-      }
-    }
-    g_igemm_tuned[igemm_key(p, EPI)] = best;
-    tune_mark_timed(TUNE_IGEMM, igemm_key(p, EPI));
-    return best;
-  }
-  if (!(p.CoutPad % 128 == 0 && p.Cin % 64 == 0)) return launch_igemm<EPI>(p, st);   // nothing to choose: a plain launch, the output stays valid
-  EventPair ev;
-  if (!ev.ok) return fail(MI355DET_ELAUNCH, "%s: event create failed", "conv_autotune");
-  hipEvent_t e0 = ev.e0, e1 = ev.e1;
-  int best = 1;
-  float best_ms = 1e30f;
-  const int cands[] = {1, 2, 3, 4, 5, 6, 15, 16, 17, 18, 19, 26, 27, 28, 40, 44, 45};     // 35 (BK 32, 3 workgroups per CU) measured slower: not tried
-  for (int cfg : cands) {
+  auto tried = [&](const CfgRow& r) {
+    if (!r.tuned || !cfg_applies(r, p)) return false;
     // data gradients run next to the weight-gradient stream: only tiles of <= 64 KB LDS (two workgroups per CU), which can share a CU
     // with a 64 KB weight-gradient workgroup; the one-per-CU tiles are a little faster alone and slower in the step (same-box A/B:
     // 1046-1047 vs 1039-1041 images/s; round 3's knob for the full list showed no difference on YOLO and is gone).
-    if ((EPI == EPI_PLAIN || EPI == EPI_RES) && (cfg == 3 || cfg == 6 || cfg == 16 || cfg == 17 || cfg == 18 || cfg == 19 || cfg == 26 || cfg == 27 || cfg == 28)) continue;
-    if ((cfg == 3 || cfg == 6) && p.CoutPad % 256 != 0) continue;
-    if (cfg == 40 && !(igemm8_applicable(p) && (EPI == EPI_STATS || EPI == EPI_PLAIN || EPI == EPI_RES || EPI == EPI_AFF || EPI == EPI_F32))) continue;
-    if ((cfg == 44 || cfg == 45) && !(igemm8_applicable(p) && (EPI == EPI_STATS || EPI == EPI_PLAIN || EPI == EPI_RES || EPI == EPI_AFF))) continue;
-    if (cfg >= 15 && (!dx_applicable(p) || ((cfg == 17 || cfg == 18 || cfg == 28) && p.CoutPad % 256 != 0))) continue;
+    if (r.solo && (EPI == EPI_PLAIN || EPI == EPI_RES)) return false;
+    // the phase-staggered kernel is timed on 3x3 stride-1 launches only (the committed tune records were made under this rule)
+    if (r.req == REQ_IG8 && !dx_applicable(p, 128, 64)) return false;
+    // the 32-deep k-step is for 32 input channels (32 -> 64 @320): a narrow shape has the plain tile and ONE alternative
+    return !(r.req == REQ_NARROW_DX && r.b == 32 && p.Cin % 64 == 0);
+  };
+  int nc = 0;
+  for (const CfgRow* r = cfg_rows<EPI>(); r->id >= 0; ++r) nc += tried(*r);
+  if (nc < 2) return launch_igemm<EPI>(p, st);   // nothing to choose: a plain launch, the output stays valid
+  EventPair ev;
+  if (!ev.ok) return fail(MI355DET_ELAUNCH, "%s: event create failed", "conv_autotune");
+  int best = p.CoutPad % 128 == 0 ? 1 : 0;
+  float best_ms = 1e30f;
+  for (const CfgRow* r = cfg_rows<EPI>(); r->id >= 0; ++r) {
+    if (!tried(*r)) continue;
     int e = 0;
-    const float ms = time_candidate([&] { return run_cfg<EPI>(cfg, p, st); }, e0, e1, st, &e);
+    const float ms = time_candidate([&] { return r->launch(p, st); }, ev.e0, ev.e1, st, &e);
     if (e) return e;
     if (ms < best_ms) {
       best_ms = ms;
-      best = cfg;
+      best = r->id;
     }
   }
   g_igemm_tuned[igemm_key(p, EPI)] = best;
@@ -1127,11 +1156,16 @@ bool g_autotune_mode = false;   // set by mi355det_conv_autotune around a regula
 TuneMap& g_s2cat_tuned = tune_table(TUNE_S2CAT);   // stride-2 data gradient: 1 = class-concatenated form, 0 = four class launches (tune record)
 int g_s2cat_force = -1;          // mi355det_debug_set(5, v): force a form (tests compare the two)
 
+// lattice pixel m IS the input / output pixel: the kernels skip the per-row divisions
+void set_linear(IgemmParams& p) {
+  p.lin_in = p.T == 1 && p.dy[0] == 0 && p.dx[0] == 0 && p.sin == 1 && p.MH == p.Hin && p.MW == p.Win;
+  p.lin_out = p.so == 1 && p.sox == 0 && p.oy0 == 0 && p.ox0 == 0 && p.MH == p.Hout && p.MW == p.Wout;
+}
+
 template <int EPI>
 int dispatch_igemm(const IgemmParams& p_in, hipStream_t st) {
   IgemmParams p = p_in;
-  p.lin_in = p.T == 1 && p.dy[0] == 0 && p.dx[0] == 0 && p.sin == 1 && p.MH == p.Hin && p.MW == p.Win;
-  p.lin_out = p.so == 1 && p.sox == 0 && p.oy0 == 0 && p.ox0 == 0 && p.MH == p.Hout && p.MW == p.Wout;
+  set_linear(p);
   return g_autotune_mode ? autotune_igemm<EPI>(p, st) : launch_igemm<EPI>(p, st);
 }
 
@@ -1154,13 +1188,6 @@ int check_shape(const mi355det_conv_shape* s, const char* what) {
     return fail(MI355DET_EINVAL, "%s: output size does not match the convolution geometry", what);
   if (s->in_ld < s->cin || s->out_ld < s->cout) return fail(MI355DET_EINVAL, "%s: pixel pitch smaller than channel count", what);
   return 0;
-}
-
-int grid_m_rows(const mi355det_conv_shape* s, int cout_pad) {
-  (void)cout_pad;
-  const int bm = 128;   // upper bound on the number of pixel tiles of any configuration
-  const long long M = (long long)s->n * s->ho * s->wo;
-  return (int)((M + bm - 1) / bm);
 }
 
 }  // namespace
@@ -1194,8 +1221,8 @@ int mi355det_debug_ptr(int key, void* ptr) {
 }
 
 int mi355det_conv_stats_rows(const mi355det_conv_shape* s, int32_t cout_pad) {
-  if (!s) return 0;
-  return grid_m_rows(s, cout_pad);
+  (void)cout_pad;      // tiles of 128 pixels: an upper bound on the number of pixel tiles of any configuration, whatever the padding
+  return s ? (int)(((long long)s->n * s->ho * s->wo + 127) / 128) : 0;
 }
 
 static int conv_fwd_impl(const mi355det_conv_shape* s, const void* x, const void* w, const float* bias, void* y, int out_f32, float* stats,
@@ -1241,7 +1268,6 @@ static int conv_fwd_impl(const mi355det_conv_shape* s, const void* x, const void
       p.ynstride = ex->out_image_stride;
     }
     if (out_f32 && ex->residual) return fail(MI355DET_EINVAL, "%s: residual needs a bf16 output", "conv_fwd_ex");
-    if (!out_f32 && (s->cout % 8)) return fail(MI355DET_EINVAL, "%s: bf16 outputs need cout %% 8 == 0", "conv_fwd_ex");
     const int r = out_f32 ? dispatch_igemm<EPI_F32>(p, S(stream)) : dispatch_igemm<EPI_AFF>(p, S(stream));
     return r < 0 ? r : 0;
   }
@@ -1283,6 +1309,32 @@ static int dgrad_taps(const mi355det_conv_shape* s, int py, int px, int* fwd_tap
       }
     }
   return n;
+}
+
+// The data gradient of `s` as an implicit GEMM over dy, for parity class (py, px) of a stride-2 layer ((0, 0) for stride 1): taps,
+// lattice, strides and origins, reduction over cout, cin output channels padded to 32.  The residual and the epilogue's own fields
+// are the caller's.  p.T == 0: a class that a 1x1 stride-2 convolution never reads (nothing to launch).
+static IgemmParams dgrad_params(const mi355det_conv_shape* s, int py, int px, const void* dy, const void* w, void* dx) {
+  IgemmParams p{};
+  int ft[9];
+  p.T = dgrad_taps(s, py, px, ft, p.dy, p.dx);
+  p.x = (const bf16_t*)dy;
+  p.w = (const bf16_t*)w;
+  p.y = dx;
+  p.zero = g_zero_page;
+  if (s->stride == 1) {
+    p.MH = s->h; p.MW = s->w; p.so = 1;
+  } else {
+    p.MH = (s->h + 1) / 2; p.MW = (s->w + 1) / 2; p.so = 2; p.oy0 = py; p.ox0 = px;
+  }
+  p.M = s->n * p.MH * p.MW;
+  p.Hin = s->ho; p.Win = s->wo; p.ldin = s->out_ld; p.Cin = s->cout; p.sin = 1;
+  p.Hout = s->h; p.Wout = s->w; p.ldout = s->in_ld;
+  p.Cout = s->cin; p.CoutPad = (s->cin + 31) / 32 * 32;
+  p.dMW = make_fastdiv((unsigned)p.MW);
+  p.dMH = make_fastdiv((unsigned)p.MH);
+  set_tap_pad(p);
+  return p;
 }
 
 size_t mi355det_dgrad_pack_elems(const mi355det_conv_shape* s) {
@@ -1529,26 +1581,16 @@ static int conv_dgrad_impl(const mi355det_conv_shape* s, const void* dy, const v
     auto run_cat = [&]() -> int {
       const bf16_t* wc = (const bf16_t*)wt + dgrad_class_elems(s);
       for (int py = 0; py < 2; ++py) {
-        IgemmParams p{};
+        IgemmParams p = dgrad_params(s, py, 0, dy, wc, dx);       // the ho x wo lattice (h, w even) over dy, output rows 2*yy + py; own taps and view:
         p.T = py ? 4 : 2;
         for (int t = 0; t < p.T; ++t) {
           p.dy[t] = py ? t >> 1 : 0;
           p.dx[t] = py ? t & 1 : t;
         }
-        p.x = (const bf16_t*)dy;
-        p.w = wc;
-        p.y = dx;
         p.res = (const bf16_t*)residual;
         p.ldres = 2 * s->cin;
-        p.zero = g_zero_page;
-        p.MH = s->ho; p.MW = s->wo;
-        p.M = s->n * s->ho * s->wo;
-        p.Hin = s->ho; p.Win = s->wo; p.ldin = s->out_ld; p.Cin = s->cout; p.sin = 1;
-        p.Hout = s->h; p.Wout = s->wo; p.ldout = 2 * s->cin;       // view [n, h, wo, 2*cin] of dx: a row of the view = the two pixels 2xx, 2xx+1
-        p.so = 2; p.sox = 1; p.oy0 = py; p.ox0 = 0;
+        p.Wout = s->wo; p.ldout = 2 * s->cin; p.sox = 1;          // view [n, h, wo, 2*cin] of dx: a row of the view = the two pixels 2xx, 2xx+1
         p.Cout = 2 * s->cin; p.CoutPad = 2 * s->cin;
-        p.dMW = make_fastdiv((unsigned)p.MW);
-        p.dMH = make_fastdiv((unsigned)p.MH);
         set_tap_pad(p);
         const int e = residual ? dispatch_igemm<EPI_RES>(p, S(stream)) : dispatch_igemm<EPI_PLAIN>(p, S(stream));
         if (e < 0) return e;
@@ -1585,37 +1627,18 @@ static int conv_dgrad_impl(const mi355det_conv_shape* s, const void* dy, const v
     }
   }
   for (int c = 0; c < classes; ++c) {
-    IgemmParams p{};
-    int ft[9];
-    p.T = dgrad_taps(s, c >> 1, c & 1, ft, p.dy, p.dx);
+    IgemmParams p = dgrad_params(s, c >> 1, c & 1, dy, wp, dx);
     if (p.T == 0 && partials) return fail(MI355DET_EINVAL, "%s: 1x1 stride-2 layers are not supported by the fused BN reduction", "conv_dgrad_bn");
     if (p.T == 0) {
       // 1x1 stride-2 convolutions never read the odd input rows / columns: their data gradient is zero (+ residual)
       const int mh = (s->h + 1) / 2, mw = (s->w + 1) / 2;
       const long long total = (long long)s->n * mh * mw * (s->cin / 8);
-      if (s->cin % 8) return fail(MI355DET_EINVAL, "%s: cin must be a multiple of 8", "conv_dgrad");
       hipLaunchKernelGGL(lattice_fill_kernel, dim3((int)min((long long)4096, (total + 255) / 256)), dim3(256), 0, S(stream), (bf16_t*)dx, s->in_ld,
                          (const bf16_t*)residual, residual_ld, s->n, s->h, s->w, mh, mw, c >> 1, c & 1, s->cin);
       continue;
     }
-    p.x = (const bf16_t*)dy;
-    p.w = wp;
-    p.y = dx;
     p.res = (const bf16_t*)residual;
     p.ldres = residual_ld;
-    p.zero = g_zero_page;
-    if (s->stride == 1) {
-      p.MH = s->h; p.MW = s->w; p.so = 1; p.oy0 = 0; p.ox0 = 0;
-    } else {
-      p.MH = (s->h + 1) / 2; p.MW = (s->w + 1) / 2; p.so = 2; p.oy0 = c >> 1; p.ox0 = c & 1;
-    }
-    p.M = s->n * p.MH * p.MW;
-    p.Hin = s->ho; p.Win = s->wo; p.ldin = s->out_ld; p.Cin = s->cout; p.sin = 1;
-    p.Hout = s->h; p.Wout = s->w; p.ldout = s->in_ld;
-    p.Cout = s->cin; p.CoutPad = cin_pad;
-    p.dMW = make_fastdiv((unsigned)p.MW);
-    p.dMH = make_fastdiv((unsigned)p.MH);
-    set_tap_pad(p);
     int e;
     if (partials) {
       p.z = (const bf16_t*)z;
@@ -1650,26 +1673,11 @@ int mi355det_conv_dgrad_mask(const mi355det_conv_shape* s, const void* dy, const
   if (s->stride != 1) return fail(MI355DET_EINVAL, "%s: stride-1 convolutions only", "conv_dgrad_mask");
   if (s->cout % 32 != 0) return fail(MI355DET_EINVAL, "%s: Cout (the dgrad reduction dim) must be a multiple of 32 (got %lld)", "conv_dgrad_mask", s->cout);
   if (s->cin % 8 != 0 || act_ld % 8 != 0 || act_ld < s->cin) return fail(MI355DET_EINVAL, "%s: cin and the activation pitch must be multiples of 8", "conv_dgrad_mask");
-  const int cin_pad = (s->cin + 31) / 32 * 32;
-  IgemmParams p{};
-  int ft[9];
-  p.T = dgrad_taps(s, 0, 0, ft, p.dy, p.dx);
-  p.x = (const bf16_t*)dy;
-  p.w = (const bf16_t*)wt;
-  p.y = dx;
+  IgemmParams p = dgrad_params(s, 0, 0, dy, wt, dx);
   p.res = (const bf16_t*)act;
   p.ldres = act_ld;
   p.scale = scale;
   p.relu = relu ? 3 : 4;
-  p.zero = g_zero_page;
-  p.MH = s->h; p.MW = s->w; p.so = 1;
-  p.M = s->n * p.MH * p.MW;
-  p.Hin = s->ho; p.Win = s->wo; p.ldin = s->out_ld; p.Cin = s->cout; p.sin = 1;
-  p.Hout = s->h; p.Wout = s->w; p.ldout = s->in_ld;
-  p.Cout = s->cin; p.CoutPad = cin_pad;
-  p.dMW = make_fastdiv((unsigned)p.MW);
-  p.dMH = make_fastdiv((unsigned)p.MH);
-  set_tap_pad(p);
   const int e = dispatch_igemm<EPI_RES>(p, S(stream));
   return e < 0 ? e : 0;
 }
@@ -1741,27 +1749,14 @@ int mi355det_conv_dgrad_ws(const mi355det_conv_shape* s, const void* dy, const v
   if (!dy || !wt || !dx) return fail(MI355DET_EINVAL, "%s: null argument", "conv_dgrad_ws");
   if (workspace_bytes < mi355det_conv_dgrad_workspace(s)) return fail(MI355DET_EINVAL, "%s: workspace too small (%zu < %zu bytes)", "conv_dgrad_ws", workspace_bytes, mi355det_conv_dgrad_workspace(s));
   if (s->cin % 8 != 0 || (residual && residual_ld % 8 != 0)) return fail(MI355DET_EINVAL, "%s: cin and the residual pitch must be multiples of 8", "conv_dgrad_ws");
-  const int cin_pad = (s->cin + 31) / 32 * 32;
-  IgemmParams p{};
-  int ft[9];
-  p.T = dgrad_taps(s, 0, 0, ft, p.dy, p.dx);
-  p.x = (const bf16_t*)dy;
-  p.w = (const bf16_t*)wt;
-  p.y = workspace;
-  p.zero = g_zero_page;
-  p.MH = s->h; p.MW = s->w; p.so = 1;
-  p.M = s->n * p.MH * p.MW;
-  p.Hin = s->ho; p.Win = s->wo; p.ldin = s->out_ld; p.Cin = s->cout; p.sin = 1;
-  p.Hout = s->h; p.Wout = s->w; p.ldout = cin_pad;
+  IgemmParams p = dgrad_params(s, 0, 0, dy, wt, workspace);      // fp32 partial tiles [ks][M][cin_pad]
+  const int cin_pad = p.CoutPad;
+  p.ldout = cin_pad;
   p.ynstride = (long long)s->h * s->w * cin_pad;
-  p.Cout = cin_pad; p.CoutPad = cin_pad;                          // the padded channels of the partial tiles are exact zeros (zero weight rows)
+  p.Cout = cin_pad;                                               // the padded channels of the partial tiles are exact zeros (zero weight rows)
   p.ksplit = ks;
   p.ysplit = (long long)p.M * cin_pad;
-  p.dMW = make_fastdiv((unsigned)p.MW);
-  p.dMH = make_fastdiv((unsigned)p.MH);
-  set_tap_pad(p);
-  p.lin_in = p.T == 1 && p.dy[0] == 0 && p.dx[0] == 0 && p.sin == 1 && p.MH == p.Hin && p.MW == p.Win;
-  p.lin_out = 1;
+  set_linear(p);
   if (int e = launch_cfg<2, 2, 4, 4, 64, 2, EPI_F32>(p, S(stream))) return e;
   const long long total = (long long)p.M * (s->cin / 8);
   hipLaunchKernelGGL(splitk_reduce_kernel, dim3((int)min((long long)2048, (total + 255) / 256)), dim3(256), 0, S(stream), (const float*)workspace, ks, p.ysplit,

@@ -588,8 +588,9 @@ int igemm8_launch(int epi, const IgemmParams& p, hipStream_t st, int rows) {
     case EPI_PLAIN: return launch8_rows<EPI_PLAIN>(p, st, rows);
     case EPI_RES: return launch8_rows<EPI_RES>(p, st, rows);
     case EPI_AFF: return launch8_rows<EPI_AFF>(p, st, rows);
-    case EPI_F32: return rows == 256 ? launch8<EPI_F32>(p, st) : fail(MI355DET_EINVAL, "%s: the fp32 head epilogue is built for the 256-pixel tile only", "igemm8");      // (the 1204-class cls_logits: Cout padded to 256)
+    case EPI_F32: if (rows == 256) return launch8<EPI_F32>(p, st); break;      // (the 1204-class cls_logits: Cout padded to 256)
     default: break;
   }
-  return fail(MI355DET_EINVAL, "%s: epilogue not built for the phase-staggered kernel", "igemm8");
+  // defensive: which epilogues and tile heights are launched is stated by rows 40 / 44 / 45 of conv_kernels.hip's configuration table
+  return fail(MI355DET_EINVAL, "%s: epilogue %lld not built for the phase-staggered kernel at %lld-pixel tiles", "igemm8", epi, rows);
 }

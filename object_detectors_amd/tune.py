@@ -146,7 +146,7 @@ def plan_build(build, group=None, share=None):
 
 
 # ---- step-level refinement ------------------------------------------------------------------------------------------------------------
-IGEMM_CANDIDATES = (1, 2, 3, 4, 5, 6, 15, 16, 17, 18, 19, 26, 27, 28, 40, 44, 45)      # conv_kernels.hip:autotune_igemm cands[]
+IGEMM_CANDIDATES = (1, 2, 3, 4, 5, 6, 15, 16, 17, 18, 19, 26, 27, 28, 40, 44, 45)      # conv_kernels.hip: the tuned wide rows of the configuration table
 WGRAD_FORM8 = 1 << 16
 _NARROW = {0: (29, 30, 31), 29: (0,), 30: (0,), 31: (0,)}
 

@@ -1,7 +1,7 @@
 """Coverage table of the convolution engine's tunable kernels (data only, no GPU).
 
-Every tile configuration the plan-time tuner may pick (conv_kernels.hip: autotune_igemm's cands[]), the narrow-output alternatives 29 / 30 /
-31 and the untuned default 0 appear here with every epilogue their run_cfg branch accepts, each on a shape where the id applies ("clean":
+Every tile configuration the plan-time tuner may pick (conv_kernels.hip: the tuned rows of the configuration table), the narrow-output
+alternatives 29 / 30 / 31 and the untuned default 0 appear here with every epilogue their table row accepts, each on a shape where the id applies ("clean":
 whole tiles) and on one with tails (a pixel count that is not a multiple of any tile height, an image boundary inside a tile, a partial
 last channel tile).  Beside them: the stride-2 data-gradient routes, the split-K data gradient and the weight-gradient split counts.
 
@@ -93,8 +93,8 @@ def epilogue(case):
 
 
 # ---- tile configurations (conv_kernels.hip)
-WIDE_IDS = (1, 2, 3, 4, 5, 6, 15, 16, 17, 18, 19, 26, 27, 28, 40, 44, 45)     # autotune_igemm: cands[]
-NARROW_IDS = (29, 30, 31)                                                      # autotune_igemm: the narrow-output alternatives
+WIDE_IDS = (1, 2, 3, 4, 5, 6, 15, 16, 17, 18, 19, 26, 27, 28, 40, 44, 45)     # the tuned wide rows, in table order
+NARROW_IDS = (29, 30, 31)                                                      # the narrow-output alternatives to the plain tile
 DX_IDS = (15, 16, 17, 18, 19, 26, 27, 28)                                      # shared-pixel-tile kernel: 3x3, stride 1
 ALL_EPIS = ("STATS", "F32", "RES", "PLAIN", "AFF", "BNRED")
 ACCEPTS = {i: ALL_EPIS for i in WIDE_IDS + NARROW_IDS + (0,)}
@@ -140,7 +140,7 @@ def _name(entry, sh, cfg, opts):
 
 
 def _applies(cfg, case):
-    """Does forced id `cfg` run on this case (conv_kernels.hip: launch_igemm / run_cfg predicates)?  The table only keeps cases where it does:
+    """Does forced id `cfg` run on this case (conv_kernels.hip: cfg_applies on the id's table row)?  The table only keeps cases where it does:
     strict mode turns every other combination into an error."""
     ep = epilogue(case)
     if ep is None or ep not in ACCEPTS.get(cfg, ()):

@@ -34,26 +34,28 @@ def function_body(text, signature):
     raise AssertionError(signature)
 
 
+ROW = re.compile(r"^\s*CFG_ROW\(\s*(\d+),\s*([eA-Z0-9 |]+?),\s*(REQ_[A-Z_0-9]+),\s*(\d+),\s*(\d+),\s*([01]),\s*([01]),", re.M)
+MASKS = dict({"e" + n: (n,) for n in EPI_NAMES.values()}, eALL=tuple(EPI_NAMES.values()))
+
+
+def cfg_rows():
+    """conv_kernels.hip: the rows of the tile configuration table, in file order (= the order the tuner tries them)."""
+    rows = [{"id": int(m[1]), "epis": tuple(sorted({n for e in m[2].split("|") for n in MASKS[e.strip()]})), "req": m[3], "a": int(m[4]),
+             "b": int(m[5]), "tuned": m[6] == "1", "solo": m[7] == "1"} for m in ROW.finditer(src("conv_kernels.hip"))]
+    assert len(rows) == src("conv_kernels.hip").count("CFG_ROW(") - 1 and len({r["id"] for r in rows}) == len(rows)      # (- 1: the #define)
+    return rows
+
+
 def igemm_candidates():
-    body = function_body(src("conv_kernels.hip"), "int autotune_igemm(")
-    m = re.search(r"const int cands\[\] = \{([^}]*)\}", body)
-    wide = tuple(int(v) for v in m.group(1).split(","))
-    alts = re.search(r"const int alt = narrow32 \? (\d+) : \(p\.CoutPad % 64 == 0 \? (\d+) : (\d+)\)", body)
-    return wide, tuple(sorted(int(v) for v in alts.groups()))
+    """The ids the tuner tries: on wide outputs (in order), and the alternatives to the plain tile (id 0) on narrow ones."""
+    tuned = [r for r in cfg_rows() if r["tuned"]]
+    wide = tuple(r["id"] for r in tuned if not r["req"].startswith("REQ_NARROW"))
+    return wide, tuple(sorted(r["id"] for r in tuned if r["req"] == "REQ_NARROW_DX"))
 
 
 def run_cfg_epilogues():
-    """id -> epilogues its run_cfg branch accepts (a branch without an EPI condition accepts all of them)."""
-    body = function_body(src("conv_kernels.hip"), "int run_cfg(int cfg")
-    out = {}
-    for line in body.splitlines():
-        m = re.match(r"\s*case (\d+):(.*)", line)
-        if not m:
-            continue
-        code = m.group(2).split("//")[0]
-        named = re.findall(r"EPI == (EPI_[A-Z0-9]+)", code)
-        out[int(m.group(1))] = tuple(sorted({EPI_NAMES[n] for n in named})) if named else tuple(sorted(EPI_NAMES.values()))
-    return out
+    """id -> epilogues its table row accepts."""
+    return {r["id"]: r["epis"] for r in cfg_rows()}
 
 
 def covered():
@@ -68,15 +70,15 @@ def covered():
 
 def test_table_lists_the_tuner_candidates():
     wide, narrow = igemm_candidates()
-    assert wide == MX.WIDE_IDS, "conv_kernels.hip: autotune_igemm's cands[] changed: update tests/conv_matrix.py"
+    assert wide == MX.WIDE_IDS, "conv_kernels.hip: the tuned rows of the configuration table changed: update tests/conv_matrix.py"
     assert narrow == MX.NARROW_IDS
 
 
 def test_table_epilogue_sets_match_run_cfg():
     acc = run_cfg_epilogues()
-    for cfg in MX.WIDE_IDS:
-        want = acc.get(cfg, tuple(sorted(EPI_NAMES.values())))      # (configuration 1 is the default branch: all epilogues)
-        assert tuple(sorted(MX.ACCEPTS[cfg])) == want, f"configuration {cfg}: run_cfg accepts {want}"
+    for cfg in (0,) + MX.WIDE_IDS + MX.NARROW_IDS:
+        want = acc[cfg]
+        assert tuple(sorted(MX.ACCEPTS[cfg])) == want, f"configuration {cfg}: its table row accepts {want}"
 
 
 @pytest.mark.parametrize("cfg", (0,) + MX.WIDE_IDS + MX.NARROW_IDS)
@@ -195,7 +197,7 @@ def test_every_record_choice_is_a_covered_case(name, entries):
 def test_coverage_check_bites():
     """Removing an id from the table, or a record entry for a pair no case runs, must fail the checks above."""
     cov = covered()
-    assert (44, "F32") not in cov and (40, "BNRED") not in cov          # excluded by run_cfg: no case, and a record naming them...
+    assert (44, "F32") not in cov and (40, "BNRED") not in cov          # excluded by their table rows: no case, and a record naming them...
     f = {"f16": 0, "epi": MX.EPI["F32"], "sox": 0, "sin": 1, "so": 1, "T": 9}
     assert effective_cfg(44, f) == (1, "F32")                            # ...runs configuration 1, which is covered
     stripped = defaultdict(set)
