@@ -14,8 +14,11 @@
 
 #include <cstdlib>
 #include <unordered_map>
+#include <vector>
 
 #include "tune_record.h"
+#include "tune_timing.h"
+#include "wgrad_choice.h"
 
 using namespace mi355;
 
@@ -926,25 +929,9 @@ __global__ __launch_bounds__(256) void colsum8_kernel(const bf16_t* __restrict__
   }
 }
 
-// Split count over the pixel axis from a small cost model (us): whole rounds of 512 resident workgroups, ~0.85 us per
-// 64-pixel k-step at 2 workgroups/CU, plus the slab round trip (~3 TB/s) and one extra launch when splitting.
-int choose_splits(int tiles, int M, double out_bytes) {
-  (void)out_bytes;
-  // default when the shape was not autotuned: fill (not exceed) one round of 512 resident workgroups
-  int sp = max(1, min(1024, 512 / max(1, tiles)));
-  sp = max(1, min(sp, M / 2048));
-  while (sp > 1) {
-    const int chunk = ((M + sp - 1) / sp + WG_BKP - 1) / WG_BKP * WG_BKP;
-    if ((M + chunk - 1) / chunk == sp) break;
-    --sp;
-  }
-  return sp;
-}
-
-// shape key -> split count found by mi355det_conv_autotune (part of the tune record); + WG_FORM8 = the 256 x 256 phase-staggered kernel
+// shape key -> split count found by mi355det_conv_wgrad_autotune (part of the tune record); + WG_FORM8 = the 256 x 256 phase-staggered kernel
 TuneMap& g_wgrad_tuned = tune_table(TUNE_WGRAD);
-int g_wgrad_force = 0;
-constexpr int WG_FORM8 = 1 << 16;
+static_assert(WGC_STEP == WG_BKP && WGC_TILE == WG_TILE && WGC_TILE8 == W8_TILE, "wgrad_choice.h describes these kernels");
 
 unsigned long long wgrad_key(const mi355det_conv_shape* s) {
   unsigned long long k = (unsigned long long)(s->n * s->ho * s->wo);
@@ -953,11 +940,6 @@ unsigned long long wgrad_key(const mi355det_conv_shape* s) {
   k = k * 17 + s->ksize * 4 + s->stride;
   k = k * 2 + MI355_F16;
   return k;
-}
-
-bool split_valid(int M, int sp) {
-  const int chunk = ((M + sp - 1) / sp + WG_BKP - 1) / WG_BKP * WG_BKP;
-  return (M + chunk - 1) / chunk == sp;
 }
 
 bf16_t* g_zero_page_w = nullptr;
@@ -969,193 +951,43 @@ int ensure_zero_page_w() {
   return 0;
 }
 
-// wgrad8_kernel: pieces of 4 pixels spanning at most two image rows, one wrap per 64-pixel advance, 31-bit byte offsets, at least one whole 256-wide
-// tile in both directions (a narrower output would multiply zero fragments: the 128 x 128 kernel is the better tile there; the last co tile
-// of a wide output may be partial - the 10 836 channels of the 1204-class cls_logits are 42.3 tiles)
-bool wgrad8_applicable(const mi355det_conv_shape* s) {
-  const long long NP = (long long)s->ksize * s->ksize * s->cin;
-  if (s->wo < 4 || WG_BKP / s->wo + 1 > s->ho || s->cout < 256 || NP < 256 || s->cin % 8 != 0) return false;
-  return ((long long)s->n * s->h * s->w + (long long)s->pad * (s->w + 1)) * s->in_ld * 2 < 0x7FFFFFF0ll;
-}
-
-}  // namespace
-
-extern "C" {
-
-size_t mi355det_conv_wgrad_workspace(const mi355det_conv_shape* s) {
-  if (!s) return 0;
-  // room for the largest split count the autotuner may pick: capped at 128 MiB, but never below three splits (the 1204-class cls_logits has
-  // 100 MB of dW: its 387 tiles of 256 x 256 are 1.5 rounds of 256 CUs with one pixel range and 3.0 with two)
-  const size_t tiles = (size_t)((s->cout + WG_TILE - 1) / WG_TILE) * (size_t)((s->ksize * s->ksize * s->cin + WG_TILE - 1) / WG_TILE);
-  const size_t per_split = tiles * WG_TILE * WG_TILE * sizeof(float);
-  size_t splits = 1024;
-  while (splits > 3 && splits * per_split > ((size_t)128 << 20)) --splits;
-  return splits * per_split;
-}
-
-// Times the candidate split counts on the caller's buffers (synchronises: plan-build time only, never in the step)
-// and remembers the fastest for this shape.  dw receives garbage accumulations: the caller re-zeroes it.
-int mi355det_conv_wgrad_autotune(const mi355det_conv_shape* s, const void* x, const void* dy, float* dw, void* workspace,
-                                 size_t workspace_bytes, void* stream) {
-  if (!s) return fail(MI355DET_EINVAL, "%s: null shape", "wgrad_autotune");
-  if (tune_locked_has(TUNE_WGRAD, wgrad_key(s))) return g_wgrad_tuned[wgrad_key(s)];      // the split came from a tune record: not timed again
-  const int M = s->n * s->ho * s->wo;
-  const size_t tiles = (size_t)((s->cout + WG_TILE - 1) / WG_TILE) * (size_t)((s->ksize * s->ksize * s->cin + WG_TILE - 1) / WG_TILE);
-  const size_t per_split = tiles * WG_TILE * WG_TILE * sizeof(float);
-  const int cands[] = {1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 20, 24, 28, 32, 40, 48, 56, 64, 96, 128, 192, 256, 384, 512, 768, 1024};
-  hipEvent_t e0, e1;
-  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return fail(MI355DET_ELAUNCH, "%s: event create failed", "wgrad_autotune");
-  int best = -1;
-  float best_ms = 1e30f;
-  int tried[32], n_tried = 0;
-  float tried_ms[32];
-  for (int sp : cands) {
-    if (sp > 1 && (sp * per_split > workspace_bytes || M / sp < 512 || (size_t)sp * tiles > 4096)) continue;
-    if (!split_valid(M, sp)) continue;
-    g_wgrad_force = sp;
-    int e = mi355det_conv_wgrad(s, x, dy, dw, nullptr, workspace, workspace_bytes, stream);   // warm-up
-    if (e) {
-      g_wgrad_force = 0;
-      (void)hipEventDestroy(e0);
-      (void)hipEventDestroy(e1);
-      return e;
-    }
-    float ms = 1e30f;
-    for (int b = 0; b < 2; ++b) {      // the faster of two batches of three (one batch let a cold L2 or a neighbour's burst decide)
-      (void)hipEventRecord(e0, S(stream));
-      for (int r = 0; r < 3; ++r) (void)mi355det_conv_wgrad(s, x, dy, dw, nullptr, workspace, workspace_bytes, stream);
-      (void)hipEventRecord(e1, S(stream));
-      (void)hipEventSynchronize(e1);
-      float t = 0.f;
-      (void)hipEventElapsedTime(&t, e0, e1);
-      if (t < ms) ms = t;
-    }
-    tried[n_tried] = sp;
-    tried_ms[n_tried++] = ms;
-    if (ms < best_ms) {
-      best_ms = ms;
-      best = sp;
-    }
-  }
-  // the phase-staggered 256 x 256 form: one or two whole rounds of one-workgroup-per-CU launches
-  int best8 = -1;
-  float best8_ms = 1e30f;
-  if (wgrad8_applicable(s) && !g_wgrad8_off) {
-    const int t8 = (int)(((s->cout + 255) / 256) * ((s->ksize * s->ksize * s->cin + 255) / 256));
-    int c8[7] = {256 / t8, 512 / t8, 128 / t8, 768 / t8, 1, 2, 3};
-    for (int a = 0; a < 7; ++a) {
-      const int sp = c8[a];
-      bool dup = sp < 1;
-      for (int b = 0; b < a; ++b) dup = dup || c8[b] == sp;
-      if (dup || (sp > 1 && (sp * per_split > workspace_bytes || M / sp < 512)) || !split_valid(M, sp)) continue;
-      g_wgrad_force = sp | WG_FORM8;
-      if (int e = mi355det_conv_wgrad(s, x, dy, dw, nullptr, workspace, workspace_bytes, stream)) {
-        g_wgrad_force = 0;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        return e;
-      }
-      float ms = 1e30f;
-      for (int b = 0; b < 2; ++b) {
-        (void)hipEventRecord(e0, S(stream));
-        for (int r = 0; r < 3; ++r) (void)mi355det_conv_wgrad(s, x, dy, dw, nullptr, workspace, workspace_bytes, stream);
-        (void)hipEventRecord(e1, S(stream));
-        (void)hipEventSynchronize(e1);
-        float t = 0.f;
-        (void)hipEventElapsedTime(&t, e0, e1);
-        if (t < ms) ms = t;
-      }
-      if (ms < best8_ms) {
-        best8_ms = ms;
-        best8 = sp;
-      }
-    }
-  }
-  // Beside the data-gradient stream fewer, longer workgroups and less slab traffic win over the split count that is fastest alone (the step-level
-  // refinement of round 4 halved the split counts of the big layers: profiles/r04_ab_results.md 7): take the SMALLEST split count within 4 % of
-  // the fastest one.
-  for (int i = 0; i < n_tried; ++i)
-    if (tried_ms[i] <= best_ms * 1.04f) {
-      best = tried[i];
-      break;
-    }
-  if (best8 > 0 && best8_ms < best_ms * 0.97f) best = best8 | WG_FORM8;
-  g_wgrad_force = 0;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  if (best > 0) {
-    g_wgrad_tuned[wgrad_key(s)] = best;
-    tune_mark_timed(TUNE_WGRAD, wgrad_key(s));
-  }
-  return best;
-}
-
-int mi355det_conv_wgrad(const mi355det_conv_shape* s, const void* x, const void* dy, float* dw, float* dbias, void* workspace,
-                        size_t workspace_bytes, void* stream) {
-  if (!s) return fail(MI355DET_EINVAL, "%s: null shape", "conv_wgrad");
+// argument checks of both entry points (the tuner's launches are launches of mi355det_conv_wgrad)
+int wgrad_check(const mi355det_conv_shape* s) {
   if (int e = ensure_zero_page_w()) return e;
   if (s->cin % 8 != 0) return fail(MI355DET_EINVAL, "%s: Cin must be a multiple of 8 (got %lld)", "conv_wgrad", s->cin);
   if (s->out_ld % 8 != 0 || s->in_ld % 8 != 0) return fail(MI355DET_EINVAL, "%s: pixel pitches must be multiples of 8", "conv_wgrad");
+  return 0;
+}
+
+// the kernel of choice `c`, the fold of its slabs and the bias column sums (wgrad_check passed)
+int wgrad_launch(const mi355det_conv_shape* s, const void* x, const void* dy, float* dw, float* dbias, void* workspace, size_t workspace_bytes,
+                 const WgradChoice& c, void* stream) {
+  const WgradGeom g(s);
+  if (c.splits > 1 && (!workspace || workspace_bytes < c.splits * g.per_split))
+    return fail(MI355DET_EWORKSPACE, "%s: workspace too small (%lld bytes needed)", "conv_wgrad", (long long)(c.splits * g.per_split));
   WgradParams p{};
   p.x = (const bf16_t*)x;
   p.dy = (const bf16_t*)dy;
   p.dw = dw;
   p.zero = g_zero_page_w;
-  p.M = s->n * s->ho * s->wo;
+  p.M = g.M;
   p.Ho = s->ho; p.Wo = s->wo; p.H = s->h; p.W = s->w;
   p.ldx = s->in_ld; p.lddy = s->out_ld;
   p.Cin = s->cin; p.Cout = s->cout; p.stride = s->stride; p.pad = s->pad; p.ks = s->ksize;
   p.T = s->ksize * s->ksize;
-  p.NP = p.T * p.Cin;
-  p.co_tiles = (p.Cout + WG_TILE - 1) / WG_TILE;
-  p.np_tiles = (p.NP + WG_TILE - 1) / WG_TILE;
+  p.NP = g.NP;
+  p.co_tiles = g.co_tiles;
+  p.np_tiles = g.np_tiles;
   p.ablate = g_wgrad_ablate;
-  const int tiles = p.co_tiles * p.np_tiles;
-  int splits = choose_splits(tiles, p.M, 4.0 * p.Cout * (double)p.NP);
-  bool form8 = false;
-  {
-    auto it = g_wgrad_tuned.find(wgrad_key(s));
-    if (it != g_wgrad_tuned.end()) {
-      splits = it->second & (WG_FORM8 - 1);
-      form8 = (it->second & WG_FORM8) != 0;
-    }
-    const int force = g_wgrad_force > 0 ? g_wgrad_force : g_wgrad_force_dbg;
-    if (g_conv_strict && g_wgrad_force <= 0 && g_wgrad_force_dbg > 0) {      // strict mode: the forced split is launched as it is or not at all
-      const int sp = g_wgrad_force_dbg & (WG_FORM8 - 1);
-      const size_t need = (size_t)sp * tiles * WG_TILE * WG_TILE * sizeof(float);
-      if (!split_valid(p.M, sp))
-        return fail(MI355DET_EINVAL, "%s: forced split count %lld is not valid for %lld pixels (strict mode, debug key 9)", "conv_wgrad", sp, p.M);
-      if (sp > 1 && (!workspace || need > workspace_bytes))
-        return fail(MI355DET_EINVAL, "%s: forced split count %lld needs %lld workspace bytes (strict mode, debug key 9)", "conv_wgrad", sp, (long long)need);
-    }
-    if (force > 0 && split_valid(p.M, force & (WG_FORM8 - 1))) {
-      splits = force & (WG_FORM8 - 1);
-      form8 = (force & WG_FORM8) != 0;
-    }
-    if (splits < 1) splits = 1;
-    if (g_wgrad_force <= 0 && (g_wgrad_force_dbg & WG_FORM8) && !(form8 && wgrad8_applicable(s)))      // the diagnostic switch must not fall back silently
-      return fail(MI355DET_EINVAL, "%s: the phase-staggered kernel was forced (debug key 7) for a shape or split count it does not take", "conv_wgrad");
-    form8 = form8 && wgrad8_applicable(s);      // (a record written for another build: fall back to the 128 x 128 kernel, same split count)
-    const size_t per_split = (size_t)tiles * WG_TILE * WG_TILE * sizeof(float);
-    while (splits > 1 && (splits * per_split > workspace_bytes || !split_valid(p.M, splits))) --splits;
-  }
-  int chunk = (p.M + splits - 1) / splits;
-  chunk = (chunk + WG_BKP - 1) / WG_BKP * WG_BKP;
-  splits = (p.M + chunk - 1) / chunk;
-  p.splits = splits;
-  p.chunk = chunk;
-  p.slab = nullptr;
-  if (splits > 1) {
-    const size_t need = (size_t)splits * tiles * WG_TILE * WG_TILE * sizeof(float);
-    if (!workspace || workspace_bytes < need) return fail(MI355DET_EWORKSPACE, "%s: workspace too small (%lld bytes needed)", "conv_wgrad", (long long)need);
-    if (p.NP % 4 != 0) return fail(MI355DET_EINVAL, "%s: k*k*Cin must be a multiple of 4", "conv_wgrad");
-    p.slab = (float*)workspace;
-  }
+  p.splits = c.splits;
+  p.chunk = c.chunk;
+  p.slab = c.splits > 1 ? (float*)workspace : nullptr;
   p.step_q = WG_BKP / p.Wo;
   p.step_r = WG_BKP % p.Wo;
   p.dWo = make_fastdiv((unsigned)p.Wo);
   p.dHo = make_fastdiv((unsigned)p.Ho);
   p.dCin = make_fastdiv((unsigned)p.Cin);
+  const int tiles = g.tiles, splits = c.splits;
   // (Measured and reverted, round 4: ONE workgroup per CU - 96 KB of dynamic LDS - for launches with many LONG workgroups.  The 1204-class
   //  cls_logits weight gradient of RetinaNet-LVIS has 1530 tiles x 1250 k-steps = 1.6 ms per workgroup and no split fits the workspace; two of
   //  them per CU leave 32 KB of LDS, so a 64 KB tile of the dependency-chain stream waits for a whole round: three FPN data gradients of
@@ -1171,12 +1003,10 @@ int mi355det_conv_wgrad(const mi355det_conv_shape* s, const void* x, const void*
   };
   // scalar pixel bookkeeping: a 4-pixel piece may span at most two image rows, byte offsets into x must fit 31 bits
   const int grp4 = g_wgrad_general != 0 || p.Wo < 4 || WG_BKP / p.Wo + 1 > p.Ho ? 0 : (p.Wo % 16 == 0 ? 3 : (p.Wo % 4 == 0 ? 1 : 2));
-  const bool fits =
-                    ((long long)s->n * p.H * p.W + (long long)p.pad * (p.W + 1)) * p.ldx * 2 < 0x7FFFFFF0ll &&
-                    (long long)chunk * p.lddy * 2 < 0x7FFFFFF0ll;
-  if (form8 && !fits && g_conv_strict && g_wgrad_force <= 0 && (g_wgrad_force_dbg & WG_FORM8))
-    return fail(MI355DET_EINVAL, "%s: the forced phase-staggered kernel does not fit the 31-bit offsets of this shape (strict mode, debug key 9)", "conv_wgrad");
-  if (form8 && fits) {
+  // A choice of the 256 x 256 form whose chunk does not fit the 31-bit offsets runs - and, as a tuner candidate, is timed - as the 128 x 128 kernel
+  // (strict mode with debug key 7 rejected it in wgrad_resolve).
+  const bool fits = wgrad_fits(s, c.chunk);
+  if (c.form8 && fits) {
     const int tiles8 = ((p.Cout + W8_TILE - 1) / W8_TILE) * ((p.NP + W8_TILE - 1) / W8_TILE);
     static DeviceOnce attr8;
     attr8.once([&] {
@@ -1228,6 +1058,49 @@ int mi355det_conv_wgrad(const mi355det_conv_shape* s, const void* x, const void*
     }
   }
   return check_launch("conv_wgrad");
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t mi355det_conv_wgrad_workspace(const mi355det_conv_shape* s) { return s ? wgrad_workspace_bytes(WgradGeom(s)) : 0; }
+
+// Times the candidate split counts on the caller's buffers (synchronises: plan-build time only, never in the step)
+// and remembers the fastest for this shape.  dw receives garbage accumulations: the caller re-zeroes it.
+int mi355det_conv_wgrad_autotune(const mi355det_conv_shape* s, const void* x, const void* dy, float* dw, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+  if (!s) return fail(MI355DET_EINVAL, "%s: null shape", "wgrad_autotune");
+  if (tune_locked_has(TUNE_WGRAD, wgrad_key(s))) return g_wgrad_tuned[wgrad_key(s)];      // the split came from a tune record: not timed again
+  const WgradGeom g(s);
+  const std::vector<int> cands = wgrad_candidates(s, g, workspace_bytes, !g_wgrad8_off);
+  std::vector<float> ms;
+  EventPair ev;
+  if (!ev.ok) return fail(MI355DET_ELAUNCH, "%s: event create failed", "wgrad_autotune");
+  if (int e = wgrad_check(s)) return e;
+  for (int v : cands) {
+    const WgradChoice c = {v & (WG_FORM8 - 1), (v & WG_FORM8) != 0, g.chunk_of(v & (WG_FORM8 - 1))};
+    int e = 0;
+    ms.push_back(time_candidate([&] { return wgrad_launch(s, x, dy, dw, nullptr, workspace, workspace_bytes, c, stream); }, ev.e0, ev.e1, S(stream), &e));
+    if (e) return e;
+  }
+  const int best = wgrad_pick(cands.data(), ms.data(), (int)cands.size());
+  if (best > 0) {
+    g_wgrad_tuned[wgrad_key(s)] = best;
+    tune_mark_timed(TUNE_WGRAD, wgrad_key(s));
+  }
+  return best;
+}
+
+int mi355det_conv_wgrad(const mi355det_conv_shape* s, const void* x, const void* dy, float* dw, float* dbias, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+  if (!s) return fail(MI355DET_EINVAL, "%s: null shape", "conv_wgrad");
+  if (int e = wgrad_check(s)) return e;
+  const auto it = g_wgrad_tuned.find(wgrad_key(s));
+  const WgradResolved r = wgrad_resolve(s, WgradGeom(s), it != g_wgrad_tuned.end() ? &it->second : nullptr, g_wgrad_force_dbg, g_conv_strict != 0,
+                                        workspace != nullptr, workspace_bytes);
+  if (r.status) return fail(r.status, "%s", r.message);
+  return wgrad_launch(s, x, dy, dw, dbias, workspace, workspace_bytes, r.choice, stream);
 }
 
 }  // extern "C"

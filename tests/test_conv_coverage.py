@@ -23,17 +23,6 @@ def src(name):
         return f.read()
 
 
-def function_body(text, signature):
-    i = text.index(signature)
-    j = text.index("{", i)
-    depth = 0
-    for k in range(j, len(text)):
-        depth += {"{": 1, "}": -1}.get(text[k], 0)
-        if depth == 0:
-            return text[j:k + 1]
-    raise AssertionError(signature)
-
-
 ROW = re.compile(r"^\s*CFG_ROW\(\s*(\d+),\s*([eA-Z0-9 |]+?),\s*(REQ_[A-Z_0-9]+),\s*(\d+),\s*(\d+),\s*([01]),\s*([01]),", re.M)
 MASKS = dict({"e" + n: (n,) for n in EPI_NAMES.values()}, eALL=tuple(EPI_NAMES.values()))
 
@@ -115,9 +104,8 @@ def test_table_shape_requirements():
 
 
 def wgrad_candidates():
-    body = function_body(src("wgrad_kernels.hip"), "int mi355det_conv_wgrad_autotune(")
-    m = re.search(r"const int cands\[\] = \{([^}]*)\}", body)
-    form = int(re.search(r"constexpr int WG_FORM8 = 1 << (\d+);", src("wgrad_kernels.hip")).group(1))
+    m = re.search(r"constexpr int WG_SPLITS\[\] = \{([^}]*)\}", src("wgrad_choice.h"))
+    form = int(re.search(r"constexpr int WG_FORM8 = 1 << (\d+);", src("wgrad_choice.h")).group(1))
     return tuple(int(v) for v in m.group(1).split(",")), 1 << form
 
 

@@ -526,6 +526,53 @@ def test_wgrad_phase_staggered_kernel_is_bit_identical(case):
     assert (got - wz.grad).abs().max().item() < 1e-2 * wz.grad.abs().max().item()
 
 
+@pytest.mark.parametrize("storage", ["bf16", "fp16"])
+def test_wgrad_autotune_contract(storage):
+    """mi355det_conv_wgrad_autotune on 2 x 40 x 40, 64 -> 256, 3x3 (3200 pixels: split counts 1..6, and 1, 2, 3 of the 256 x 256 form): it returns
+    a member of the candidate list (tests/golden/wgrad_choice.json, the list tests/test_wgrad_choice.py checks on the CPU), records it under one
+    key, keeps it, obeys a locked record, and the value it chose is one strict mode launches as it is."""
+    import ctypes as C
+    import json
+    import os
+    from object_detectors_amd import _lib, ops, tune
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wgrad_choice.json")) as f:
+        gold = json.load(f)
+    lines = [l for l in gold["input"] if l[0] in "SR"]
+    cands = gold["output"][lines.index("S 2 40 40 64 40 40 256 3 1 1 64 256")]["ws"][2]["cands"]
+    assert len(cands) > 6
+    Lb = _lib.storage_lib(storage)
+    shape = ops.conv_shape(2, 40, 40, 64, 256, 3, 1)
+    dt = torch.bfloat16 if storage == "bf16" else torch.float16
+    x = torch.zeros((2, 40, 40, 64), dtype=dt, device=dev())
+    dy = torch.zeros((2, 40, 40, 256), dtype=dt, device=dev())
+    dw = torch.zeros(256, 9 * 64, device=dev())
+    ws = torch.zeros(Lb.mi355det_conv_wgrad_workspace(C.byref(shape)), dtype=torch.uint8, device=dev())
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    vp = lambda t_: C.c_void_p(t_.data_ptr())      # noqa: E731
+
+    def autotune():
+        return Lb.mi355det_conv_wgrad_autotune(C.byref(shape), vp(x), vp(dy), vp(dw), vp(ws), ws.numel(), st)
+    try:
+        tune.clear()
+        v = autotune()
+        assert v in cands, (v, _lib.lib().mi355det_last_error().decode())
+        rec = [e for e in tune.to_entries(tune.export_bytes()) if e[0] == "wgrad"]
+        assert len(rec) == 1 and rec[0][2] == v and tune.wgrad_key_fields(rec[0][1]) == (3200, 256, 64, 3, 1, storage == "fp16"), rec
+        assert autotune() == v
+        locked = tune.from_entries([("wgrad", rec[0][1], 5)])
+        tune.import_bytes(locked, replace=True, lock=True)
+        assert autotune() == 5 and tune.export_bytes() == locked
+        Lb.mi355det_debug_set(9, 1)
+        Lb.mi355det_debug_set(7, v)
+        e = Lb.mi355det_conv_wgrad(C.byref(shape), vp(x), vp(dy), vp(dw), None, vp(ws), ws.numel(), st)
+        torch.cuda.synchronize()
+        assert e == 0, _lib.lib().mi355det_last_error().decode()
+    finally:
+        Lb.mi355det_debug_set(9, 0)
+        Lb.mi355det_debug_set(7, 0)
+        tune.clear()
+
+
 @pytest.mark.parametrize("case", [(2, 8, 128, 32, 64, 32, 64, False), (1, 6, 64, 32, 64, 40, 64, True), (2, 4, 64, 64, 64, 64, 64, True),
                                   (1, 10, 256, 64, 64, 64, 72, False), (3, 4, 128, 32, 64, 32, 80, True), (2, 4, 64, 64, 128, 64, 128, True)])
 def test_stride2_dgrad_single_launch_matches_class_launches(case):
