@@ -2,6 +2,7 @@
 // pairwise box_iou, fused IoU+Matcher, BoxCoder, anchor grid, sigmoid focal loss.
 // Wavefront-reduction / bit-mask kernels, HBM/latency-bound; -ffp-contract=off for bit-exact
 // threshold decisions against the reference's unfused float32 arithmetic.
+#include "bitonic_sort.h"
 #include "common.h"
 
 using namespace mi355;
@@ -167,22 +168,7 @@ __global__ __launch_bounds__(SORT_THREADS) void nms_sort_kernel(const float* __r
       __syncthreads();
     }
   } else {
-  for (int k = 2; k <= npad; k <<= 1) {
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        for (int i = threadIdx.x; i < npad; i += SORT_THREADS) {
-          const int ixj = i ^ j;
-          if (ixj > i) {
-            const unsigned long long a = keys[i], c = keys[ixj];
-            const bool desc = (i & k) == 0;   // descending overall
-            if (desc ? a < c : a > c) {
-              keys[i] = c;
-              keys[ixj] = a;
-            }
-          }
-        }
-        __syncthreads();
-      }
-    }
+    bitonic_sort_desc<SORT_THREADS>(keys, npad);
   }
   if (CHUNK) {
     const unsigned* rk = (const unsigned*)keys;

@@ -1,10 +1,6 @@
 // Mask branch of Mask R-CNN (tvision/mask_rcnn.py:21-300, tvision/roi_heads.py:99-183,403-537,844-887, the masks parts of
 // tvision/transform.py:26-62,228-247).  bf16 storage, fp32 arithmetic; the R-CNN path is bf16-only, so there are no fp16 twins.
 //
-//   mask_roi_pool        MultiScaleRoIAlign(['0'..'3'], 14, 2) into the conv layout: bf16 NHWC [R, 14, 14, C] with a pixel pitch (the input
-//                        of mask_fcn1).  The forward repeats the arithmetic of roi_align_nhwc_kernel (roi_kernels.hip) operation for operation
-//                        and rounds once: out == bf16(mi355det_roi_align_nhwc).  The backward takes the bf16 NHWC gradient of mask_fcn1's
-//                        data gradient and scatters it with the same fp32 atomics as the box branch.
 //   mask_targets         project_masks_on_boxes: roi_align(gt_masks[:, None].float(), [matched_idx, box], (M, M), 1.0) with torchvision's
 //                        defaults sampling_ratio = -1 (adaptive) and aligned = False, on the uint8 masks of every image in one launch.
 //   mask_loss            mask_fcn_logits (1x1, 256 -> K) restricted to the label channel + binary_cross_entropy_with_logits(mean), fused,
@@ -12,105 +8,27 @@
 //   mask_resize_nearest  F.interpolate(mask[:, None].float(), ..., mode='nearest')[:, 0].byte() with torch's source-index rule.
 //   paste_masks          paste_masks_in_image (expand_masks, expand_boxes, per-box bilinear resize, clipped paste), each output pixel once.
 //
+// The branch's pooling, MultiScaleRoIAlign(['0'..'3'], 14, 2) into the conv layout (mi355det_mask_roi_pool), is the per-sample channels-last
+// kernel of roi_kernels.hip with a bf16 NHWC store.
+//
 // The ConvTranspose2d(256, 256, 2, stride=2) of the mask predictor has no kernel here: with kernel == stride its output pixel (2i+di, 2j+dj)
 // depends on input pixel (i, j) only, so it IS the 1x1 convolution 256 -> 4*256 of the existing MFMA kernels (conv_fwd_ex / conv_dgrad_mask /
 // conv_wgrad) with output channel q*256 + co, q = 2*di + dj.  Its output stays in that sub-pixel order [R, 14, 14, 4, 256]; mask_loss and
 // mask_probs do the depth-to-space in their indexing (mask branch).
 //
-// Compiled with -ffp-contract=off (build.py): the pooling forward must round exactly like roi_align_nhwc_kernel, and the targets, the nearest
-// index and the paste follow torch's CPU float32 operation order.
+// Compiled with -ffp-contract=off (build.py): the targets (on the RoIAlign rules of roi_sample.h), the nearest index and the paste follow
+// torch's CPU float32 operation order.
 #include "common.h"
+#include "roi_sample.h"
 
 using namespace mi355;
 
 namespace {
 
-struct MaskLevels {
-  const bf16_t* feat[4];
-  float* grad[4];
-  int h[4], w[4], ld[4];
-  float scale[4];
-};
-
 struct MaskImages {
   const uint8_t* masks[MI355DET_MASK_MAX_IMAGES];
   int h[MI355DET_MASK_MAX_IMAGES], w[MI355DET_MASK_MAX_IMAGES];
 };
-
-__device__ __forceinline__ int mask_map_level(const float4 r, int k_min, int k_max) {
-  const float s = sqrtf((r.z - r.x) * (r.w - r.y));
-  int k = (int)floorf(4.0f + log2f(s / 224.0f) + 1e-6f);
-  k = min(max(k, k_min), k_max);
-  return k - k_min;
-}
-
-// One thread per (RoI, bin, channel), channels innermost: coalesced bf16 reads / writes (forward) and contiguous atomics (backward).
-template <bool BWD>
-__global__ __launch_bounds__(256) void mask_roi_pool_kernel(MaskLevels L, int num_levels, const float* __restrict__ rois, int K, int C, int ph,
-                                                            int pw, int sampling, int k_min, int k_max, bf16_t* __restrict__ out, int out_ld,
-                                                            const bf16_t* __restrict__ gout, int gout_ld) {
-  const long long total = (long long)K * ph * pw * C;
-  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    const int c = (int)(i % C);
-    const long long pix = i / C;                 // (k * ph + py) * pw + px
-    const int px = (int)(pix % pw);
-    const long long t = pix / pw;
-    const int py = (int)(t % ph), k = (int)(t / ph);
-    const float* r = rois + 5 * (size_t)k;
-    const int b = (int)r[0];
-    const float4 box = make_float4(r[1], r[2], r[3], r[4]);
-    int lv = num_levels > 1 ? mask_map_level(box, k_min, k_max) : 0;
-    int H = L.h[0], W = L.w[0], ld = L.ld[0];
-    float sc = L.scale[0];
-    const bf16_t* f = L.feat[0];
-    float* gf = L.grad[0];
-#pragma unroll
-    for (int q = 1; q < 4; ++q)
-      if (lv == q) {
-        H = L.h[q]; W = L.w[q]; ld = L.ld[q]; sc = L.scale[q]; f = L.feat[q]; gf = L.grad[q];
-      }
-    // aligned = False (MultiScaleRoIAlign): offset 0, RoI sides clamped to >= 1
-    const float x1 = box.x * sc, y1 = box.y * sc, x2 = box.z * sc, y2 = box.w * sc;
-    const float rw = fmaxf(x2 - x1, 1.0f), rh = fmaxf(y2 - y1, 1.0f);
-    const float bh = rh / (float)ph, bw = rw / (float)pw;
-    const int gh = sampling > 0 ? sampling : (int)ceilf(rh / (float)ph), gw = sampling > 0 ? sampling : (int)ceilf(rw / (float)pw);
-    const float cnt = fmaxf((float)(gh * gw), 1.0f);
-    const size_t img = (size_t)b * H * W;
-    float acc = 0.f;
-    const float g = BWD ? bf2f(gout[pix * gout_ld + c]) / cnt : 0.f;
-    for (int iy = 0; iy < gh; ++iy) {
-      float y = y1 + py * bh + ((float)iy + 0.5f) * bh / (float)gh;
-      for (int ix = 0; ix < gw; ++ix) {
-        float x = x1 + px * bw + ((float)ix + 0.5f) * bw / (float)gw;
-        float yy = y;
-        if (yy < -1.0f || yy > (float)H || x < -1.0f || x > (float)W) continue;
-        if (yy <= 0.f) yy = 0.f;
-        if (x <= 0.f) x = 0.f;
-        int yl = (int)yy, xl = (int)x, yh, xh;
-        if (yl >= H - 1) {
-          yh = yl = H - 1;
-          yy = (float)yl;
-        } else yh = yl + 1;
-        if (xl >= W - 1) {
-          xh = xl = W - 1;
-          x = (float)xl;
-        } else xh = xl + 1;
-        const float ly = yy - yl, lx = x - xl, hy = 1.f - ly, hx = 1.f - lx;
-        const size_t p00 = (img + (size_t)yl * W + xl), p01 = (img + (size_t)yl * W + xh), p10 = (img + (size_t)yh * W + xl),
-                     p11 = (img + (size_t)yh * W + xh);
-        if (!BWD) {
-          acc += hy * hx * bf2f(f[p00 * ld + c]) + hy * lx * bf2f(f[p01 * ld + c]) + ly * hx * bf2f(f[p10 * ld + c]) + ly * lx * bf2f(f[p11 * ld + c]);
-        } else {
-          atomicAdd(gf + p00 * C + c, g * hy * hx);
-          atomicAdd(gf + p01 * C + c, g * hy * lx);
-          atomicAdd(gf + p10 * C + c, g * ly * hx);
-          atomicAdd(gf + p11 * C + c, g * ly * lx);
-        }
-      }
-    }
-    if (!BWD) out[pix * out_ld + c] = f2bf(acc / cnt);
-  }
-}
 
 // torchvision roi_align (CPU kernel order) on one uint8 mask plane per RoI: spatial_scale 1, aligned = False, adaptive sampling.
 __global__ __launch_bounds__(256) void mask_targets_kernel(MaskImages I, int n_images, const float* __restrict__ rois,
@@ -128,35 +46,20 @@ __global__ __launch_bounds__(256) void mask_targets_kernel(MaskImages I, int n_i
     }
     const int H = I.h[b], W = I.w[b];
     const uint8_t* m = I.masks[b] + (size_t)gt_index[k] * H * W;
-    const float x1 = r[1], y1 = r[2], x2 = r[3], y2 = r[4];
-    const float rw = fmaxf(x2 - x1, 1.0f), rh = fmaxf(y2 - y1, 1.0f);
-    const float bh = rh / (float)M, bw = rw / (float)M;
-    const int gh = (int)ceilf(rh / (float)M), gw = (int)ceilf(rw / (float)M);
-    const float cnt = fmaxf((float)(gh * gw), 1.0f);
+    const RoiBins B = roi_bins(make_float4(r[1], r[2], r[3], r[4]), 1.0f, false, M, M, 0);
     float acc = 0.f;
-    for (int iy = 0; iy < gh; ++iy) {
-      float y = y1 + py * bh + ((float)iy + 0.5f) * bh / (float)gh;
-      for (int ix = 0; ix < gw; ++ix) {
-        float x = x1 + px * bw + ((float)ix + 0.5f) * bw / (float)gw;
-        if (y < -1.0f || y > (float)H || x < -1.0f || x > (float)W) continue;
-        float yy = y <= 0.f ? 0.f : y;
-        if (x <= 0.f) x = 0.f;
-        int yl = (int)yy, xl = (int)x, yh, xh;
-        if (yl >= H - 1) {
-          yh = yl = H - 1;
-          yy = (float)yl;
-        } else yh = yl + 1;
-        if (xl >= W - 1) {
-          xh = xl = W - 1;
-          x = (float)xl;
-        } else xh = xl + 1;
-        const float ly = yy - yl, lx = x - xl, hy = 1.f - ly, hx = 1.f - lx;
-        const float w1 = hy * hx, w2 = hy * lx, w3 = ly * hx, w4 = ly * lx;
-        acc += w1 * (float)m[(size_t)yl * W + xl] + w2 * (float)m[(size_t)yl * W + xh] + w3 * (float)m[(size_t)yh * W + xl] +
-               w4 * (float)m[(size_t)yh * W + xh];
+    for (int iy = 0; iy < B.gh; ++iy) {
+      const float y = bin_sample(B.y1, py, B.bh, iy, B.gh);
+      for (int ix = 0; ix < B.gw; ++ix) {
+        const float x = bin_sample(B.x1, px, B.bw, ix, B.gw);
+        RoiCorners q;
+        if (!roi_corners(y, x, H, W, q)) continue;
+        const float w1 = q.hy * q.hx, w2 = q.hy * q.lx, w3 = q.ly * q.hx, w4 = q.ly * q.lx;
+        acc += w1 * (float)m[(size_t)q.yl * W + q.xl] + w2 * (float)m[(size_t)q.yl * W + q.xh] + w3 * (float)m[(size_t)q.yh * W + q.xl] +
+               w4 * (float)m[(size_t)q.yh * W + q.xh];
       }
     }
-    out[i] = acc / cnt;
+    out[i] = acc / B.cnt;
   }
 }
 
@@ -340,36 +243,6 @@ inline int grid_for(long long total) { return (int)min((long long)256 * 64, max(
 }  // namespace
 
 extern "C" {
-
-int mi355det_mask_roi_pool(const void* const* feats, const int32_t* hs, const int32_t* ws, const int32_t* lds, const float* scales,
-                           int32_t num_levels, const float* rois, int32_t num_rois, int32_t channels, int32_t pooled_h, int32_t pooled_w,
-                           int32_t sampling_ratio, int32_t k_min, int32_t k_max, void* out, int32_t out_ld, const void* grad_out,
-                           int32_t grad_ld, float* const* grad_feats, void* stream) {
-  if (num_levels < 1 || num_levels > 4 || num_rois < 0 || channels <= 0 || pooled_h <= 0 || pooled_w <= 0 || !feats || !hs || !ws || !scales)
-    return fail(MI355DET_EINVAL, "%s: bad arguments", "mask_roi_pool");
-  const bool bwd = grad_out != nullptr;
-  if (bwd != (grad_feats != nullptr) || (!bwd && !out)) return fail(MI355DET_EINVAL, "%s: give out, or grad_out with grad_feats", "mask_roi_pool");
-  if ((!bwd && out_ld < channels) || (bwd && grad_ld < channels)) return fail(MI355DET_EINVAL, "%s: pitch below the channel count", "mask_roi_pool");
-  if (num_rois == 0) return MI355DET_OK;
-  MaskLevels L{};
-  for (int q = 0; q < num_levels; ++q) {
-    L.feat[q] = (const bf16_t*)feats[q];
-    L.grad[q] = bwd ? grad_feats[q] : nullptr;
-    L.h[q] = hs[q];
-    L.w[q] = ws[q];
-    L.ld[q] = lds ? lds[q] : channels;
-    L.scale[q] = scales[q];
-  }
-  const long long total = (long long)num_rois * channels * pooled_h * pooled_w;
-  const int blocks = (int)min((long long)256 * 32, (total + 255) / 256);
-  if (bwd)
-    hipLaunchKernelGGL(mask_roi_pool_kernel<true>, dim3(blocks), dim3(256), 0, S(stream), L, num_levels, rois, num_rois, channels, pooled_h,
-                       pooled_w, sampling_ratio, k_min, k_max, nullptr, 0, (const bf16_t*)grad_out, grad_ld);
-  else
-    hipLaunchKernelGGL(mask_roi_pool_kernel<false>, dim3(blocks), dim3(256), 0, S(stream), L, num_levels, rois, num_rois, channels, pooled_h,
-                       pooled_w, sampling_ratio, k_min, k_max, (bf16_t*)out, out_ld, nullptr, 0);
-  return check_launch("mask_roi_pool");
-}
 
 int mi355det_mask_targets(const mi355det_mask_images* images, const float* rois, const int64_t* gt_index, int32_t num_rois, int32_t m,
                           float* out, void* stream) {

@@ -1,140 +1,83 @@
 // RoIAlign / MultiScaleRoIAlign (torchvision.ops.roi_align semantics, call sites tvision/frcnn.py:208-211,
-// tvision/roi_heads.py:818) and per-row top-k selection (tvision/rpn.py:215-228, retinanet.py:437-445).
-// HBM/latency-bound gather kernels; -ffp-contract=off like the other box kernels.
+// tvision/roi_heads.py:818,844-887) and per-row top-k selection (tvision/rpn.py:215-228, retinanet.py:437-445).
+// HBM/latency-bound gather kernels; -ffp-contract=off like the other box kernels.  The RoIAlign rules live in roi_sample.h.
 #include <stdlib.h>
 
+#include "bitonic_sort.h"
 #include "common.h"
+#include "roi_sample.h"
 
 using namespace mi355;
 
 namespace {
 
-struct Levels {
-  const float* feat[4];
-  int h[4], w[4];
-  float scale[4];
-  int num;
-};
-
-__device__ __forceinline__ float bilinear(const float* __restrict__ f, int H, int W, float y, float x) {
-  if (y < -1.0f || y > (float)H || x < -1.0f || x > (float)W) return 0.f;
-  if (y <= 0.f) y = 0.f;
-  if (x <= 0.f) x = 0.f;
-  int yl = (int)y, xl = (int)x, yh, xh;
-  if (yl >= H - 1) {
-    yh = yl = H - 1;
-    y = (float)yl;
-  } else yh = yl + 1;
-  if (xl >= W - 1) {
-    xh = xl = W - 1;
-    x = (float)xl;
-  } else xh = xl + 1;
-  const float ly = y - yl, lx = x - xl, hy = 1.f - ly, hx = 1.f - lx;
-  return hy * hx * f[yl * W + xl] + hy * lx * f[yl * W + xh] + ly * hx * f[yh * W + xl] + ly * lx * f[yh * W + xh];
-}
-
-__device__ __forceinline__ void bilinear_grad(float* __restrict__ g, int H, int W, float y, float x, float v) {
-  if (y < -1.0f || y > (float)H || x < -1.0f || x > (float)W) return;
-  if (y <= 0.f) y = 0.f;
-  if (x <= 0.f) x = 0.f;
-  int yl = (int)y, xl = (int)x, yh, xh;
-  if (yl >= H - 1) {
-    yh = yl = H - 1;
-    y = (float)yl;
-  } else yh = yl + 1;
-  if (xl >= W - 1) {
-    xh = xl = W - 1;
-    x = (float)xl;
-  } else xh = xl + 1;
-  const float ly = y - yl, lx = x - xl, hy = 1.f - ly, hx = 1.f - lx;
-  atomicAdd(g + yl * W + xl, v * hy * hx);
-  atomicAdd(g + yl * W + xh, v * hy * lx);
-  atomicAdd(g + yh * W + xl, v * ly * hx);
-  atomicAdd(g + yh * W + xh, v * ly * lx);
-}
-
-// LevelMapper of MultiScaleRoIAlign: k = floor(4 + log2(sqrt(area)/224) + 1e-6) clamped to the pyramid
-__device__ __forceinline__ int map_level(const float4 r, int k_min, int k_max) {
-  const float s = sqrtf((r.z - r.x) * (r.w - r.y));
-  int k = (int)floorf(4.0f + log2f(s / 224.0f) + 1e-6f);
-  k = min(max(k, k_min), k_max);
-  return k - k_min;
-}
-
 // rois [K,5] = (batch, x1,y1,x2,y2); out [K,C,ph,pw].  MULTI: level chosen per RoI, else level 0.
 template <bool MULTI, bool BWD>
-__global__ __launch_bounds__(256) void roi_align_kernel(Levels L, const float* __restrict__ rois, int K, int C, int ph, int pw, int sampling,
-                                                        int aligned, int k_min, int k_max, float* __restrict__ out, const float* __restrict__ gout,
-                                                        float* __restrict__ gfeat0, float* __restrict__ gfeat1, float* __restrict__ gfeat2,
-                                                        float* __restrict__ gfeat3) {
+__global__ __launch_bounds__(256) void roi_align_kernel(RoiLevels<float> L, const float* __restrict__ rois, int K, int C, int ph, int pw,
+                                                        int sampling, int aligned, int k_min, int k_max, float* __restrict__ out,
+                                                        const float* __restrict__ gout) {
   const long long total = (long long)K * C * ph * pw;
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int px = (int)(i % pw), py = (int)((i / pw) % ph), c = (int)((i / ((long long)pw * ph)) % C), k = (int)(i / ((long long)pw * ph * C));
     const float* r = rois + 5 * (size_t)k;
     const int b = (int)r[0];
     const float4 box = make_float4(r[1], r[2], r[3], r[4]);
-    int lv = 0;
-    if (MULTI) lv = map_level(box, k_min, k_max);
-    int H = L.h[0], W = L.w[0];
-    float sc = L.scale[0];
-    const float* f = L.feat[0];
-    float* gf = gfeat0;
-#pragma unroll
-    for (int q = 1; q < 4; ++q)
-      if (lv == q) {
-        H = L.h[q]; W = L.w[q]; sc = L.scale[q]; f = L.feat[q];
-        gf = q == 1 ? gfeat1 : (q == 2 ? gfeat2 : gfeat3);
-      }
-    const float off = aligned ? 0.5f : 0.0f;
-    const float x1 = box.x * sc - off, y1 = box.y * sc - off, x2 = box.z * sc - off, y2 = box.w * sc - off;
-    float rw = x2 - x1, rh = y2 - y1;
-    if (!aligned) {
-      rw = fmaxf(rw, 1.0f);
-      rh = fmaxf(rh, 1.0f);
-    }
-    const float bh = rh / (float)ph, bw = rw / (float)pw;
-    const int gh = sampling > 0 ? sampling : (int)ceilf(rh / (float)ph), gw = sampling > 0 ? sampling : (int)ceilf(rw / (float)pw);
-    const float cnt = fmaxf((float)(gh * gw), 1.0f);
+    const auto l = L.pick(MULTI ? map_level(box, k_min, k_max) : 0);
+    const int H = l.h, W = l.w;
+    const RoiBins B = roi_bins(box, l.scale, aligned, ph, pw, sampling);
     const size_t plane = ((size_t)b * C + c) * (size_t)H * W;
-    if (!BWD) {
-      float acc = 0.f;
-      for (int iy = 0; iy < gh; ++iy) {
-        const float y = y1 + py * bh + ((float)iy + 0.5f) * bh / (float)gh;
-        for (int ix = 0; ix < gw; ++ix) {
-          const float x = x1 + px * bw + ((float)ix + 0.5f) * bw / (float)gw;
-          acc += bilinear(f + plane, H, W, y, x);
-        }
-      }
-      out[i] = acc / cnt;
-    } else {
-      const float g = gout[i] / cnt;
-      for (int iy = 0; iy < gh; ++iy) {
-        const float y = y1 + py * bh + ((float)iy + 0.5f) * bh / (float)gh;
-        for (int ix = 0; ix < gw; ++ix) {
-          const float x = x1 + px * bw + ((float)ix + 0.5f) * bw / (float)gw;
-          bilinear_grad(gf + plane, H, W, y, x, g);
+    const float* f = BWD ? nullptr : l.feat + plane;
+    float* gf = BWD ? l.grad + plane : nullptr;
+    float acc = 0.f;
+    const float g = BWD ? gout[i] / B.cnt : 0.f;
+    for (int iy = 0; iy < B.gh; ++iy) {
+      const float y = bin_sample(B.y1, py, B.bh, iy, B.gh);
+      for (int ix = 0; ix < B.gw; ++ix) {
+        const float x = bin_sample(B.x1, px, B.bw, ix, B.gw);
+        RoiCorners q;
+        if (!roi_corners(y, x, H, W, q)) continue;
+        if (!BWD) {
+          acc += q.hy * q.hx * f[q.yl * W + q.xl] + q.hy * q.lx * f[q.yl * W + q.xh] + q.ly * q.hx * f[q.yh * W + q.xl] +
+                 q.ly * q.lx * f[q.yh * W + q.xh];
+        } else {
+          atomicAdd(gf + q.yl * W + q.xl, g * q.hy * q.hx);
+          atomicAdd(gf + q.yl * W + q.xh, g * q.hy * q.lx);
+          atomicAdd(gf + q.yh * W + q.xl, g * q.ly * q.hx);
+          atomicAdd(gf + q.yh * W + q.xh, g * q.ly * q.lx);
         }
       }
     }
+    if (!BWD) out[i] = acc / B.cnt;
   }
 }
 
 // ---- channels-last form: bf16 NHWC features (the engines' native layout), lanes over channels ---------------------------
 // The NCHW kernel above spends its backward in scattered fp32 atomics (64 lanes -> 64 different rows: measured 5.3 ms for
 // 2048 RoIs x 256 channels).  With channels innermost a wave's atomics fall into one or two contiguous 256-byte runs (the
-// full-rate shape of the memory-side atomic unit) and the forward reads 128-byte runs; the pooled tensor keeps the
-// reference's [K, C, ph, pw] order (box_head.fc6 expects it), at the price of 4-byte strided accesses on that (small) side.
-struct LevelsCL {
-  const bf16_t* feat[4];
-  float* grad[4];
-  int h[4], w[4], ld[4];
-  float scale[4];
+// full-rate shape of the memory-side atomic unit) and the forward reads 128-byte runs.
+//
+// Where the pooled value of (RoI k, bin py px, channel c) and its gradient live:
+struct PooledF32 {          // fp32 [K, C, ph, pw], the reference's order (box_head.fc6 expects it): 4-byte strided accesses on that (small) side
+  float* out;
+  const float* gout;
+  int C, ph, pw;
+  __device__ __forceinline__ long long at(int k, int py, int px, int c) const { return (((long long)k * C + c) * ph + py) * pw + px; }
+  __device__ __forceinline__ float grad(int k, int py, int px, int c) const { return gout[at(k, py, px, c)]; }
+  __device__ __forceinline__ void store(int k, int py, int px, int c, float v) const { out[at(k, py, px, c)] = v; }
+};
+struct PooledBf16 {         // bf16 NHWC [K, ph, pw, ld]: the conv layout (mask_fcn1's input, its data gradient), rounded once
+  bf16_t* out;
+  const bf16_t* gout;
+  int ld, ph, pw;
+  __device__ __forceinline__ long long at(int k, int py, int px, int c) const { return (((long long)k * ph + py) * pw + px) * ld + c; }
+  __device__ __forceinline__ float grad(int k, int py, int px, int c) const { return bf2f(gout[at(k, py, px, c)]); }
+  __device__ __forceinline__ void store(int k, int py, int px, int c, float v) const { out[at(k, py, px, c)] = f2bf(v); }
 };
 
-template <bool BWD>
-__global__ __launch_bounds__(256) void roi_align_nhwc_kernel(LevelsCL L, int num_levels, const float* __restrict__ rois, int K, int C, int ph, int pw,
-                                                             int sampling, int aligned, int k_min, int k_max, float* __restrict__ out,
-                                                             const float* __restrict__ gout) {
+// One thread per (RoI, bin, channel), channels innermost: coalesced bf16 reads (forward) and contiguous atomics (backward).
+template <bool BWD, class IO>
+__global__ __launch_bounds__(256) void roi_align_nhwc_kernel(RoiLevels<bf16_t> L, int num_levels, const float* __restrict__ rois, int K, int C, int ph,
+                                                             int pw, int sampling, int aligned, int k_min, int k_max, IO io) {
   const long long total = (long long)K * ph * pw * C;
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int c = (int)(i % C);
@@ -145,61 +88,34 @@ __global__ __launch_bounds__(256) void roi_align_nhwc_kernel(LevelsCL L, int num
     const float* r = rois + 5 * (size_t)k;
     const int b = (int)r[0];
     const float4 box = make_float4(r[1], r[2], r[3], r[4]);
-    int lv = num_levels > 1 ? map_level(box, k_min, k_max) : 0;
-    int H = L.h[0], W = L.w[0], ld = L.ld[0];
-    float sc = L.scale[0];
-    const bf16_t* f = L.feat[0];
-    float* gf = L.grad[0];
-#pragma unroll
-    for (int q = 1; q < 4; ++q)
-      if (lv == q) {
-        H = L.h[q]; W = L.w[q]; ld = L.ld[q]; sc = L.scale[q]; f = L.feat[q]; gf = L.grad[q];
-      }
-    const float off = aligned ? 0.5f : 0.0f;
-    const float x1 = box.x * sc - off, y1 = box.y * sc - off, x2 = box.z * sc - off, y2 = box.w * sc - off;
-    float rw = x2 - x1, rh = y2 - y1;
-    if (!aligned) {
-      rw = fmaxf(rw, 1.0f);
-      rh = fmaxf(rh, 1.0f);
-    }
-    const float bh = rh / (float)ph, bw = rw / (float)pw;
-    const int gh = sampling > 0 ? sampling : (int)ceilf(rh / (float)ph), gw = sampling > 0 ? sampling : (int)ceilf(rw / (float)pw);
-    const float cnt = fmaxf((float)(gh * gw), 1.0f);
-    const long long oidx = (((long long)k * C + c) * ph + py) * pw + px;
+    const auto l = L.pick(num_levels > 1 ? map_level(box, k_min, k_max) : 0);
+    const int H = l.h, W = l.w, ld = l.ld;
+    const bf16_t* f = l.feat;
+    float* gf = l.grad;
+    const RoiBins B = roi_bins(box, l.scale, aligned, ph, pw, sampling);
     const size_t img = (size_t)b * H * W;
     float acc = 0.f;
-    const float g = BWD ? gout[oidx] / cnt : 0.f;
-    for (int iy = 0; iy < gh; ++iy) {
-      float y = y1 + py * bh + ((float)iy + 0.5f) * bh / (float)gh;
-      for (int ix = 0; ix < gw; ++ix) {
-        float x = x1 + px * bw + ((float)ix + 0.5f) * bw / (float)gw;
-        float yy = y;
-        if (yy < -1.0f || yy > (float)H || x < -1.0f || x > (float)W) continue;
-        if (yy <= 0.f) yy = 0.f;
-        if (x <= 0.f) x = 0.f;
-        int yl = (int)yy, xl = (int)x, yh, xh;
-        if (yl >= H - 1) {
-          yh = yl = H - 1;
-          yy = (float)yl;
-        } else yh = yl + 1;
-        if (xl >= W - 1) {
-          xh = xl = W - 1;
-          x = (float)xl;
-        } else xh = xl + 1;
-        const float ly = yy - yl, lx = x - xl, hy = 1.f - ly, hx = 1.f - lx;
-        const size_t p00 = (img + (size_t)yl * W + xl), p01 = (img + (size_t)yl * W + xh), p10 = (img + (size_t)yh * W + xl),
-                     p11 = (img + (size_t)yh * W + xh);
+    const float g = BWD ? io.grad(k, py, px, c) / B.cnt : 0.f;
+    for (int iy = 0; iy < B.gh; ++iy) {
+      const float y = bin_sample(B.y1, py, B.bh, iy, B.gh);
+      for (int ix = 0; ix < B.gw; ++ix) {
+        const float x = bin_sample(B.x1, px, B.bw, ix, B.gw);
+        RoiCorners q;
+        if (!roi_corners(y, x, H, W, q)) continue;
+        const size_t p00 = (img + (size_t)q.yl * W + q.xl), p01 = (img + (size_t)q.yl * W + q.xh), p10 = (img + (size_t)q.yh * W + q.xl),
+                     p11 = (img + (size_t)q.yh * W + q.xh);
         if (!BWD) {
-          acc += hy * hx * bf2f(f[p00 * ld + c]) + hy * lx * bf2f(f[p01 * ld + c]) + ly * hx * bf2f(f[p10 * ld + c]) + ly * lx * bf2f(f[p11 * ld + c]);
+          acc += q.hy * q.hx * bf2f(f[p00 * ld + c]) + q.hy * q.lx * bf2f(f[p01 * ld + c]) + q.ly * q.hx * bf2f(f[p10 * ld + c]) +
+                 q.ly * q.lx * bf2f(f[p11 * ld + c]);
         } else {
-          atomicAdd(gf + p00 * C + c, g * hy * hx);
-          atomicAdd(gf + p01 * C + c, g * hy * lx);
-          atomicAdd(gf + p10 * C + c, g * ly * hx);
-          atomicAdd(gf + p11 * C + c, g * ly * lx);
+          atomicAdd(gf + p00 * C + c, g * q.hy * q.hx);
+          atomicAdd(gf + p01 * C + c, g * q.hy * q.lx);
+          atomicAdd(gf + p10 * C + c, g * q.ly * q.hx);
+          atomicAdd(gf + p11 * C + c, g * q.ly * q.lx);
         }
       }
     }
-    if (!BWD) out[oidx] = acc / cnt;
+    if (!BWD) io.store(k, py, px, c, acc / B.cnt);
   }
 }
 
@@ -213,25 +129,9 @@ __global__ __launch_bounds__(256) void roi_align_nhwc_kernel(LevelsCL L, int num
 // touched rows x columns of the footprint (a 14-pixel RoI: ~225): 2048 RoIs x 256 channels went from 1.28 ms to the time below.
 #define RSEP_BINS 7
 #define RSEP_CAP 512           // footprint rows / columns held in LDS (= the largest feature map side this form accepts)
-struct RsepAxis {
-  int lo, n;                   // first touched pixel and extent of the footprint along the axis
-};
-
-// weights of one axis: thread `bin` (< 7) walks the samples of its bin.  start / bin_size / grid as in roi_align_nhwc_kernel.
-__device__ __forceinline__ void rsep_sample(float s, int size, bool& ok, int& lo, int& hi, float& wl, float& wh) {
-  ok = !(s < -1.0f || s > (float)size);
-  if (s <= 0.f) s = 0.f;
-  lo = (int)s;
-  if (lo >= size - 1) {
-    hi = lo = size - 1;
-    s = (float)lo;
-  } else hi = lo + 1;
-  wh = s - lo;
-  wl = 1.f - wh;
-}
 
 template <bool BWD>
-__global__ __launch_bounds__(256) void roi_align_sep_kernel(LevelsCL L, int num_levels, const float* __restrict__ rois, int C, int sampling,
+__global__ __launch_bounds__(256) void roi_align_sep_kernel(RoiLevels<bf16_t> L, int num_levels, const float* __restrict__ rois, int C, int sampling,
                                                             int aligned, int k_min, int k_max, float* __restrict__ out,
                                                             const float* __restrict__ gout) {
   __shared__ float A[2][RSEP_CAP * RSEP_BINS];        // [axis][pixel - lo][bin]
@@ -241,44 +141,29 @@ __global__ __launch_bounds__(256) void roi_align_sep_kernel(LevelsCL L, int num_
   const float* r = rois + 5 * (size_t)k;
   const int b = (int)r[0];
   const float4 box = make_float4(r[1], r[2], r[3], r[4]);
-  const int lv = num_levels > 1 ? map_level(box, k_min, k_max) : 0;
-  int H = L.h[0], W = L.w[0], ld = L.ld[0];
-  float sc = L.scale[0];
-  const bf16_t* f = L.feat[0];
-  float* gf = L.grad[0];
-#pragma unroll
-  for (int q = 1; q < 4; ++q)
-    if (lv == q) {
-      H = L.h[q]; W = L.w[q]; ld = L.ld[q]; sc = L.scale[q]; f = L.feat[q]; gf = L.grad[q];
-    }
-  const float off = aligned ? 0.5f : 0.0f;
-  const float x1 = box.x * sc - off, y1 = box.y * sc - off, x2 = box.z * sc - off, y2 = box.w * sc - off;
-  float rw = x2 - x1, rh = y2 - y1;
-  if (!aligned) {
-    rw = fmaxf(rw, 1.0f);
-    rh = fmaxf(rh, 1.0f);
-  }
-  const float bh = rh / (float)RSEP_BINS, bw = rw / (float)RSEP_BINS;
-  const int gh = sampling > 0 ? sampling : (int)ceilf(rh / (float)RSEP_BINS), gw = sampling > 0 ? sampling : (int)ceilf(rw / (float)RSEP_BINS);
-  const float cnt = fmaxf((float)(gh * gw), 1.0f);
+  const auto l = L.pick(num_levels > 1 ? map_level(box, k_min, k_max) : 0);
+  const int H = l.h, W = l.w, ld = l.ld;
+  const bf16_t* f = l.feat;
+  float* gf = l.grad;
+  const RoiBins B = roi_bins(box, l.scale, aligned, RSEP_BINS, RSEP_BINS, sampling);
+  const float cnt = B.cnt;
   if (threadIdx.x < 2) {
     s_lo[threadIdx.x] = 0x7fffffff;
     s_hi[threadIdx.x] = -1;
   }
   __syncthreads();
-  // threads 0..6: the y axis, 64..70: the x axis (one wave each); pass 1 = extent of the footprint
+  // threads 0..6: the y axis, 64..70: the x axis (one wave each): thread `bin` walks the samples of its bin; pass 1 = extent of the footprint
   const int axis = threadIdx.x >> 6, bin = threadIdx.x & 63;
   const bool worker = axis < 2 && bin < RSEP_BINS;
-  const float a0 = axis ? x1 : y1, bs = axis ? bw : bh;
-  const int gn = axis ? gw : gh, size = axis ? W : H;
+  const float a0 = axis ? B.x1 : B.y1, bs = axis ? B.bw : B.bh;
+  const int gn = axis ? B.gw : B.gh, size = axis ? W : H;
   if (worker) {
     int mn = 0x7fffffff, mx = -1;
     for (int i = 0; i < gn; ++i) {
-      const float sp = a0 + bin * bs + ((float)i + 0.5f) * bs / (float)gn;
       bool ok;
       int lo, hi;
       float wl, wh;
-      rsep_sample(sp, size, ok, lo, hi, wl, wh);
+      axis_sample(bin_sample(a0, bin, bs, i, gn), size, ok, lo, hi, wl, wh);
       if (ok) mn = min(mn, lo), mx = max(mx, hi);
     }
     if (mx >= 0) {
@@ -300,11 +185,10 @@ __global__ __launch_bounds__(256) void roi_align_sep_kernel(LevelsCL L, int num_
   if (worker && !empty) {                                    // pass 2: column `bin` of the axis' weight matrix (no other thread writes it)
     const int base = axis ? xlo : ylo;
     for (int i = 0; i < gn; ++i) {
-      const float sp = a0 + bin * bs + ((float)i + 0.5f) * bs / (float)gn;
       bool ok;
       int lo, hi;
       float wl, wh;
-      rsep_sample(sp, size, ok, lo, hi, wl, wh);
+      axis_sample(bin_sample(a0, bin, bs, i, gn), size, ok, lo, hi, wl, wh);
       if (!ok) continue;
       A[axis][(lo - base) * RSEP_BINS + bin] += wl;
       A[axis][(hi - base) * RSEP_BINS + bin] += wh;
@@ -392,6 +276,34 @@ __global__ __launch_bounds__(256) void roi_align_sep_kernel(LevelsCL L, int num_
 // selected elements, bitonic sort of the <= 16384 survivors.  Elements <= min_value are never selected.
 #define TOPK_THREADS 1024
 #define TOPK_MAXK 16384
+// the three radix digits of the 32-bit ordered key, highest first: 11 + 11 + 10 bits
+__device__ constexpr int topk_shift(int level) { return level == 0 ? 21 : (level == 1 ? 10 : 0); }
+__device__ constexpr int topk_bits(int level) { return level < 2 ? 11 : 10; }
+
+// sort key of element `index` (< 2^32): descending order of the packed keys = descending value, ties lower index first; 0 = padding
+__device__ __forceinline__ unsigned long long topk_pack(unsigned key, unsigned index) { return ((unsigned long long)key << 32) | (0xFFFFFFFFu - index); }
+__device__ __forceinline__ long long topk_index(unsigned long long kv) { return (long long)(0xFFFFFFFFu - (unsigned)(kv & 0xFFFFFFFFull)); }
+__device__ __forceinline__ float topk_value(unsigned long long kv) { return ord2f((unsigned)(kv >> 32)); }
+
+// The tail of every form: keys[0, m) (LDS, written before the call) are padded with zeros to a power of two (>= 64) and sorted; the first
+// min(m, k) go to idx_row / val_row (val_row may be null), their number to *count_ptr.
+template <int THREADS>
+__device__ __forceinline__ void topk_sort_emit(unsigned long long* keys, int m, int k, long long* __restrict__ idx_row, float* __restrict__ val_row,
+                                               int* __restrict__ count_ptr) {
+  int npad = 64;
+  while (npad < m) npad <<= 1;
+  for (int i = m + threadIdx.x; i < npad; i += THREADS) keys[i] = 0;
+  __syncthreads();
+  bitonic_sort_desc<THREADS>(keys, npad);
+  const int take = min(m, k);
+  for (int i = threadIdx.x; i < take; i += THREADS) {
+    const unsigned long long kv = keys[i];
+    idx_row[i] = topk_index(kv);
+    if (val_row) val_row[i] = topk_value(kv);
+  }
+  if (threadIdx.x == 0) *count_ptr = take;
+}
+
 __device__ __forceinline__ void topk_select_digit(const unsigned* __restrict__ hist, int nb, unsigned need, unsigned* s_out /* [3]: digit, need, all */) {
   // one wave: highest bucket b with (count of keys in buckets > b) < need <= (count in buckets >= b)
   const int lane = threadIdx.x;
@@ -437,17 +349,15 @@ __device__ __forceinline__ void topk_row_ordered(const float* __restrict__ xr, l
   }
   __syncthreads();
   // --- radix select of the k-th largest key among keys > min_key
-  const int shifts[3] = {21, 10, 0};
-  const int bits[3] = {11, 11, 10};
   unsigned mask_hi = 0;
   for (int pass = 0; pass < 3; ++pass) {
-    const int nb = 1 << bits[pass];
+    const int nb = 1 << topk_bits(pass);
     for (int i = threadIdx.x; i < 2048; i += TOPK_THREADS) hist[i] = 0;
     __syncthreads();
     const unsigned prefix = s_prefix;
     for (long long i = threadIdx.x; i < n; i += TOPK_THREADS) {
       const unsigned key = f2ord(xr[i]);
-      if (key > min_key && (key & mask_hi) == prefix) atomicAdd(&hist[(key >> shifts[pass]) & (nb - 1)], 1u);
+      if (key > min_key && (key & mask_hi) == prefix) atomicAdd(&hist[(key >> topk_shift(pass)) & (nb - 1)], 1u);
     }
     __syncthreads();
     if (threadIdx.x < WAVE) topk_select_digit(hist, nb, s_need, s_digit);   // (a serial scan of the 2048 buckets by one thread cost 55 us per pass)
@@ -458,12 +368,12 @@ __device__ __forceinline__ void topk_row_ordered(const float* __restrict__ xr, l
         s_prefix = 0xFFFFFFFFu;   // marker
       } else {
         s_need = s_digit[1];
-        s_prefix = prefix | (s_digit[0] << shifts[pass]);
+        s_prefix = prefix | (s_digit[0] << topk_shift(pass));
       }
     }
     __syncthreads();
     if (s_prefix == 0xFFFFFFFFu) break;
-    mask_hi |= (unsigned)((1 << bits[pass]) - 1) << shifts[pass];
+    mask_hi |= (unsigned)((1 << topk_bits(pass)) - 1) << topk_shift(pass);
   }
   const bool all_valid = s_prefix == 0xFFFFFFFFu;
   const unsigned thr = all_valid ? min_key : s_prefix;      // select key > thr, plus the first s_need elements == thr
@@ -503,7 +413,7 @@ __device__ __forceinline__ void topk_row_ordered(const float* __restrict__ xr, l
     __syncthreads();
     int off = s_base;
     for (int w = 0; w < wid; ++w) off += wsum[w];
-    if (sel && off + spre < TOPK_MAXK) keys[off + spre] = ((unsigned long long)key << 32) | (0xFFFFFFFFu - (unsigned)i);
+    if (sel && off + spre < TOPK_MAXK) keys[off + spre] = topk_pack(key, (unsigned)i);
     __syncthreads();
     if (threadIdx.x == 0) {
       int t = 0;
@@ -512,31 +422,8 @@ __device__ __forceinline__ void topk_row_ordered(const float* __restrict__ xr, l
     }
     __syncthreads();
   }
-  const int m = min(s_base, TOPK_MAXK);
-  int npad = 64;
-  while (npad < m) npad <<= 1;
-  for (int i = m + threadIdx.x; i < npad; i += TOPK_THREADS) keys[i] = 0;
-  __syncthreads();
-  for (int kk = 2; kk <= npad; kk <<= 1)
-    for (int j = kk >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < npad; i += TOPK_THREADS) {
-        const int ixj = i ^ j;
-        if (ixj > i) {
-          const unsigned long long a = keys[i], c = keys[ixj];
-          if (((i & kk) == 0) ? a < c : a > c) {
-            keys[i] = c;
-            keys[ixj] = a;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  for (int i = threadIdx.x; i < m; i += TOPK_THREADS) {
-    const unsigned long long kv = keys[i];
-    idx_row[i] = (long long)(0xFFFFFFFFu - (unsigned)(kv & 0xFFFFFFFFull));
-    if (val_row) val_row[i] = ord2f((unsigned)(kv >> 32));
-  }
-  if (threadIdx.x == 0) *count_ptr = m;
+  // fewer than k keys above the threshold plus at most s_need ties were selected: never more than k
+  topk_sort_emit<TOPK_THREADS>(keys, min(s_base, TOPK_MAXK), k, idx_row, val_row, count_ptr);
 }
 
 __global__ __launch_bounds__(TOPK_THREADS) void topk_kernel(const float* __restrict__ x, long long n, long long row_stride, int k,
@@ -570,16 +457,14 @@ struct TopkState {           // per row, zeroed by the launch function
 
 // state after `levels` histogram levels: prefix bits, remaining need, all_valid
 __device__ __forceinline__ void topk_replay(const TopkState* st, int levels, unsigned k, unsigned* s_sel /* LDS [4] */) {
-  const int shifts[3] = {21, 10, 0};
-  const int bits[3] = {11, 11, 10};
   unsigned prefix = 0, need = k, all = 0, stop = 0;
   __shared__ unsigned s_tmp[3];
   for (int l = 0; l < levels && !all && !stop; ++l) {
-    if (threadIdx.x < WAVE) topk_select_digit(st->hist[l], 1 << bits[l], need, s_tmp);
+    if (threadIdx.x < WAVE) topk_select_digit(st->hist[l], 1 << topk_bits(l), need, s_tmp);
     __syncthreads();
     all = s_tmp[2];
     if (!all) {
-      prefix |= s_tmp[0] << shifts[l];
+      prefix |= s_tmp[0] << topk_shift(l);
       need = s_tmp[1];
       // Early stop: the keys above this bucket (k - need of them) plus the whole bucket fit the candidate buffer - the final sort picks the
       // k best of them exactly, so the remaining histogram levels (a full pass over the row each) are skipped.  With a score threshold
@@ -602,8 +487,6 @@ __global__ __launch_bounds__(1024) void topk_hist_kernel(const float* __restrict
                                                           TopkState* __restrict__ states) {
   __shared__ unsigned hist[2048];
   __shared__ unsigned s_sel[4];
-  const int shifts[3] = {21, 10, 0};
-  const int bits[3] = {11, 11, 10};
   const int row = blockIdx.y;
   TopkState* st = states + row;
   const float* xr = x + (size_t)row * row_stride;
@@ -613,13 +496,13 @@ __global__ __launch_bounds__(1024) void topk_hist_kernel(const float* __restrict
   if (s_sel[2] || s_sel[3]) return;                          // fewer than k valid keys in the row, or the candidates already fit: nothing to refine
   const unsigned prefix = s_sel[0];
   unsigned mask_hi = 0;
-  for (int l = 0; l < LEVEL; ++l) mask_hi |= (unsigned)((1 << bits[l]) - 1) << shifts[l];
+  for (int l = 0; l < LEVEL; ++l) mask_hi |= (unsigned)((1 << topk_bits(l)) - 1) << topk_shift(l);
   const long long per = (n + gridDim.x - 1) / gridDim.x;
   const long long lo = per * blockIdx.x, hi = min(n, lo + per);
-  const int nb = 1 << bits[LEVEL];
+  const int nb = 1 << topk_bits(LEVEL);
   auto count = [&](float v) {
     const unsigned key = f2ord(v);
-    if (key > min_key && (key & mask_hi) == prefix) atomicAdd(&hist[(key >> shifts[LEVEL]) & (nb - 1)], 1u);
+    if (key > min_key && (key & mask_hi) == prefix) atomicAdd(&hist[(key >> topk_shift(LEVEL)) & (nb - 1)], 1u);
   };
   // 16-byte loads over the aligned body of this workgroup's range (the scalar form read 108 M-element rows at 2.3 TB/s)
   if (lo < hi) {
@@ -681,7 +564,7 @@ __global__ __launch_bounds__(1024) void topk_collect_kernel(const float* __restr
       const bool tie = !all && !coarse && key == thr && key > min_key;
       if (gt || tie) {
         const unsigned p = atomicAdd(&s_cnt, 1u);
-        s_keys[p] = ((unsigned long long)key << 32) | (0xFFFFFFFFu - (unsigned)(lo + i));
+        s_keys[p] = topk_pack(key, (unsigned)(lo + i));
       }
     };
     if (r == 0) {
@@ -719,32 +602,9 @@ __global__ __launch_bounds__(TOPK_THREADS) void topk_finish_kernel(int k, TopkSt
   const TopkState* st = states + row;
   if (st->overflow) return;                                   // the one-workgroup launch behind this one redoes the row
   const int m = (int)min(st->n_gt, (unsigned)TOPK_MAXK);
-  int npad = 64;
-  while (npad < m) npad <<= 1;
   const unsigned long long* in = cand + (size_t)row * TOPK_MAXK;
-  for (int i = threadIdx.x; i < npad; i += TOPK_THREADS) keys[i] = i < m ? in[i] : 0ull;
-  __syncthreads();
-  for (int kk = 2; kk <= npad; kk <<= 1)
-    for (int j = kk >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < npad; i += TOPK_THREADS) {
-        const int ixj = i ^ j;
-        if (ixj > i) {
-          const unsigned long long a = keys[i], c = keys[ixj];
-          if (((i & kk) == 0) ? a < c : a > c) {
-            keys[i] = c;
-            keys[ixj] = a;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  const int take = min(m, k);
-  for (int i = threadIdx.x; i < take; i += TOPK_THREADS) {
-    const unsigned long long kv = keys[i];
-    idx_out[(size_t)row * k + i] = (long long)(0xFFFFFFFFu - (unsigned)(kv & 0xFFFFFFFFull));
-    if (val_out) val_out[(size_t)row * k + i] = ord2f((unsigned)(kv >> 32));
-  }
-  if (threadIdx.x == 0) count_out[row] = take;
+  for (int i = threadIdx.x; i < m; i += TOPK_THREADS) keys[i] = in[i];
+  topk_sort_emit<TOPK_THREADS>(keys, m, k, idx_out + (size_t)row * k, val_out ? val_out + (size_t)row * k : nullptr, count_out + row);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -787,18 +647,16 @@ __global__ __launch_bounds__(TOPK_THREADS) void topk_seg_kernel(const float* __r
   long long* idx_row = G.idx[sg] + (size_t)row * k;
   float* val_row = G.val[sg] ? G.val[sg] + (size_t)row * k : nullptr;
   const unsigned min_key = f2ord(min_value);
-  const int shifts[3] = {21, 10, 0};
-  const int bits[3] = {11, 11, 10};
   const unsigned target = (unsigned)min(TOPK_MAXK, max(4096, 2 * k));        // candidates worth sorting rather than another pass over the row
   unsigned prefix = 0, mask_hi = 0, need = (unsigned)k, cand = 0;
   bool all = false, done = false;
   for (int l = 0; l < 3 && !done; ++l) {
     for (int i = threadIdx.x; i < 2048; i += TOPK_THREADS) hist[i] = 0;
     __syncthreads();
-    const int nb = 1 << bits[l];
+    const int nb = 1 << topk_bits(l);
     topk_row_scan(xr, n, [&](int, float v) {
       const unsigned key = f2ord(v);
-      if (key > min_key && (key & mask_hi) == prefix) atomicAdd(&hist[(key >> shifts[l]) & (nb - 1)], 1u);
+      if (key > min_key && (key & mask_hi) == prefix) atomicAdd(&hist[(key >> topk_shift(l)) & (nb - 1)], 1u);
     });
     __syncthreads();
     if (threadIdx.x < WAVE) topk_select_digit(hist, nb, need, s_sel);
@@ -807,8 +665,8 @@ __global__ __launch_bounds__(TOPK_THREADS) void topk_seg_kernel(const float* __r
       all = done = true;
     } else {
       cand = ((unsigned)k - s_sel[1]) + hist[s_sel[0]];
-      prefix |= s_sel[0] << shifts[l];
-      mask_hi |= (unsigned)(nb - 1) << shifts[l];
+      prefix |= s_sel[0] << topk_shift(l);
+      mask_hi |= (unsigned)(nb - 1) << topk_shift(l);
       need = s_sel[1];
       done = cand <= target;
     }
@@ -824,36 +682,41 @@ __global__ __launch_bounds__(TOPK_THREADS) void topk_seg_kernel(const float* __r
     const unsigned key = f2ord(v);
     if (key > min_key && (all || (key & mask_hi) >= prefix)) {
       const unsigned p = atomicAdd(&s_cnt, 1u);
-      if (p < (unsigned)TOPK_MAXK) keys[p] = ((unsigned long long)key << 32) | (0xFFFFFFFFu - (unsigned)i);
+      if (p < (unsigned)TOPK_MAXK) keys[p] = topk_pack(key, (unsigned)i);
     }
   });
   __syncthreads();
-  const int m = (int)min(s_cnt, (unsigned)TOPK_MAXK);
-  int npad = 64;
-  while (npad < m) npad <<= 1;
-  for (int i = m + threadIdx.x; i < npad; i += TOPK_THREADS) keys[i] = 0;
-  __syncthreads();
-  for (int kk = 2; kk <= npad; kk <<= 1)
-    for (int j = kk >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < npad; i += TOPK_THREADS) {
-        const int ixj = i ^ j;
-        if (ixj > i) {
-          const unsigned long long a = keys[i], c = keys[ixj];
-          if (((i & kk) == 0) ? a < c : a > c) {
-            keys[i] = c;
-            keys[ixj] = a;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  const int take = min(m, k);
-  for (int i = threadIdx.x; i < take; i += TOPK_THREADS) {
-    const unsigned long long kv = keys[i];
-    idx_row[i] = (long long)(0xFFFFFFFFu - (unsigned)(kv & 0xFFFFFFFFull));
-    if (val_row) val_row[i] = ord2f((unsigned)(kv >> 32));
+  topk_sort_emit<TOPK_THREADS>(keys, (int)min(s_cnt, (unsigned)TOPK_MAXK), k, idx_row, val_row, G.cnt[sg] + row);
+}
+
+// the level table of an entry point (feats / grad_feats may be null; lds null = channels)
+template <class T>
+RoiLevels<T> make_levels(const void* const* feats, float* const* grad_feats, const int32_t* hs, const int32_t* ws, const int32_t* lds,
+                         const float* scales, int num_levels, int channels) {
+  RoiLevels<T> L{};
+  for (int q = 0; q < num_levels; ++q) {
+    L.feat[q] = feats ? (const T*)feats[q] : nullptr;
+    L.grad[q] = grad_feats ? grad_feats[q] : nullptr;
+    L.h[q] = hs[q];
+    L.w[q] = ws[q];
+    L.ld[q] = lds ? lds[q] : channels;
+    L.scale[q] = scales[q];
   }
-  if (threadIdx.x == 0) G.cnt[sg][row] = take;
+  return L;
+}
+
+// launch of the per-sample channels-last kernel (forward when io.gout is null)
+template <class IO>
+void launch_nhwc(const RoiLevels<bf16_t>& L, int num_levels, const float* rois, int num_rois, int channels, int ph, int pw, int sampling, int aligned,
+                 int k_min, int k_max, IO io, void* stream) {
+  const long long total = (long long)num_rois * channels * ph * pw;
+  const int blocks = (int)min((long long)256 * 32, (total + 255) / 256);
+  if (io.gout)
+    hipLaunchKernelGGL((roi_align_nhwc_kernel<true, IO>), dim3(blocks), dim3(256), 0, S(stream), L, num_levels, rois, num_rois, channels, ph, pw,
+                       sampling, aligned, k_min, k_max, io);
+  else
+    hipLaunchKernelGGL((roi_align_nhwc_kernel<false, IO>), dim3(blocks), dim3(256), 0, S(stream), L, num_levels, rois, num_rois, channels, ph, pw,
+                       sampling, aligned, k_min, k_max, io);
 }
 
 }  // namespace
@@ -866,22 +729,13 @@ int mi355det_roi_align(const float* const* feats, const int32_t* hs, const int32
   if (num_levels < 1 || num_levels > 4 || num_rois < 0 || channels <= 0 || pooled_h <= 0 || pooled_w <= 0)
     return fail(MI355DET_EINVAL, "%s: bad arguments", "roi_align");
   if (num_rois == 0) return 0;
-  Levels L{};
-  L.num = num_levels;
-  float* gf[4] = {nullptr, nullptr, nullptr, nullptr};
-  for (int q = 0; q < num_levels; ++q) {
-    L.feat[q] = feats ? feats[q] : nullptr;
-    L.h[q] = hs[q];
-    L.w[q] = ws[q];
-    L.scale[q] = scales[q];
-    if (grad_feats) gf[q] = grad_feats[q];
-  }
+  const RoiLevels<float> L = make_levels<float>((const void* const*)feats, grad_feats, hs, ws, nullptr, scales, num_levels, 0);
   const long long total = (long long)num_rois * channels * pooled_h * pooled_w;
   const int blocks = (int)min((long long)256 * 16, (total + 255) / 256);
   const bool multi = num_levels > 1, bwd = grad_out != nullptr;
   auto launch = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, S(stream), L, rois, num_rois, channels, pooled_h, pooled_w, sampling_ratio, aligned, k_min,
-                       k_max, out, grad_out, gf[0], gf[1], gf[2], gf[3]);
+                       k_max, out, grad_out);
   };
   if (multi && bwd) launch(roi_align_kernel<true, true>);
   else if (multi) launch(roi_align_kernel<true, false>);
@@ -897,15 +751,7 @@ int mi355det_roi_align_nhwc(const void* const* feats, const int32_t* hs, const i
     return fail(MI355DET_EINVAL, "%s: bad arguments", "roi_align_nhwc");
   if ((grad_out != nullptr) != (grad_feats != nullptr)) return fail(MI355DET_EINVAL, "%s: grad_out and grad_feats go together", "roi_align_nhwc");
   if (num_rois == 0) return 0;
-  LevelsCL L{};
-  for (int q = 0; q < num_levels; ++q) {
-    L.feat[q] = feats ? (const bf16_t*)feats[q] : nullptr;
-    L.grad[q] = grad_feats ? grad_feats[q] : nullptr;
-    L.h[q] = hs[q];
-    L.w[q] = ws[q];
-    L.ld[q] = lds ? lds[q] : channels;
-    L.scale[q] = scales[q];
-  }
+  const RoiLevels<bf16_t> L = make_levels<bf16_t>(feats, grad_feats, hs, ws, lds, scales, num_levels, channels);
   bool separable = pooled_h == RSEP_BINS && pooled_w == RSEP_BINS;
   for (int q = 0; q < num_levels; ++q) separable = separable && hs[q] <= RSEP_CAP && ws[q] <= RSEP_CAP;
   if (separable) {          // the 7x7 box head: one workgroup per RoI, footprint weights in LDS
@@ -917,15 +763,27 @@ int mi355det_roi_align_nhwc(const void* const* feats, const int32_t* hs, const i
                          k_min, k_max, out, grad_out);
     return check_launch("roi_align_nhwc");
   }
-  const long long total = (long long)num_rois * channels * pooled_h * pooled_w;
-  const int blocks = (int)min((long long)256 * 32, (total + 255) / 256);
-  if (grad_out)
-    hipLaunchKernelGGL(roi_align_nhwc_kernel<true>, dim3(blocks), dim3(256), 0, S(stream), L, num_levels, rois, num_rois, channels, pooled_h, pooled_w,
-                       sampling_ratio, aligned, k_min, k_max, out, grad_out);
-  else
-    hipLaunchKernelGGL(roi_align_nhwc_kernel<false>, dim3(blocks), dim3(256), 0, S(stream), L, num_levels, rois, num_rois, channels, pooled_h, pooled_w,
-                       sampling_ratio, aligned, k_min, k_max, out, grad_out);
+  launch_nhwc(L, num_levels, rois, num_rois, channels, pooled_h, pooled_w, sampling_ratio, aligned, k_min, k_max,
+              PooledF32{out, grad_out, channels, pooled_h, pooled_w}, stream);
   return check_launch("roi_align_nhwc");
+}
+
+// MultiScaleRoIAlign(['0'..'3'], 14, 2) of the mask branch into the conv layout: the per-sample kernel of mi355det_roi_align_nhwc with the
+// pooled tensor as bf16 NHWC [R, ph, pw, out_ld] (aligned = False), so out == bf16(mi355det_roi_align_nhwc) by construction.
+int mi355det_mask_roi_pool(const void* const* feats, const int32_t* hs, const int32_t* ws, const int32_t* lds, const float* scales,
+                           int32_t num_levels, const float* rois, int32_t num_rois, int32_t channels, int32_t pooled_h, int32_t pooled_w,
+                           int32_t sampling_ratio, int32_t k_min, int32_t k_max, void* out, int32_t out_ld, const void* grad_out,
+                           int32_t grad_ld, float* const* grad_feats, void* stream) {
+  if (num_levels < 1 || num_levels > 4 || num_rois < 0 || channels <= 0 || pooled_h <= 0 || pooled_w <= 0 || !feats || !hs || !ws || !scales)
+    return fail(MI355DET_EINVAL, "%s: bad arguments", "mask_roi_pool");
+  const bool bwd = grad_out != nullptr;
+  if (bwd != (grad_feats != nullptr) || (!bwd && !out)) return fail(MI355DET_EINVAL, "%s: give out, or grad_out with grad_feats", "mask_roi_pool");
+  if ((!bwd && out_ld < channels) || (bwd && grad_ld < channels)) return fail(MI355DET_EINVAL, "%s: pitch below the channel count", "mask_roi_pool");
+  if (num_rois == 0) return MI355DET_OK;
+  const RoiLevels<bf16_t> L = make_levels<bf16_t>(feats, grad_feats, hs, ws, lds, scales, num_levels, channels);
+  launch_nhwc(L, num_levels, rois, num_rois, channels, pooled_h, pooled_w, sampling_ratio, 0, k_min, k_max,
+              PooledBf16{bwd ? nullptr : (bf16_t*)out, (const bf16_t*)grad_out, bwd ? grad_ld : out_ld, pooled_h, pooled_w}, stream);
+  return check_launch("mask_roi_pool");
 }
 
 int mi355det_topk(const float* x, int32_t rows, int64_t n, int64_t row_stride, int32_t k, float min_value, int64_t* idx_out, float* val_out,

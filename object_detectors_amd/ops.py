@@ -678,21 +678,24 @@ def conv_dgrad_bn(shape, dy, w_dgrad, dx, z, scale_shift, slope, residual=None, 
     return sums
 
 
+def _level_tables(feats, scales):
+    """ctypes tables (pointers, heights, widths, pixel pitches, scales) of 1..4 bf16 NHWC pyramid levels."""
+    nl = len(feats)
+    for f in feats:
+        if f.dtype != torch.bfloat16 or f.dim() != 4 or f.stride(3) != 1:
+            raise ValueError("channels-last RoIAlign expects bf16 [n,h,w,C] tensors with contiguous channels")
+    return (nl, (C.c_void_p * nl)(*[f.data_ptr() for f in feats]), (C.c_int32 * nl)(*[f.shape[1] for f in feats]),
+            (C.c_int32 * nl)(*[f.shape[2] for f in feats]), (C.c_int32 * nl)(*[f.stride(2) for f in feats]),
+            (C.c_float * nl)(*[float(s) for s in scales]))
+
+
 def roi_align_nhwc(feats, rois, output_size, scales, sampling_ratio=2, aligned=False, k_min=2, k_max=5, grad_out=None):
     """Channels-last RoIAlign: feats = list of bf16 NHWC maps [n,h,w,C] (1..4 levels, pixel pitch = stride(2)); rois [K,5].
     Forward -> fp32 [K,C,ph,pw]; with grad_out -> list of fp32 NHWC feature gradients."""
-    for f in feats:
-        if f.dtype != torch.bfloat16 or f.dim() != 4 or f.stride(3) != 1:
-            raise ValueError("roi_align_nhwc expects bf16 [n,h,w,C] tensors with contiguous channels")
+    nl, P, hs, ws, lds, sc = _level_tables(feats, scales)
     rois = _f32c(rois)
-    nl = len(feats)
     ph, pw = (output_size, output_size) if isinstance(output_size, int) else output_size
     K, Cc = rois.shape[0], feats[0].shape[3]
-    P = (C.c_void_p * nl)(*[f.data_ptr() for f in feats])
-    hs = (C.c_int32 * nl)(*[f.shape[1] for f in feats])
-    ws = (C.c_int32 * nl)(*[f.shape[2] for f in feats])
-    lds = (C.c_int32 * nl)(*[f.stride(2) for f in feats])
-    sc = (C.c_float * nl)(*[float(s) for s in scales])
     if grad_out is None:
         out = torch.empty((K, Cc, ph, pw), device=rois.device, dtype=torch.float32)
         check(lib().mi355det_roi_align_nhwc(P, hs, ws, lds, sc, nl, ptr(rois), K, Cc, ph, pw, int(sampling_ratio), int(aligned), k_min, k_max,
@@ -732,17 +735,7 @@ def fastrcnn_loss(class_logits, box_regression, labels, regression_targets, clas
     return losses, gl, gb
 
 
-# ------------------------------------------------------------------------------------ Mask R-CNN mask branch (csrc/mask_kernels.hip)
-def _level_tables(feats, scales):
-    nl = len(feats)
-    for f in feats:
-        if f.dtype != torch.bfloat16 or f.dim() != 4 or f.stride(3) != 1:
-            raise ValueError("mask_roi_pool expects bf16 [n,h,w,C] tensors with contiguous channels")
-    return (nl, (C.c_void_p * nl)(*[f.data_ptr() for f in feats]), (C.c_int32 * nl)(*[f.shape[1] for f in feats]),
-            (C.c_int32 * nl)(*[f.shape[2] for f in feats]), (C.c_int32 * nl)(*[f.stride(2) for f in feats]),
-            (C.c_float * nl)(*[float(s) for s in scales]))
-
-
+# ------------------------------------------------------------------------------------ Mask R-CNN mask branch (csrc/mask_kernels.hip; the pooling: csrc/roi_kernels.hip)
 def mask_roi_pool(feats, rois, scales, k_min, k_max, output_size=14, sampling_ratio=2, out=None):
     """MultiScaleRoIAlign(['0'..'3'], 14, 2) into bf16 NHWC [K, 14, 14, C] (mask_fcn1's input); == bf16(roi_align_nhwc) bit for bit."""
     rois = _f32c(rois)

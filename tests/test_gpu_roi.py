@@ -237,3 +237,32 @@ def test_roi_align_separable_edge_cases(sampling, aligned):
     db = ops.roi_align_nhwc(feats_cl, rois, 7, scales, sampling, aligned, 2, 5, grad_out=go)
     for a, b_ in zip(da, db):
         torch.testing.assert_close(b_, a.permute(0, 2, 3, 1), rtol=1e-4, atol=1e-4)
+
+
+def test_roi_align_per_sample_forms_bit_equal():
+    """The per-sample forward of the NCHW kernel (fp32 planes) and of the channels-last kernel (bf16 NHWC) on the same bf16-rounded
+    features: both add the same four products per sample in the same order with contraction off, so the outputs are equal bit for bit.
+    Pooled sizes that do not take the separable form; a level with a pixel pitch above the channel count; boxes partly outside, wholly
+    beyond the map, of zero area, the whole image, 1.5 px wide and 2 px high."""
+    from object_detectors_amd import ops
+    n, c = 2, 40
+    sizes, scales = [(24, 20), (12, 10), (6, 5), (3, 3)], [0.25, 0.125, 0.0625, 0.03125]
+    feats = [T(detrand.uniform(100 + q, (n, c, h, w), -1, 1)).bfloat16().float() for q, (h, w) in enumerate(sizes)]
+    feats_cl = [f.permute(0, 2, 3, 1).contiguous().bfloat16() for f in feats]
+    wide = torch.zeros((n, sizes[1][0], sizes[1][1], 48), device=dev(), dtype=torch.bfloat16)
+    wide[..., :c] = feats_cl[1]
+    feats_cl[1] = wide[..., :c]                                   # pixel pitch 48, 40 channels
+    assert feats_cl[1].stride(2) == 48
+    fixed = np.array([[-5, -5, 3, 2], [120, 110, 160, 150], [30, 30, 30, 30], [0, 0, 80, 96], [40, 20, 41.5, 60], [0, 50, 80, 52]], np.float32)
+    tl = detrand.uniform(110, (18, 2), -20, 70)
+    wh = np.exp(detrand.uniform(111, (18, 2), np.log(4), np.log(600))).astype(np.float32)
+    boxes = np.concatenate([fixed, np.concatenate([tl, tl + wh], 1)]).astype(np.float32)
+    assert len(set(tv.map_levels(boxes[6:], 2, 5).tolist())) >= 3
+    rois = T(np.concatenate([(np.arange(24) % n).astype(np.float32)[:, None], boxes], 1))
+    for size in ((5, 3), (14, 14)):
+        for sampling, aligned in ((2, False), (0, False), (3, True)):
+            ya = ops.roi_align_multi(feats, rois, size, scales, sampling, aligned, 2, 5)
+            yb = ops.roi_align_nhwc(feats_cl, rois, size, scales, sampling, aligned, 2, 5)
+            assert ya.shape == yb.shape == (24, c) + size
+            assert float(ya.abs().max()) > 0
+            assert torch.equal(ya, yb), (size, sampling, aligned, float((ya - yb).abs().max()))
