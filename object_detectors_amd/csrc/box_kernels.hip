@@ -3,6 +3,7 @@
 // Wavefront-reduction / bit-mask kernels, HBM/latency-bound; -ffp-contract=off for bit-exact
 // threshold decisions against the reference's unfused float32 arithmetic.
 #include "bitonic_sort.h"
+#include "box_rules.h"
 #include "common.h"
 
 using namespace mi355;
@@ -582,19 +583,12 @@ __global__ void nms_keep_kernel(char* __restrict__ ws_base, NmsWs L, long long* 
   if (blockIdx.x == 0 && threadIdx.x == 0) keep_count[b] = kc;
 }
 
-// ---- torchvision box_iou ----------------------------------------------------------------------
-__device__ __forceinline__ float tv_iou(const float4 a, const float4 b) {
-  const float area_a = (a.z - a.x) * (a.w - a.y), area_b = (b.z - b.x) * (b.w - b.y);
-  const float w = fmaxf(fminf(a.z, b.z) - fmaxf(a.x, b.x), 0.0f), h = fmaxf(fminf(a.w, b.w) - fmaxf(a.y, b.y), 0.0f);
-  const float inter = w * h;
-  return inter / (area_a + area_b - inter);
-}
-
+// ---- torchvision box_iou (the rule: box_rules.h) ------------------------------------------------
 __global__ void box_iou_kernel(const float* __restrict__ b1, const float* __restrict__ b2, float* __restrict__ out, long long m, long long n) {
   const long long total = m * n;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const long long r = i / n, c = i - r * n;
-    out[i] = tv_iou(*(const float4*)(b1 + 4 * r), *(const float4*)(b2 + 4 * c));
+    out[i] = box_iou(*(const float4*)(b1 + 4 * r), *(const float4*)(b2 + 4 * c));
   }
 }
 
@@ -624,22 +618,14 @@ __global__ __launch_bounds__(MATCH_THREADS) void match_pass1_kernel(const float*
     float best = -INFINITY;
     int arg = 0;
     for (int g = 0; g < m; ++g) {
-      const float v = tv_iou(sg[g], a);
-      if (g == 0 || v > best) {   // first maximum, as torch.max(dim=0)
-        best = v;
-        arg = g;
-      }
+      const float v = box_iou(sg[g], a);
+      matcher_argmax(v, g, best, arg);
       unsigned o = live ? f2ord(v) : 0u;
 #pragma unroll
       for (int s = 32; s > 0; s >>= 1) o = max(o, (unsigned)__shfl_xor((int)o, s, WAVE));
       if ((threadIdx.x & 63) == 0) atomicMax(sbest + g, o);
     }
-    if (live) {
-      long long r = arg;
-      if (best < lo) r = -1;
-      else if (best < hi) r = -2;
-      matches[i] = r;
-    }
+    if (live) matches[i] = match_verdict(best, arg, lo, hi);
   }
   __syncthreads();
   for (int g = threadIdx.x; g < m; g += MATCH_THREADS) atomicMax(gt_best + g, sbest[g]);
@@ -662,24 +648,18 @@ __global__ __launch_bounds__(MATCH_THREADS) void match_pass2_kernel(const float*
   int arg = 0;
   bool rescue = false;
   for (int g = 0; g < m; ++g) {
-    const float v = tv_iou(sg[g], a);
-    if (g == 0 || v > best) {
-      best = v;
-      arg = g;
-    }
+    const float v = box_iou(sg[g], a);
+    matcher_argmax(v, g, best, arg);
     rescue = rescue || (v == ord2f(sb[g]));
   }
   if (rescue) matches[i] = arg;
 }
 
-// ---- BoxCoder (tvision/_utils.py:79-125, 190-223) -------------------------------------------------
+// ---- BoxCoder (the rules: box_rules.h) ------------------------------------------------------------
 __global__ void box_encode_kernel(const float* __restrict__ ref, const float* __restrict__ prop, float* __restrict__ out, long long n, float wx,
                                   float wy, float ww, float wh) {
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const float4 p = *(const float4*)(prop + 4 * i), r = *(const float4*)(ref + 4 * i);
-    const float ew = p.z - p.x, eh = p.w - p.y, ecx = p.x + 0.5f * ew, ecy = p.y + 0.5f * eh;
-    const float gw = r.z - r.x, gh = r.w - r.y, gcx = r.x + 0.5f * gw, gcy = r.y + 0.5f * gh;
-    *(float4*)(out + 4 * i) = make_float4(wx * (gcx - ecx) / ew, wy * (gcy - ecy) / eh, ww * logf(gw / ew), wh * logf(gh / eh));
+    *(float4*)(out + 4 * i) = box_encode(*(const float4*)(prop + 4 * i), *(const float4*)(ref + 4 * i), wx, wy, ww, wh);
   }
 }
 
@@ -688,11 +668,7 @@ __global__ void box_decode_kernel(const float* __restrict__ codes, const float* 
   const long long total = n * k;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const long long r = i / k;
-    const float4 b = *(const float4*)(boxes + 4 * r), c = *(const float4*)(codes + 4 * i);
-    const float w = b.z - b.x, h = b.w - b.y, cx = b.x + 0.5f * w, cy = b.y + 0.5f * h;
-    const float dx = c.x / wx, dy = c.y / wy, dw = fminf(c.z / ww, clip), dh = fminf(c.w / wh, clip);
-    const float pcx = dx * w + cx, pcy = dy * h + cy, pw = expf(dw) * w, ph = expf(dh) * h;
-    *(float4*)(out + 4 * i) = make_float4(pcx - 0.5f * pw, pcy - 0.5f * ph, pcx + 0.5f * pw, pcy + 0.5f * ph);
+    *(float4*)(out + 4 * i) = box_decode(*(const float4*)(codes + 4 * i), *(const float4*)(boxes + 4 * r), wx, wy, ww, wh, clip);
   }
 }
 
@@ -1026,10 +1002,8 @@ __global__ __launch_bounds__(256) void retina_reg_kernel(const float* __restrict
       const float4 a = *(const float4*)(anchors + r * 4);
       const float4 q = *(const float4*)(gt_boxes + (mi + gt_off[b]) * 4);
       const float4 pv = *(const float4*)(pred + i * 4);
-      const float ew = a.z - a.x, eh = a.w - a.y, ecx = a.x + 0.5f * ew, ecy = a.y + 0.5f * eh;
-      const float gw = q.z - q.x, gh = q.w - q.y, gcx = q.x + 0.5f * gw, gcy = q.y + 0.5f * gh;
-      const float t0 = wx * (gcx - ecx) / ew, t1 = wy * (gcy - ecy) / eh, t2 = ww * logf(gw / ew), t3 = wh * logf(gh / eh);
-      const float d0 = pv.x - t0, d1 = pv.y - t1, d2 = pv.z - t2, d3 = pv.w - t3;
+      const float4 t = box_encode(a, q, wx, wy, ww, wh);
+      const float d0 = pv.x - t.x, d1 = pv.y - t.y, d2 = pv.z - t.z, d3 = pv.w - t.w;
       acc += (fabsf(d0) + fabsf(d1) + fabsf(d2) + fabsf(d3)) * wimg;
       const float gs = gscale * wimg;
       g = make_float4(d0 > 0.f ? gs : (d0 < 0.f ? -gs : 0.f), d1 > 0.f ? gs : (d1 < 0.f ? -gs : 0.f), d2 > 0.f ? gs : (d2 < 0.f ? -gs : 0.f),

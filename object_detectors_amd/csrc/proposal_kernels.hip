@@ -3,6 +3,7 @@
 // per-level NMS of every image side by side, the first post_nms_top_n survivors gathered into dense outputs.  The torch form of the
 // same chain is ~60 small launches whose host time (1.7 ms at batch 4) sits between the network forward and the RoI branch with the
 // device idle; here the host issues ~14 launches from C.  Latency-bound integer / gather work: nothing to tile.
+#include "box_rules.h"
 #include "common.h"
 
 using namespace mi355;
@@ -11,66 +12,118 @@ namespace {
 
 constexpr int MAX_LEVELS = 8;
 
-struct ProposalLevels {
+// The three whole-batch tails (RPN proposals, RetinaNet detections, RoI-head detections) are one sequence: per-level top-k, ONE candidate
+// kernel over all levels and images (decode + clip of the selected entries, validity as a mask), batched NMS, gather.  What differs between
+// them is where a selected entry's anchor, code, score and label come from: the source types below.
+
+// The per-level top-k outputs.  Level l owns the columns [koff[l], koff[l + 1]) of the candidate axis [K]; the RoI head is the one-level case.
+struct TopkLevels {
   int nlev;
-  int start[MAX_LEVELS];        // first anchor of the level in the concatenated [A] axis
-  int k[MAX_LEVELS];            // min(pre_nms_top_n, anchors of the level)
-  int koff[MAX_LEVELS + 1];     // prefix sums of k: column range of the level in the candidate axis [K]
-  long long idx_off[MAX_LEVELS];   // byte offsets of the level's top-k outputs in the workspace: idx [N, k] int64 ...
-  long long val_off[MAX_LEVELS];   // ... and val [N, k] float
-  long long cnt_off[MAX_LEVELS];   // ... and the number of selected entries per image [N] int32 (< k only for rows with NaN / -inf logits)
+  int k[MAX_LEVELS];               // entries asked of the level
+  int koff[MAX_LEVELS + 1];        // prefix sums of k
+  int64_t* idx[MAX_LEVELS];        // [N, k] flat index inside the level's row
+  float* val[MAX_LEVELS];          // [N, k] its value
+  int* cnt[MAX_LEVELS];            // [N] selected entries of the image (< k: the row holds fewer finite logits / scores above the threshold)
 };
 
-// One thread per candidate (image, j).  Formulas in the order of ops.box_decode (BoxCoder.decode_single, tvision/_utils.py:196-232, weights 1)
-// and clip_boxes_to_image / remove_small_boxes (rpn.py:263-270); -ffp-contract=off keeps them bit-equal to the unfused route.
-__global__ __launch_bounds__(256) void rpn_select_kernel(const char* __restrict__ ws, ProposalLevels L, const float* __restrict__ deltas,
-                                                         const float* __restrict__ anchors, const float* __restrict__ lim, int n_images,
-                                                         long long A, float xform_clip, float min_size, float score_thresh,
-                                                         float* __restrict__ boxes, float* __restrict__ masked, float* __restrict__ scores,
-                                                         long long* __restrict__ lvl) {
+__device__ __forceinline__ int level_of(const TopkLevels& L, int j) {
+  int l = 0;
+#pragma unroll
+  for (int q = 1; q < MAX_LEVELS; ++q)
+    if (q < L.nlev && j >= L.koff[q]) l = q;
+  return l;
+}
+
+struct Candidate {
+  float4 box, code;      // anchor / proposal and its regression code
+  float4 weights;        // BoxCoder weights
+  float score;
+  long long label;       // NMS category
+};
+
+__device__ __forceinline__ float4 ld4(const float* p, long long row) { return *(const float4*)(p + 4 * row); }
+__device__ __forceinline__ float sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// RegionProposalNetwork.filter_proposals (rpn.py:215-280): anchor start[l] + idx of the concatenated [A] axis, NMS per level,
+// remove_small_boxes and the score threshold (rpn.py:263-270) as the mask
+struct RpnSource {
+  int start[MAX_LEVELS];      // first anchor of the level
+  const float *deltas, *anchors;
+  long long A;
+  float min_size, score_thresh;
+  __device__ __forceinline__ Candidate get(int img, int l, long long idx, float logit) const {
+    const long long a = (long long)start[l] + idx;
+    return {ld4(anchors, a), ld4(deltas, (long long)img * A + a), make_float4(1.0f, 1.0f, 1.0f, 1.0f), sigmoid(logit), l};
+  }
+  __device__ __forceinline__ bool valid(const float4 o, float s) const { return box_min_side(o, min_size) && (s >= score_thresh); }
+  __device__ __forceinline__ long long pad_label(int l) const { return l; }
+};
+
+// RetinaNet.postprocess_detections (retinanet.py:414-472): the flat index of a level's [HWA x classes] scores; the threshold was the top-k's
+struct RetinaSource {
+  int num_classes;
+  long long hwa[MAX_LEVELS];
+  const float* reg[MAX_LEVELS];        // [N, HWA_l, 4]
+  const float* anchors[MAX_LEVELS];    // [HWA_l, 4]
+  __device__ __forceinline__ Candidate get(int img, int l, long long idx, float logit) const {
+    const long long a = idx / num_classes;
+    return {ld4(anchors[l], a), ld4(reg[l], (long long)img * hwa[l] + a), make_float4(1.0f, 1.0f, 1.0f, 1.0f), sigmoid(logit), idx - a * num_classes};
+  }
+  __device__ __forceinline__ bool valid(const float4, float) const { return true; }
+  __device__ __forceinline__ long long pad_label(int) const { return 0; }
+};
+
+// RoIHeads.postprocess_detections (roi_heads.py:715-781): (proposal, class) from the flat index of the [P x C] scores, the head's coder
+// weights, the score as given, small boxes masked
+struct RoiSource {
+  int P, C;
+  const float *reg, *props;      // [N, P, C, 4], [N, P, 4]
+  float wx, wy, ww, wh, min_size;
+  __device__ __forceinline__ Candidate get(int img, int, long long idx, float score) const {
+    const int p = (int)(idx / C), cls = (int)(idx - (long long)p * C);
+    const long long row = (long long)img * P + p;
+    return {ld4(props, row), ld4(reg, row * C + cls), make_float4(wx, wy, ww, wh), score, cls};
+  }
+  __device__ __forceinline__ bool valid(const float4 o, float) const { return box_min_side(o, min_size); }
+  __device__ __forceinline__ long long pad_label(int) const { return 0; }
+};
+
+// One thread per candidate (image, j).  -ffp-contract=off keeps decode and clip bit-equal to the composed route (ops.box_decode, then
+// clip_boxes_to_image in torch).
+template <class Source>
+__global__ __launch_bounds__(256) void candidate_kernel(TopkLevels L, Source src, const float* __restrict__ lim, int n_images, float xform_clip,
+                                                        float* __restrict__ boxes, float* __restrict__ masked, float* __restrict__ scores,
+                                                        long long* __restrict__ labels) {
   const int K = L.koff[L.nlev];
   const long long total = (long long)n_images * K;
   for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
     const int img = (int)(t / K), j = (int)(t - (long long)img * K);
-    int l = 0;
-#pragma unroll
-    for (int q = 1; q < MAX_LEVELS; ++q)
-      if (q < L.nlev && j >= L.koff[q]) l = q;
-    const int jj = j - L.koff[l], kl = L.k[l];
-    if (jj >= ((const int*)(ws + L.cnt_off[l]))[img]) {      // not selected (the row holds fewer than k finite logits): a masked zero box
+    const int l = level_of(L, j), jj = j - L.koff[l];
+    if (jj >= L.cnt[l][img]) {      // not selected: a masked zero box
       *(float4*)(boxes + 4 * t) = make_float4(0.f, 0.f, 0.f, 0.f);
       scores[t] = 0.f;
       masked[t] = -INFINITY;
-      lvl[t] = l;
+      labels[t] = src.pad_label(l);
       continue;
     }
-    const long long a = (long long)L.start[l] + ((const long long*)(ws + L.idx_off[l]))[(long long)img * kl + jj];
-    const float logit = ((const float*)(ws + L.val_off[l]))[(long long)img * kl + jj];
-    const float4 b = *(const float4*)(anchors + 4 * a), c = *(const float4*)(deltas + 4 * ((long long)img * A + a));
-    const float w = b.z - b.x, h = b.w - b.y, cx = b.x + 0.5f * w, cy = b.y + 0.5f * h;
-    const float dw = fminf(c.z, xform_clip), dh = fminf(c.w, xform_clip);
-    const float pcx = c.x * w + cx, pcy = c.y * h + cy, pw = expf(dw) * w, ph = expf(dh) * h;
-    float4 o = make_float4(pcx - 0.5f * pw, pcy - 0.5f * ph, pcx + 0.5f * pw, pcy + 0.5f * ph);
-    const float4 m = *(const float4*)(lim + 4 * img);
-    o.x = fminf(fmaxf(o.x, 0.f), m.x);
-    o.y = fminf(fmaxf(o.y, 0.f), m.y);
-    o.z = fminf(fmaxf(o.z, 0.f), m.z);
-    o.w = fminf(fmaxf(o.w, 0.f), m.w);
-    const float s = 1.0f / (1.0f + expf(-logit));
-    const bool valid = (o.z - o.x >= min_size) && (o.w - o.y >= min_size) && (s >= score_thresh);
+    const long long e = (long long)img * L.k[l] + jj;
+    const Candidate c = src.get(img, l, L.idx[l][e], L.val[l][e]);
+    const float4 o = box_clip(box_decode(c.code, c.box, c.weights.x, c.weights.y, c.weights.z, c.weights.w, xform_clip), ld4(lim, img));
     *(float4*)(boxes + 4 * t) = o;
-    scores[t] = s;
-    masked[t] = valid ? s : -INFINITY;
-    lvl[t] = l;
+    scores[t] = c.score;
+    masked[t] = src.valid(o, c.score) ? c.score : -INFINITY;
+    labels[t] = c.label;
   }
 }
 
 // One workgroup per image: the kept list is in descending (masked) score order, so the masked candidates that survived come last and the
-// valid survivors are a prefix; count them, cut at post_nms_top_n, gather.
-__global__ __launch_bounds__(256) void rpn_gather_kernel(const float* __restrict__ boxes, const float* __restrict__ masked,
-                                                         const float* __restrict__ scores, const long long* __restrict__ keep,
-                                                         const int* __restrict__ keep_cnt, int K, int post, float* __restrict__ out_boxes,
-                                                         float* __restrict__ out_scores, int* __restrict__ out_counts) {
+// valid survivors are a prefix; count them, cut at `post`, gather.  LABELS: with the label column (the detection tails).
+template <bool LABELS>
+__global__ __launch_bounds__(256) void gather_kernel(const float* __restrict__ boxes, const float* __restrict__ masked,
+                                                     const float* __restrict__ scores, const long long* __restrict__ labels,
+                                                     const long long* __restrict__ keep, const int* __restrict__ keep_cnt, int K, int post,
+                                                     float* __restrict__ out_boxes, float* __restrict__ out_scores,
+                                                     long long* __restrict__ out_labels, int* __restrict__ out_counts) {
   __shared__ int s_cnt;
   const int img = blockIdx.x;
   if (threadIdx.x == 0) s_cnt = 0;
@@ -86,14 +139,17 @@ __global__ __launch_bounds__(256) void rpn_gather_kernel(const float* __restrict
   if (threadIdx.x == 0) out_counts[img] = cnt;
   for (int j = threadIdx.x; j < post; j += blockDim.x) {
     float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
-    float s = 0.f;
+    float sc = 0.f;
+    long long lb = 0;
     if (j < cnt) {
       const long long src = (long long)img * K + kp[j];
       b = *(const float4*)(boxes + 4 * src);
-      s = scores[src];
+      sc = scores[src];
+      if (LABELS) lb = labels[src];
     }
     *(float4*)(out_boxes + 4 * ((long long)img * post + j)) = b;
-    out_scores[(long long)img * post + j] = s;
+    out_scores[(long long)img * post + j] = sc;
+    if (LABELS) out_labels[(long long)img * post + j] = lb;
   }
 }
 
@@ -122,13 +178,6 @@ struct RoiSampleArgs {
   const long long* perm_neg[ROI_MAX_IMAGES];
 };
 
-__device__ __forceinline__ float roi_iou(const float4 a, const float4 b) {      // torchvision box_iou(a = ground truth, b = candidate)
-  const float area_a = (a.z - a.x) * (a.w - a.y), area_b = (b.z - b.x) * (b.w - b.y);
-  const float w = fmaxf(fminf(a.z, b.z) - fmaxf(a.x, b.x), 0.0f), h = fmaxf(fminf(a.w, b.w) - fmaxf(a.y, b.y), 0.0f);
-  const float inter = w * h;
-  return inter / (area_a + area_b - inter);
-}
-
 __device__ __forceinline__ float4 roi_candidate(const float* __restrict__ props, const float* __restrict__ gt, int img, int P, int pc, int gt0, int j) {
   return j < pc ? *(const float4*)(props + 4 * ((long long)img * P + j)) : *(const float4*)(gt + 4 * (long long)(gt0 + j - pc));
 }
@@ -151,16 +200,9 @@ __global__ __launch_bounds__(256) void roi_match_kernel(const float* __restrict_
     const float4 b = roi_candidate(props, gt, img, P, pc, gt0, j);
     float best = -INFINITY;
     int arg = 0;
-    for (int q = 0; q < g; ++q) {
-      const float v = roi_iou(sg[q], b);
-      if (q == 0 || v > best) {           // first maximum, as torch.max(dim=0)
-        best = v;
-        arg = q;
-      }
-    }
-    int m = arg;
-    if (best < lo) m = -1;                // Matcher.BELOW_LOW_THRESHOLD
-    else if (best < hi) m = -2;           // Matcher.BETWEEN_THRESHOLDS
+    for (int q = 0; q < g; ++q)
+      matcher_argmax(box_iou(sg[q], b), q, best, arg);      // box_iou(ground truth, candidate)
+    const int m = match_verdict(best, arg, lo, hi);
     const int cl = max(m, 0);             // roi_heads.py:640 clamp(min=0)
     lab = m == -1 ? 0 : (m == -2 ? -1 : (int)gt_labels[gt0 + cl]);
     matched[(long long)img * C + j] = cl;
@@ -244,186 +286,104 @@ __global__ __launch_bounds__(1024) void roi_sample_kernel(const float* __restric
     rois[5 * o + 4] = p.w;
     out_labels[o] = lab[j];
     out_matched[o] = m;
-    // BoxCoder.encode_single (tvision/_utils.py:79-125), the operation order of box_encode_kernel
-    const float ew = p.z - p.x, eh = p.w - p.y, ecx = p.x + 0.5f * ew, ecy = p.y + 0.5f * eh;
-    const float gw = r.z - r.x, gh = r.w - r.y, gcx = r.x + 0.5f * gw, gcy = r.y + 0.5f * gh;
-    *(float4*)(out_reg + 4 * o) = make_float4(wx * (gcx - ecx) / ew, wy * (gcy - ecy) / eh, ww * logf(gw / ew), wh * logf(gh / eh));
+    *(float4*)(out_reg + 4 * o) = box_encode(p, r, wx, wy, ww, wh);
   }
 }
 
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
-struct ProposalWs {
-  ProposalLevels L;
+// The workspace of a whole-batch tail: per level the top-k outputs idx, val, cnt, then the top-k scratch, the candidates [N, K] (boxes,
+// masked scores for the NMS, scores, labels), the NMS outputs and the NMS scratch.
+struct DetWs {
+  TopkLevels L;
   int K;
-  size_t topk_ws, boxes, masked, scores, lvl, keep, keep_cnt, nms_ws, total;
+  void *topk_ws, *nms_ws;
+  float *boxes, *masked, *scores;
+  long long *labels, *keep;
+  int* keep_cnt;
+  size_t total;
 };
 
-int proposal_layout(int n_images, const int64_t* level_counts, int nlev, int pre, ProposalWs& W) {
-  if (n_images <= 0 || nlev <= 0 || nlev > MAX_LEVELS || pre <= 0 || !level_counts) return 1;
+// ws == nullptr: only W.total is wanted (the *_workspace functions)
+void det_layout(int n_images, int nlev, const int* k, void* ws, DetWs& W) {
   size_t off = 0;
-  long long start = 0;
+  auto take = [&](size_t bytes) {
+    void* p = (void*)((uintptr_t)ws + off);
+    off = align256(off + bytes);
+    return p;
+  };
+  W.L = TopkLevels{};
   W.L.nlev = nlev;
-  W.L.koff[0] = 0;
-  for (int l = 0; l < nlev; ++l) {
-    if (level_counts[l] <= 0 || start + level_counts[l] >= (1ll << 31)) return 1;
-    const int k = (int)(level_counts[l] < pre ? level_counts[l] : pre);
-    W.L.start[l] = (int)start;
-    W.L.k[l] = k;
-    W.L.koff[l + 1] = W.L.koff[l] + k;
-    W.L.idx_off[l] = (long long)off;
-    off = align256(off + (size_t)n_images * k * sizeof(int64_t));
-    W.L.val_off[l] = (long long)off;
-    off = align256(off + (size_t)n_images * k * sizeof(float));
-    W.L.cnt_off[l] = (long long)off;
-    off = align256(off + (size_t)n_images * sizeof(int32_t));
-    start += level_counts[l];
+  for (int l = 0; l < MAX_LEVELS; ++l) {
+    W.L.koff[l + 1] = W.L.koff[l];
+    if (l >= nlev) continue;
+    W.L.k[l] = k[l];
+    W.L.koff[l + 1] += k[l];
+    W.L.idx[l] = (int64_t*)take((size_t)n_images * k[l] * sizeof(int64_t));
+    W.L.val[l] = (float*)take((size_t)n_images * k[l] * sizeof(float));
+    W.L.cnt[l] = (int*)take((size_t)n_images * sizeof(int32_t));
   }
-  for (int l = nlev; l < MAX_LEVELS; ++l) W.L.start[l] = W.L.k[l] = 0, W.L.koff[l + 1] = W.L.koff[nlev], W.L.idx_off[l] = W.L.val_off[l] = W.L.cnt_off[l] = 0;
   W.K = W.L.koff[nlev];
   const size_t NK = (size_t)n_images * W.K;
-  W.topk_ws = off, off = align256(off + mi355det_topk_workspace(n_images));
-  W.boxes = off, off = align256(off + NK * 4 * sizeof(float));
-  W.masked = off, off = align256(off + NK * sizeof(float));
-  W.scores = off, off = align256(off + NK * sizeof(float));
-  W.lvl = off, off = align256(off + NK * sizeof(int64_t));
-  W.keep = off, off = align256(off + NK * sizeof(int64_t));
-  W.keep_cnt = off, off = align256(off + sizeof(int32_t) * (size_t)n_images);
-  W.nms_ws = off, off = align256(off + mi355det_nms_workspace(n_images, W.K));
+  W.topk_ws = take(mi355det_topk_workspace(n_images));
+  W.boxes = (float*)take(NK * 4 * sizeof(float));
+  W.masked = (float*)take(NK * sizeof(float));
+  W.scores = (float*)take(NK * sizeof(float));
+  W.labels = (long long*)take(NK * sizeof(int64_t));
+  W.keep = (long long*)take(NK * sizeof(int64_t));
+  W.keep_cnt = (int*)take(sizeof(int32_t) * (size_t)n_images);
+  W.nms_ws = take(mi355det_nms_workspace(n_images, W.K));
   W.total = off;
+}
+
+// The argument checks of the three heads; each ends in det_layout.  Non-zero: invalid.
+int rpn_layout(int n_images, const int64_t* level_counts, int nlev, int pre, void* ws, DetWs& W) {
+  if (n_images <= 0 || nlev <= 0 || nlev > MAX_LEVELS || pre <= 0 || !level_counts) return 1;
+  int k[MAX_LEVELS];
+  long long start = 0;
+  for (int l = 0; l < nlev; ++l) {
+    if (level_counts[l] <= 0 || start + level_counts[l] >= (1ll << 31)) return 1;
+    k[l] = (int)(level_counts[l] < pre ? level_counts[l] : pre);
+    start += level_counts[l];
+  }
+  det_layout(n_images, nlev, k, ws, W);
   return 0;
 }
 
-// ---- RetinaNet.postprocess_detections for the whole batch (tvision/retinanet.py:414-472) ------------------------------------------------
-// per level: thresholded top-k over the flattened [HWA x K] scores of every image (mi355det_topk_ws), then ONE kernel for all levels:
-// anchor / class from the flat index, decode + clip of the selected anchors, sigmoid; per-class NMS of all images side by side; the first
-// detections_per_img survivors gathered.  Candidates a level could not fill (fewer than k scores above the threshold) are masked entries.
-struct RetinaLevels {
-  int nlev, num_classes;
-  int k[MAX_LEVELS], koff[MAX_LEVELS + 1];
-  long long hwa[MAX_LEVELS];
-  long long idx_off[MAX_LEVELS], val_off[MAX_LEVELS], cnt_off[MAX_LEVELS];
-  const float* reg[MAX_LEVELS];        // [N, HWA_l, 4]
-  const float* anchors[MAX_LEVELS];    // [HWA_l, 4]
-};
-
-__global__ __launch_bounds__(256) void retina_select_kernel(const char* __restrict__ ws, RetinaLevels L, const float* __restrict__ lim, int n_images,
-                                                            float xform_clip, float* __restrict__ boxes, float* __restrict__ masked,
-                                                            float* __restrict__ scores, long long* __restrict__ labels) {
-  const int K = L.koff[L.nlev];
-  const long long total = (long long)n_images * K;
-  for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
-    const int img = (int)(t / K), j = (int)(t - (long long)img * K);
-    int l = 0;
-#pragma unroll
-    for (int q = 1; q < MAX_LEVELS; ++q)
-      if (q < L.nlev && j >= L.koff[q]) l = q;
-    const int jj = j - L.koff[l], kl = L.k[l];
-    if (jj >= ((const int*)(ws + L.cnt_off[l]))[img]) {
-      *(float4*)(boxes + 4 * t) = make_float4(0.f, 0.f, 0.f, 0.f);
-      scores[t] = 0.f;
-      masked[t] = -INFINITY;
-      labels[t] = 0;
-      continue;
-    }
-    const long long flat = ((const long long*)(ws + L.idx_off[l]))[(long long)img * kl + jj];
-    const float logit = ((const float*)(ws + L.val_off[l]))[(long long)img * kl + jj];
-    const long long a = flat / L.num_classes;
-    const int cls = (int)(flat - a * L.num_classes);
-    const float4 b = *(const float4*)(L.anchors[l] + 4 * a), c = *(const float4*)(L.reg[l] + 4 * ((long long)img * L.hwa[l] + a));
-    const float w = b.z - b.x, h = b.w - b.y, cx = b.x + 0.5f * w, cy = b.y + 0.5f * h;
-    const float dw = fminf(c.z, xform_clip), dh = fminf(c.w, xform_clip);
-    const float pcx = c.x * w + cx, pcy = c.y * h + cy, pw = expf(dw) * w, ph = expf(dh) * h;
-    float4 o = make_float4(pcx - 0.5f * pw, pcy - 0.5f * ph, pcx + 0.5f * pw, pcy + 0.5f * ph);
-    const float4 m = *(const float4*)(lim + 4 * img);
-    o.x = fminf(fmaxf(o.x, 0.f), m.x);
-    o.y = fminf(fmaxf(o.y, 0.f), m.y);
-    o.z = fminf(fmaxf(o.z, 0.f), m.z);
-    o.w = fminf(fmaxf(o.w, 0.f), m.w);
-    const float sc = 1.0f / (1.0f + expf(-logit));
-    *(float4*)(boxes + 4 * t) = o;
-    scores[t] = sc;
-    masked[t] = sc;
-    labels[t] = cls;
-  }
-}
-
-__global__ __launch_bounds__(256) void retina_gather_kernel(const float* __restrict__ boxes, const float* __restrict__ masked,
-                                                            const float* __restrict__ scores, const long long* __restrict__ labels,
-                                                            const long long* __restrict__ keep, const int* __restrict__ keep_cnt, int K, int post,
-                                                            float* __restrict__ out_boxes, float* __restrict__ out_scores,
-                                                            long long* __restrict__ out_labels, int* __restrict__ out_counts) {
-  __shared__ int s_cnt;
-  const int img = blockIdx.x;
-  if (threadIdx.x == 0) s_cnt = 0;
-  __syncthreads();
-  const int kc = min(keep_cnt[img], K);
-  const long long* kp = keep + (long long)img * K;
-  int mine = 0;
-  for (int j = threadIdx.x; j < kc; j += blockDim.x) mine += masked[(long long)img * K + kp[j]] > -INFINITY ? 1 : 0;
-  for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o, WAVE);
-  if ((threadIdx.x & (WAVE - 1)) == 0 && mine) atomicAdd(&s_cnt, mine);
-  __syncthreads();
-  const int cnt = min(s_cnt, post);
-  if (threadIdx.x == 0) out_counts[img] = cnt;
-  for (int j = threadIdx.x; j < post; j += blockDim.x) {
-    float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
-    float sc = 0.f;
-    long long lb = 0;
-    if (j < cnt) {
-      const long long src = (long long)img * K + kp[j];
-      b = *(const float4*)(boxes + 4 * src);
-      sc = scores[src];
-      lb = labels[src];
-    }
-    *(float4*)(out_boxes + 4 * ((long long)img * post + j)) = b;
-    out_scores[(long long)img * post + j] = sc;
-    out_labels[(long long)img * post + j] = lb;
-  }
-}
-
-struct RetinaWs {
-  RetinaLevels L;
-  int K;
-  size_t topk_ws, boxes, masked, scores, labels, keep, keep_cnt, nms_ws, total;
-};
-
-int retina_layout(int n_images, const int64_t* level_anchors, int nlev, int num_classes, int topk, RetinaWs& W) {
+int retina_layout(int n_images, const int64_t* level_anchors, int nlev, int num_classes, int topk, void* ws, DetWs& W) {
   if (n_images <= 0 || nlev <= 0 || nlev > MAX_LEVELS || num_classes <= 0 || topk <= 0 || topk > 16384 || !level_anchors) return 1;
-  size_t off = 0;
-  W.L.nlev = nlev;
-  W.L.num_classes = num_classes;
-  W.L.koff[0] = 0;
+  int k[MAX_LEVELS];
   for (int l = 0; l < nlev; ++l) {
     const long long n = level_anchors[l] * (long long)num_classes;
     if (level_anchors[l] <= 0 || n >= (1ll << 32)) return 1;
-    const int k = (int)(n < topk ? n : topk);
-    W.L.k[l] = k;
-    W.L.hwa[l] = level_anchors[l];
-    W.L.koff[l + 1] = W.L.koff[l] + k;
-    W.L.idx_off[l] = (long long)off;
-    off = align256(off + (size_t)n_images * k * sizeof(int64_t));
-    W.L.val_off[l] = (long long)off;
-    off = align256(off + (size_t)n_images * k * sizeof(float));
-    W.L.cnt_off[l] = (long long)off;
-    off = align256(off + (size_t)n_images * sizeof(int32_t));
+    k[l] = (int)(n < topk ? n : topk);
   }
-  for (int l = nlev; l < MAX_LEVELS; ++l) {
-    W.L.k[l] = 0, W.L.hwa[l] = 0, W.L.koff[l + 1] = W.L.koff[nlev], W.L.idx_off[l] = W.L.val_off[l] = W.L.cnt_off[l] = 0;
-    W.L.reg[l] = W.L.anchors[l] = nullptr;
-  }
-  W.K = W.L.koff[nlev];
-  const size_t NK = (size_t)n_images * W.K;
-  W.topk_ws = off, off = align256(off + mi355det_topk_workspace(n_images));
-  W.boxes = off, off = align256(off + NK * 4 * sizeof(float));
-  W.masked = off, off = align256(off + NK * sizeof(float));
-  W.scores = off, off = align256(off + NK * sizeof(float));
-  W.labels = off, off = align256(off + NK * sizeof(int64_t));
-  W.keep = off, off = align256(off + NK * sizeof(int64_t));
-  W.keep_cnt = off, off = align256(off + sizeof(int32_t) * (size_t)n_images);
-  W.nms_ws = off, off = align256(off + mi355det_nms_workspace(n_images, W.K));
-  W.total = off;
+  det_layout(n_images, nlev, k, ws, W);
   return 0;
+}
+
+int roi_det_layout(int n_images, int max_proposals, int num_classes, int k, void* ws, DetWs& W) {
+  const long long row = (long long)max_proposals * num_classes;
+  if (max_proposals <= 0 || num_classes <= 0 || n_images <= 0 || row >= (1ll << 32) || k <= 0 || k > 16384 || k > row) return 1;
+  det_layout(n_images, 1, &k, ws, W);
+  return 0;
+}
+
+// Candidates of every level and image, batched NMS per label, the first `post` valid survivors (out_labels may be null: the RPN)
+template <class Source>
+int detection_tail(const char* name, const DetWs& W, const Source& src, const float* clip_limits, int n_images, float xform_clip, float nms_thresh,
+                   int post, float* out_boxes, float* out_scores, int64_t* out_labels, int32_t* out_counts, void* stream) {
+  const long long total = (long long)n_images * W.K;
+  hipLaunchKernelGGL(candidate_kernel<Source>, dim3((int)((total + 255) / 256)), dim3(256), 0, S(stream), W.L, src, clip_limits, n_images, xform_clip,
+                     W.boxes, W.masked, W.scores, W.labels);
+  if (int e = mi355det_nms_batch(W.boxes, W.masked, (const int64_t*)W.labels, n_images, W.K, nms_thresh, (int64_t*)W.keep, W.keep_cnt, W.nms_ws,
+                                 mi355det_nms_workspace(n_images, W.K), stream))
+    return e;
+  auto gather = out_labels ? gather_kernel<true> : gather_kernel<false>;
+  hipLaunchKernelGGL(gather, dim3(n_images), dim3(256), 0, S(stream), (const float*)W.boxes, (const float*)W.masked, (const float*)W.scores,
+                     (const long long*)W.labels, (const long long*)W.keep, (const int*)W.keep_cnt, W.K, post, out_boxes, out_scores,
+                     (long long*)out_labels, out_counts);
+  return check_launch(name);
 }
 
 // ---- RegionProposalNetwork.compute_loss (tvision/rpn.py:282-318), forward and gradient in one launch ------------------------------------
@@ -464,78 +424,13 @@ __global__ __launch_bounds__(1024) void rpn_loss_kernel(const float* __restrict_
   }
 }
 
-// ---- RoIHeads.postprocess_detections for the whole batch (tvision/roi_heads.py:715-781) ------------------------------------------------
-// scores [N, P, C] (softmax / sigmoid / gombit already applied, class 0 and padded proposals pushed below the threshold by the caller),
-// box_regression [N, P, C, 4], proposals [N, P, 4]: thresholded top-k over the flattened P x C scores of every image, decode of the
-// selected (proposal, class) pairs with the head's BoxCoder weights, clip, small boxes masked, per-class NMS, the first detections_per_img.
-__global__ __launch_bounds__(256) void roi_det_select_kernel(const long long* __restrict__ idx, const float* __restrict__ val,
-                                                             const int* __restrict__ cnt, int k, int P, int C, const float* __restrict__ reg,
-                                                             const float* __restrict__ props, const float* __restrict__ lim, int n_images, float wx,
-                                                             float wy, float ww, float wh, float xform_clip, float min_size,
-                                                             float* __restrict__ boxes, float* __restrict__ masked, float* __restrict__ scores,
-                                                             long long* __restrict__ labels) {
-  const long long total = (long long)n_images * k;
-  for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
-    const int img = (int)(t / k), j = (int)(t - (long long)img * k);
-    if (j >= cnt[img]) {
-      *(float4*)(boxes + 4 * t) = make_float4(0.f, 0.f, 0.f, 0.f);
-      scores[t] = 0.f;
-      masked[t] = -INFINITY;
-      labels[t] = 0;
-      continue;
-    }
-    const long long flat = idx[t];
-    const int p = (int)(flat / C), cls = (int)(flat - (long long)p * C);
-    const float4 b = *(const float4*)(props + 4 * ((long long)img * P + p));
-    const float4 c = *(const float4*)(reg + 4 * (((long long)img * P + p) * C + cls));
-    const float w = b.z - b.x, h = b.w - b.y, cx = b.x + 0.5f * w, cy = b.y + 0.5f * h;
-    const float dx = c.x / wx, dy = c.y / wy, dw = fminf(c.z / ww, xform_clip), dh = fminf(c.w / wh, xform_clip);      // box_decode_kernel's order
-    const float pcx = dx * w + cx, pcy = dy * h + cy, pw = expf(dw) * w, ph = expf(dh) * h;
-    float4 o = make_float4(pcx - 0.5f * pw, pcy - 0.5f * ph, pcx + 0.5f * pw, pcy + 0.5f * ph);
-    const float4 m = *(const float4*)(lim + 4 * img);
-    o.x = fminf(fmaxf(o.x, 0.f), m.x);
-    o.y = fminf(fmaxf(o.y, 0.f), m.y);
-    o.z = fminf(fmaxf(o.z, 0.f), m.z);
-    o.w = fminf(fmaxf(o.w, 0.f), m.w);
-    const float sc = val[t];
-    const bool valid = (o.z - o.x >= min_size) && (o.w - o.y >= min_size);
-    *(float4*)(boxes + 4 * t) = o;
-    scores[t] = sc;
-    masked[t] = valid ? sc : -INFINITY;
-    labels[t] = cls;
-  }
-}
-
-struct RoiDetWs {
-  size_t idx, val, cnt, topk_ws, boxes, masked, scores, labels, keep, keep_cnt, nms_ws, total;
-};
-
-int roi_det_layout(int n_images, long long row, int k, RoiDetWs& W) {
-  if (n_images <= 0 || row <= 0 || row >= (1ll << 32) || k <= 0 || k > 16384 || k > row) return 1;
-  const size_t NK = (size_t)n_images * k;
-  size_t off = 0;
-  W.idx = off, off = align256(off + NK * sizeof(int64_t));
-  W.val = off, off = align256(off + NK * sizeof(float));
-  W.cnt = off, off = align256(off + sizeof(int32_t) * (size_t)n_images);
-  W.topk_ws = off, off = align256(off + mi355det_topk_workspace(n_images));
-  W.boxes = off, off = align256(off + NK * 4 * sizeof(float));
-  W.masked = off, off = align256(off + NK * sizeof(float));
-  W.scores = off, off = align256(off + NK * sizeof(float));
-  W.labels = off, off = align256(off + NK * sizeof(int64_t));
-  W.keep = off, off = align256(off + NK * sizeof(int64_t));
-  W.keep_cnt = off, off = align256(off + sizeof(int32_t) * (size_t)n_images);
-  W.nms_ws = off, off = align256(off + mi355det_nms_workspace(n_images, k));
-  W.total = off;
-  return 0;
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t mi355det_rpn_proposals_workspace(int32_t n_images, const int64_t* level_counts, int32_t nlev, int32_t pre_nms_top_n) {
-  ProposalWs W;
-  if (proposal_layout(n_images, level_counts, nlev, pre_nms_top_n, W)) return 0;
+  DetWs W;
+  if (rpn_layout(n_images, level_counts, nlev, pre_nms_top_n, nullptr, W)) return 0;
   return W.total;
 }
 
@@ -543,45 +438,27 @@ int mi355det_rpn_proposals(const float* objectness, const float* deltas, const f
                            const int64_t* level_counts, int32_t nlev, int32_t pre_nms_top_n, int32_t post_nms_top_n, float nms_thresh,
                            float score_thresh, float min_size, float xform_clip, float* out_boxes, float* out_scores, int32_t* out_counts,
                            void* workspace, size_t workspace_bytes, void* stream) {
-  ProposalWs W;
-  if (proposal_layout(n_images, level_counts, nlev, pre_nms_top_n, W))
+  DetWs W;
+  if (rpn_layout(n_images, level_counts, nlev, pre_nms_top_n, workspace, W))
     return fail(MI355DET_EINVAL, "%s: need 1..8 non-empty levels, fewer than 2^31 anchors, positive batch and pre_nms_top_n", "rpn_proposals");
   if (post_nms_top_n <= 0) return fail(MI355DET_EINVAL, "%s: post_nms_top_n must be positive", "rpn_proposals");
   if (!objectness || !deltas || !anchors || !clip_limits || !out_boxes || !out_scores || !out_counts || !workspace)
     return fail(MI355DET_EINVAL, "%s: null argument", "rpn_proposals");
   if (workspace_bytes < W.total) return fail(MI355DET_EWORKSPACE, "%s: workspace too small", "rpn_proposals");
-  char* ws = (char*)workspace;
-  long long A = 0;
-  for (int l = 0; l < nlev; ++l) A += level_counts[l];
-  {                                      // rpn.py:215-228: per-level top-k of the logits; every level and image in one launch sequence
-    int64_t seg_start[MAX_LEVELS];
-    int32_t seg_k[MAX_LEVELS];
-    int64_t* idx_out[MAX_LEVELS];
-    float* val_out[MAX_LEVELS];
-    int32_t* cnt_out[MAX_LEVELS];
-    for (int l = 0; l < nlev; ++l) {
-      seg_start[l] = W.L.start[l];
-      seg_k[l] = W.L.k[l];
-      idx_out[l] = (int64_t*)(ws + W.L.idx_off[l]);
-      val_out[l] = (float*)(ws + W.L.val_off[l]);
-      cnt_out[l] = (int32_t*)(ws + W.L.cnt_off[l]);
-    }
-    if (int e = mi355det_topk_segments(objectness, n_images, A, nlev, seg_start, level_counts, seg_k, -INFINITY, idx_out, val_out, cnt_out,
-                                       ws + W.topk_ws, mi355det_topk_workspace(n_images), stream))
-      return e;
+  RpnSource src{};
+  src.deltas = deltas, src.anchors = anchors, src.min_size = min_size, src.score_thresh = score_thresh;
+  int64_t seg_start[MAX_LEVELS];
+  for (int l = 0; l < nlev; ++l) {
+    src.start[l] = (int)src.A;
+    seg_start[l] = src.A;
+    src.A += level_counts[l];
   }
-  const long long total = (long long)n_images * W.K;
-  hipLaunchKernelGGL(rpn_select_kernel, dim3((int)((total + 255) / 256)), dim3(256), 0, S(stream), ws, W.L, deltas, anchors, clip_limits, n_images,
-                     A, xform_clip, min_size, score_thresh, (float*)(ws + W.boxes), (float*)(ws + W.masked), (float*)(ws + W.scores),
-                     (long long*)(ws + W.lvl));
-  if (int e = mi355det_nms_batch((const float*)(ws + W.boxes), (const float*)(ws + W.masked), (const int64_t*)(ws + W.lvl), n_images, W.K,
-                                 nms_thresh, (int64_t*)(ws + W.keep), (int32_t*)(ws + W.keep_cnt), ws + W.nms_ws,
-                                 mi355det_nms_workspace(n_images, W.K), stream))
+  // rpn.py:215-228: per-level top-k of the logits; every level and image in one launch sequence
+  if (int e = mi355det_topk_segments(objectness, n_images, src.A, nlev, seg_start, level_counts, W.L.k, -INFINITY, W.L.idx, W.L.val, W.L.cnt, W.topk_ws,
+                                     mi355det_topk_workspace(n_images), stream))
     return e;
-  hipLaunchKernelGGL(rpn_gather_kernel, dim3(n_images), dim3(256), 0, S(stream), (const float*)(ws + W.boxes), (const float*)(ws + W.masked),
-                     (const float*)(ws + W.scores), (const long long*)(ws + W.keep), (const int*)(ws + W.keep_cnt), W.K, post_nms_top_n, out_boxes,
-                     out_scores, out_counts);
-  return check_launch("rpn_proposals");
+  return detection_tail("rpn_proposals", W, src, clip_limits, n_images, xform_clip, nms_thresh, post_nms_top_n, out_boxes, out_scores, nullptr,
+                        out_counts, stream);
 }
 
 int mi355det_roi_match(const float* proposals, const int32_t* proposal_counts, int32_t n_images, int32_t max_proposals, const float* gt_boxes,
@@ -642,8 +519,8 @@ int mi355det_roi_sample(const float* proposals, const int32_t* proposal_counts, 
 }
 
 size_t mi355det_retina_detections_workspace(int32_t n_images, const int64_t* level_anchors, int32_t nlev, int32_t num_classes, int32_t topk_candidates) {
-  RetinaWs W;
-  if (retina_layout(n_images, level_anchors, nlev, num_classes, topk_candidates, W)) return 0;
+  DetWs W;
+  if (retina_layout(n_images, level_anchors, nlev, num_classes, topk_candidates, nullptr, W)) return 0;
   return W.total;
 }
 
@@ -652,33 +529,27 @@ int mi355det_retina_detections(const float* const* cls_logits, const float* cons
                                float logit_thresh, int32_t topk_candidates, float nms_thresh, int32_t detections_per_img, float xform_clip,
                                float* out_boxes, float* out_scores, int64_t* out_labels, int32_t* out_counts, void* workspace,
                                size_t workspace_bytes, void* stream) {
-  RetinaWs W;
-  if (retina_layout(n_images, level_anchors, nlev, num_classes, topk_candidates, W))
+  DetWs W;
+  if (retina_layout(n_images, level_anchors, nlev, num_classes, topk_candidates, workspace, W))
     return fail(MI355DET_EINVAL, "%s: need 1..8 levels with fewer than 2^32 scores per image, 1 <= topk_candidates <= 16384", "retina_detections");
   if (detections_per_img <= 0 || !cls_logits || !bbox_regression || !anchors || !clip_limits || !out_boxes || !out_scores || !out_labels || !out_counts ||
       !workspace)
     return fail(MI355DET_EINVAL, "%s: null argument or detections_per_img <= 0", "retina_detections");
   if (workspace_bytes < W.total) return fail(MI355DET_EWORKSPACE, "%s: workspace too small", "retina_detections");
-  char* ws = (char*)workspace;
+  RetinaSource src{};
+  src.num_classes = num_classes;
   for (int l = 0; l < nlev; ++l) {
     if (!cls_logits[l] || !bbox_regression[l] || !anchors[l]) return fail(MI355DET_EINVAL, "%s: null level pointer", "retina_detections");
-    W.L.reg[l] = bbox_regression[l];
-    W.L.anchors[l] = anchors[l];
+    src.hwa[l] = level_anchors[l];
+    src.reg[l] = bbox_regression[l];
+    src.anchors[l] = anchors[l];
     const long long n = level_anchors[l] * (long long)num_classes;          // retinanet.py:437-445: threshold, then top-k of the flattened scores
-    if (int e = mi355det_topk_ws(cls_logits[l], n_images, n, n, W.L.k[l], logit_thresh, (int64_t*)(ws + W.L.idx_off[l]), (float*)(ws + W.L.val_off[l]),
-                                 (int32_t*)(ws + W.L.cnt_off[l]), ws + W.topk_ws, mi355det_topk_workspace(n_images), stream))
+    if (int e = mi355det_topk_ws(cls_logits[l], n_images, n, n, W.L.k[l], logit_thresh, W.L.idx[l], W.L.val[l], W.L.cnt[l], W.topk_ws,
+                                 mi355det_topk_workspace(n_images), stream))
       return e;
   }
-  const long long total = (long long)n_images * W.K;
-  hipLaunchKernelGGL(retina_select_kernel, dim3((int)((total + 255) / 256)), dim3(256), 0, S(stream), ws, W.L, clip_limits, n_images, xform_clip,
-                     (float*)(ws + W.boxes), (float*)(ws + W.masked), (float*)(ws + W.scores), (long long*)(ws + W.labels));
-  if (int e = mi355det_nms_batch((const float*)(ws + W.boxes), (const float*)(ws + W.masked), (const int64_t*)(ws + W.labels), n_images, W.K, nms_thresh,
-                                 (int64_t*)(ws + W.keep), (int32_t*)(ws + W.keep_cnt), ws + W.nms_ws, mi355det_nms_workspace(n_images, W.K), stream))
-    return e;
-  hipLaunchKernelGGL(retina_gather_kernel, dim3(n_images), dim3(256), 0, S(stream), (const float*)(ws + W.boxes), (const float*)(ws + W.masked),
-                     (const float*)(ws + W.scores), (const long long*)(ws + W.labels), (const long long*)(ws + W.keep), (const int*)(ws + W.keep_cnt), W.K,
-                     detections_per_img, out_boxes, out_scores, (long long*)out_labels, out_counts);
-  return check_launch("retina_detections");
+  return detection_tail("retina_detections", W, src, clip_limits, n_images, xform_clip, nms_thresh, detections_per_img, out_boxes, out_scores,
+                        out_labels, out_counts, stream);
 }
 
 int mi355det_rpn_loss(const float* objectness, const float* pred_bbox_deltas, const float* labels, const float* regression_targets, int64_t total,
@@ -697,8 +568,8 @@ int mi355det_rpn_loss(const float* objectness, const float* pred_bbox_deltas, co
 }
 
 size_t mi355det_roi_detections_workspace(int32_t n_images, int32_t max_proposals, int32_t num_classes, int32_t max_candidates) {
-  RoiDetWs W;
-  if (max_proposals <= 0 || num_classes <= 0 || roi_det_layout(n_images, (long long)max_proposals * num_classes, max_candidates, W)) return 0;
+  DetWs W;
+  if (roi_det_layout(n_images, max_proposals, num_classes, max_candidates, nullptr, W)) return 0;
   return W.total;
 }
 
@@ -707,31 +578,21 @@ int mi355det_roi_detections(const float* scores, const float* box_regression, co
                             float wh, float xform_clip, float min_size, float nms_thresh, int32_t detections_per_img, float* out_boxes,
                             float* out_scores, int64_t* out_labels, int32_t* out_counts, int32_t* candidate_counts, void* workspace,
                             size_t workspace_bytes, void* stream) {
-  RoiDetWs W;
-  if (max_proposals <= 0 || num_classes <= 0 || roi_det_layout(n_images, (long long)max_proposals * num_classes, max_candidates, W))
+  DetWs W;
+  if (roi_det_layout(n_images, max_proposals, num_classes, max_candidates, workspace, W))
     return fail(MI355DET_EINVAL, "%s: need a positive batch, 1 <= max_candidates <= min(16384, proposals x classes)", "roi_detections");
   if (detections_per_img <= 0 || !scores || !box_regression || !proposals || !clip_limits || !out_boxes || !out_scores || !out_labels || !out_counts ||
       !candidate_counts || !workspace)
     return fail(MI355DET_EINVAL, "%s: null argument or detections_per_img <= 0", "roi_detections");
   if (workspace_bytes < W.total) return fail(MI355DET_EWORKSPACE, "%s: workspace too small", "roi_detections");
-  char* ws = (char*)workspace;
+  W.L.cnt[0] = candidate_counts;      // the candidates per image are an output of this call: the top-k writes them there, not into the workspace
   const long long row = (long long)max_proposals * num_classes;
-  if (int e = mi355det_topk_ws(scores, n_images, row, row, max_candidates, score_thresh, (int64_t*)(ws + W.idx), (float*)(ws + W.val), candidate_counts,
-                               ws + W.topk_ws, mi355det_topk_workspace(n_images), stream))
+  if (int e = mi355det_topk_ws(scores, n_images, row, row, max_candidates, score_thresh, W.L.idx[0], W.L.val[0], W.L.cnt[0], W.topk_ws,
+                               mi355det_topk_workspace(n_images), stream))
     return e;
-  const long long total = (long long)n_images * max_candidates;
-  hipLaunchKernelGGL(roi_det_select_kernel, dim3((int)((total + 255) / 256)), dim3(256), 0, S(stream), (const long long*)(ws + W.idx),
-                     (const float*)(ws + W.val), (const int*)candidate_counts, max_candidates, max_proposals, num_classes, box_regression, proposals,
-                     clip_limits, n_images, wx, wy, ww, wh, xform_clip, min_size, (float*)(ws + W.boxes), (float*)(ws + W.masked),
-                     (float*)(ws + W.scores), (long long*)(ws + W.labels));
-  if (int e = mi355det_nms_batch((const float*)(ws + W.boxes), (const float*)(ws + W.masked), (const int64_t*)(ws + W.labels), n_images, max_candidates,
-                                 nms_thresh, (int64_t*)(ws + W.keep), (int32_t*)(ws + W.keep_cnt), ws + W.nms_ws,
-                                 mi355det_nms_workspace(n_images, max_candidates), stream))
-    return e;
-  hipLaunchKernelGGL(retina_gather_kernel, dim3(n_images), dim3(256), 0, S(stream), (const float*)(ws + W.boxes), (const float*)(ws + W.masked),
-                     (const float*)(ws + W.scores), (const long long*)(ws + W.labels), (const long long*)(ws + W.keep), (const int*)(ws + W.keep_cnt),
-                     max_candidates, detections_per_img, out_boxes, out_scores, (long long*)out_labels, out_counts);
-  return check_launch("roi_detections");
+  const RoiSource src{max_proposals, num_classes, box_regression, proposals, wx, wy, ww, wh, min_size};
+  return detection_tail("roi_detections", W, src, clip_limits, n_images, xform_clip, nms_thresh, detections_per_img, out_boxes, out_scores, out_labels,
+                        out_counts, stream);
 }
 
 }  // extern "C"

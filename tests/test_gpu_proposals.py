@@ -237,3 +237,78 @@ def test_roi_detections_batch_matches_per_image_route(loss_type, c):
             assert a.shape == b.shape and torch.equal(a, b), (q, a.shape, b.shape)
     assert roi_heads_postprocess_detections_batch(logits, reg, pad, cnt_dev, shapes, tf, 0.05, 0.5, 100, (10.0, 10.0, 5.0, 5.0), loss_type,
                                                   max_candidates=16) is None
+
+
+def _boxes_cpu(g, shape, extent, size):
+    ctr = torch.rand(shape + (2,), generator=g) * extent
+    wh = torch.rand(shape + (2,), generator=g) * size + 2
+    return torch.cat([ctr - wh / 2, ctr + wh / 2], -1)
+
+
+def _assert_padded(i, count, ref_rows, got_rows):
+    """rows below `count` of image i equal the composed route bit for bit, every output column is zero from `count` on"""
+    for r, o in zip(ref_rows, got_rows):
+        assert r.shape[0] == count and torch.equal(o[i, :count], r), (i, count, r.shape)
+        assert (o[i, count:] == 0).all(), (i, count)
+
+
+@pytest.mark.parametrize("head", ["rpn", "retina", "roi"])
+def test_whole_batch_tails_padded_rows_and_image_without_candidates(head, monkeypatch):
+    """The candidate step and the gather the three whole-batch tails share, at the smallest sizes with two levels, a level that is not
+    filled, more outputs than candidates, and a second image in which nothing passes the threshold (finite logits: both routes see the
+    same candidates).  Padded outputs of the one-call routes against the composed routes: count 0 and all-zero rows for the empty image,
+    zero rows from counts[i] on, bit-equal rows below."""
+    from object_detectors_amd import ops
+    from object_detectors_amd.tvision import postprocess as pp
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(77)
+    shapes = [(200, 240), (192, 256)]
+    lim = pp._clip_limits(shapes, dev, torch.float32).reshape(2, 4)
+    clip = math.log(1000.0 / 16)
+    if head == "rpn":
+        levels, pre, post = [48, 16], 32, 64                     # 32 + 16 = 48 candidate columns, fewer than post
+        obj = torch.randn((2, 64), generator=g) * 3
+        obj[1] = -20.0                                           # sigmoid far below score_thresh
+        anchors = _boxes_cpu(g, (64,), 260.0, 120.0) - 10
+        deltas = torch.randn((2, 64, 4), generator=g) * 0.5
+        deltas[:, ::7, 2:] = -20.0                               # below min_size
+        obj, anchors, deltas = obj.to(dev), anchors.to(dev), deltas.to(dev)
+        props = ops.box_decode(deltas.reshape(-1, 4), anchors.repeat(2, 1), (1.0, 1.0, 1.0, 1.0), clip).reshape(2, -1, 4)
+        rb, rs = pp.rpn_filter_proposals(props, obj, shapes, levels, pre, post, 0.7, 0.5)
+        boxes, scores, counts = ops.rpn_proposals(obj, deltas, anchors, lim, levels, pre, post, 0.7, 0.5, xform_clip=clip)
+        counts = counts.tolist()
+        assert 0 < counts[0] < 48 and counts[1] == 0, counts
+        for i in range(2):
+            _assert_padded(i, counts[i], (rb[i], rs[i]), (boxes, scores))
+    elif head == "retina":
+        hwas, k_cls, topk, det = [4 * 4 * 9, 2 * 2 * 9], 3, 50, 300      # 432 and 108 scores per image: k = 50 + 50 columns
+        logits = [torch.randn((2, h, k_cls), generator=g) * 2 for h in hwas]
+        logits[1][0] -= 4.0                                      # image 0 fills its second level only in part
+        for t in logits:
+            t[1] = -20.0
+        regs = [(torch.randn((2, h, 4), generator=g) * 0.3).to(dev) for h in hwas]
+        anchors = [_boxes_cpu(g, (h,), 240.0, 60.0).to(dev) for h in hwas]
+        logits = [t.to(dev) for t in logits]
+        monkeypatch.setattr(pp, "_RETINA_FUSED", False)
+        ref = pp.retinanet_postprocess_detections(logits, regs, anchors, shapes, None, 0.05, topk, 0.5, det)
+        boxes, scores, labels, counts = ops.retina_detections(logits, regs, anchors, lim, math.log(0.05 / 0.95), topk, 0.5, det, clip)
+        counts = counts.tolist()
+        assert 0 < counts[0] < 100 and counts[1] == 0, counts
+        for i in range(2):
+            _assert_padded(i, counts[i], (ref[i]["boxes"], ref[i]["scores"], ref[i]["labels"]), (boxes, scores, labels))
+    else:
+        n, p, c, weights, max_cand, det = 2, 8, 4, (10.0, 10.0, 5.0, 5.0), 16, 32
+        class_logits = torch.randn((n * p, c), generator=g) * 4
+        class_logits[p:, 0] = 20.0                               # image 1: every foreground score far below score_thresh
+        props = _boxes_cpu(g, (n, p), 180.0, 90.0).clamp(min=0)
+        reg = torch.randn((n * p, c * 4), generator=g) * 0.5
+        reg[::3, 2::4] = -60.0                                   # collapsed boxes: dropped by remove_small_boxes
+        class_logits, props, reg = class_logits.to(dev), props.to(dev), reg.to(dev)
+        rb, rs, rl = pp.roi_heads_postprocess_detections(class_logits, reg, [props[0], props[1]], shapes, 1.0, 0.05, 0.5, det, weights, "ce")
+        sc = torch.softmax(1.0 * class_logits, -1).reshape(n, p, c)
+        sc[:, :, 0] = float("-inf")                              # the background column, as roi_heads_postprocess_detections_batch
+        boxes, scores, labels, meta, k = ops.roi_detections(sc, reg, props, lim, 0.05, max_cand, weights, 0.5, det)
+        meta = meta.tolist()
+        assert k == max_cand and 0 < meta[0] < meta[2] < max_cand and meta[1] == 0 and meta[3] == 0, meta
+        for i in range(n):
+            _assert_padded(i, meta[i], (rb[i], rs[i], rl[i]), (boxes, scores, labels))
