@@ -522,6 +522,31 @@ int mi355det_pack_weights_batched(const void* dev_table, int32_t n_entries, int3
 /* dw fp32 [cout][k][k][cin] -> torch layout [cout][cin][k][k] (param.grad) */
 int mi355det_unpack_wgrad(const mi355det_conv_shape* s, const float* dw, float* grad, void* stream);
 
+/* Grouped 3x3 convolution: conv2 of the ResNeXt Bottleneck (utilities/resnet.py: conv3x3(width, width, stride, groups), resnext50_32x4d /
+ * resnext101_32x8d).  bf16 storage only.  s->cin == s->cout are the TOTAL channel counts, `groups` divides them.  Supported: ksize 3, pad 1,
+ * stride 1 or 2, channels per group in {4, 8, 16, 32, 64}, cin a multiple of 32, any n / h / w and any pitches in_ld >= cin, out_ld >= cout
+ * (16-byte accesses when base and pitch allow, 2-byte otherwise); pitch padding is never read or written.  Everything else returns
+ * MI355DET_EINVAL before any launch.  Not a tuner candidate: one kernel per direction, no tune-record entries.
+ *   gconv_pack_elems     bf16 elements of ONE operand image (forward and data-gradient image have the same size); 0 = unsupported shape
+ *   gconv_pack_weights   fp32 masters [cout][3][3][cin/groups] (w_is_ohwi) or torch [cout][cin/groups][3][3] -> the block-diagonal forward
+ *                        image (w_fwd) and / or the flipped, transposed data-gradient image (w_dgrad); either may be NULL.  Enqueued on
+ *                        `stream`, no synchronisation (trainable layers repack every step)
+ *   gconv_fwd_ex         y = relu?(conv(x, w) * scale + shift); e may be NULL; e->relu 0 or 1; a residual or out_f32 != 0 is MI355DET_EINVAL
+ *   gconv_dgrad          dx [n,h,w,cin] (pitch in_ld) from dy [n,ho,wo,cout] (pitch out_ld): every element of dx is written, nothing is
+ *                        accumulated
+ *   gconv_wgrad          dw fp32 [cout][3][3][cin/groups] (the parameter-gradient layout) is WRITTEN, not accumulated: per-split partials go
+ *                        to the workspace with plain stores and are added in split order - no atomics, bit-identical from call to call.
+ *                        A workspace below mi355det_gconv_wgrad_workspace bytes returns MI355DET_EWORKSPACE. */
+size_t mi355det_gconv_pack_elems(const mi355det_conv_shape* s, int32_t groups);
+int mi355det_gconv_pack_weights(const mi355det_conv_shape* s, int32_t groups, const float* w, int w_is_ohwi, void* w_fwd, void* w_dgrad,
+                                void* stream);
+int mi355det_gconv_fwd_ex(const mi355det_conv_shape* s, int32_t groups, const void* x, const void* w_fwd, const mi355det_conv_epilogue* e,
+                          void* y, int out_f32, void* stream);
+int mi355det_gconv_dgrad(const mi355det_conv_shape* s, int32_t groups, const void* dy, const void* w_dgrad, void* dx, void* stream);
+size_t mi355det_gconv_wgrad_workspace(const mi355det_conv_shape* s, int32_t groups);
+int mi355det_gconv_wgrad(const mi355det_conv_shape* s, int32_t groups, const void* x, const void* dy, float* dw, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 /* BatchNorm2d (training) + LeakyReLU(0.1) around the conv (darknet.py:15-16,19-20):
  *   bn_finalize: stats -> scale/shift (+ running stats update, momentum 0.1, unbiased var).
  *   bn_act_fwd: a = lrelu(z*scale+shift) [+ residual]   (bf16 in/out, vectorised)

@@ -113,6 +113,12 @@ PROTOTYPES = {
     "mi355det_pack_table_build": (C.c_int, [P(PackItem), i32, vp, sz]),
     "mi355det_pack_weights_batched": (C.c_int, [vp, i32, i32, vp]),
     "mi355det_unpack_wgrad": (C.c_int, [P(ConvShape), vp, vp, vp]),
+    "mi355det_gconv_pack_elems": (sz, [P(ConvShape), i32]),
+    "mi355det_gconv_pack_weights": (C.c_int, [P(ConvShape), i32, vp, C.c_int, vp, vp, vp]),
+    "mi355det_gconv_fwd_ex": (C.c_int, [P(ConvShape), i32, vp, vp, P(ConvEpilogue), vp, C.c_int, vp]),
+    "mi355det_gconv_dgrad": (C.c_int, [P(ConvShape), i32, vp, vp, vp, vp]),
+    "mi355det_gconv_wgrad_workspace": (sz, [P(ConvShape), i32]),
+    "mi355det_gconv_wgrad": (C.c_int, [P(ConvShape), i32, vp, vp, vp, vp, sz, vp]),
     "mi355det_conv_autotune_mode": (C.c_int, [C.c_int]),
     "mi355det_tune_export": (sz, [vp, sz]),
     "mi355det_tune_import": (C.c_int, [vp, sz, C.c_int]),

@@ -31,6 +31,7 @@ SOURCES = [
     ("igemm8_kernels.hip", []),
     ("wgrad_kernels.hip", []),
     ("dgrad_s2_kernels.hip", []),
+    ("gconv_kernels.hip", []),                           # grouped 3x3 (ResNeXt): bf16 only, no fp16 twin
     ("elem_kernels.hip", []),
     ("stem_kernels.hip", ["-fno-slp-vectorize"]),
     ("stem_l1_kernels.hip", ["-fno-slp-vectorize"]),     # packed fp32 adds cost more moves than they save (and 36 VGPRs)

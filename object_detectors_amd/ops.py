@@ -516,6 +516,44 @@ def conv_wgrad(shape, x, dy, dw, dbias=None, workspace=None):
                                     workspace.numel() if workspace is not None else 0, stream_ptr()), "conv_wgrad")
 
 
+# ------------------------------------------------------------------------------------ grouped 3x3 convolution (bf16 storage only)
+def gconv_shape(n, h, w, c, stride=1, in_ld=None, out_ld=None):
+    """ConvShape of a grouped 3x3 convolution: c = cin = cout are the totals (the group count is a separate argument of every call)."""
+    return conv_shape(n, h, w, c, c, 3, stride, in_ld, out_ld)
+
+
+def gconv_pack(shape, groups, w_master, ohwi=False, want_dgrad=True, wf=None, wd=None):
+    """fp32 [cout, cin/groups, 3, 3] (or OHWI [cout, 3, 3, cin/groups]) -> (forward image, data-gradient image), both bf16."""
+    elems = _lib.lib().mi355det_gconv_pack_elems(C.byref(shape), groups)
+    if not elems:
+        check(-1, "gconv_pack")
+    if wf is None:
+        wf = torch.empty(elems, device=w_master.device, dtype=torch.bfloat16)
+    if want_dgrad and wd is None:
+        wd = torch.empty(elems, device=w_master.device, dtype=torch.bfloat16)
+    check(_lib.lib().mi355det_gconv_pack_weights(C.byref(shape), groups, ptr(_f32c(w_master)), int(ohwi), ptr(wf), ptr(wd) if want_dgrad else None,
+                                                 stream_ptr()), "gconv_pack_weights")
+    return wf, (wd if want_dgrad else None)
+
+
+def gconv_fwd(shape, groups, x, w_fwd, y, scale=None, shift=None, relu=False):
+    e = _lib.ConvEpilogue(ptr(scale), ptr(shift), None, 0, int(bool(relu)), 0)
+    check(_lib.lib().mi355det_gconv_fwd_ex(C.byref(shape), groups, ptr(x), ptr(w_fwd), C.byref(e), ptr(y), 0, stream_ptr()), "gconv_fwd_ex")
+
+
+def gconv_dgrad(shape, groups, dy, w_dgrad, dx):
+    check(_lib.lib().mi355det_gconv_dgrad(C.byref(shape), groups, ptr(dy), ptr(w_dgrad), ptr(dx), stream_ptr()), "gconv_dgrad")
+
+
+def gconv_wgrad(shape, groups, x, dy, dw, workspace=None):
+    """dw fp32 [cout, 3, 3, cin/groups] is written (not accumulated); fixed summation order."""
+    need = _lib.lib().mi355det_gconv_wgrad_workspace(C.byref(shape), groups)
+    if workspace is None:
+        workspace = torch.empty(max(need, 16), device=dw.device, dtype=torch.uint8)
+    check(_lib.lib().mi355det_gconv_wgrad(C.byref(shape), groups, ptr(x), ptr(dy), ptr(dw), ptr(workspace), workspace.numel(), stream_ptr()),
+          "gconv_wgrad")
+
+
 # ------------------------------------------------------------------------------------ RoIAlign / top-k
 def roi_align_multi(feats, rois, output_size, scales, sampling_ratio=2, aligned=False, k_min=2, k_max=5, grad_out=None):
     """feats: list of NCHW fp32 maps (1..4 levels); rois [K,5].  Forward -> [K,C,ph,pw]; with grad_out -> list of dfeats."""

@@ -171,10 +171,15 @@ class BackwardSchedule:
         self.py(ev.record, self.main)
         self.py(self.side.wait_event, ev)
 
-    def wgrad(self, shp, x_ptr, dy_ptr, dw, dbias, dz_index=None, record=True):
-        """mi355det_conv_wgrad on the side stream, behind everything the main stream has issued; dz_index: dy is dz2[dz_index]."""
+    def wgrad(self, shp, x_ptr, dy_ptr, dw, dbias, dz_index=None, record=True, groups=1):
+        """mi355det_conv_wgrad (groups > 1: mi355det_gconv_wgrad, which has no bias sum) on the side stream, behind everything the main
+        stream has issued; dz_index: dy is dz2[dz_index]."""
         self.publish()
-        self.bwd.append((self.L.mi355det_conv_wgrad, (C.byref(shp), x_ptr, dy_ptr, _vp(dw), _vp(dbias)) + self.ws + (self.side_ptr,)))
+        if groups > 1:
+            assert dbias is None
+            self.bwd.append((self.L.mi355det_gconv_wgrad, (C.byref(shp), groups, x_ptr, dy_ptr, _vp(dw)) + self.ws + (self.side_ptr,)))
+        else:
+            self.bwd.append((self.L.mi355det_conv_wgrad, (C.byref(shp), x_ptr, dy_ptr, _vp(dw), _vp(dbias)) + self.ws + (self.side_ptr,)))
         if record:
             ev = self.new_event()
             self.py(ev.record, self.side)

@@ -24,7 +24,11 @@ from ..plan_core import Act, BackwardSchedule, GradAccumulator, PlanBase, _vp, b
 from .anchor_utils import AnchorGenerator
 
 LAYERS = [3, 4, 6, 3]
-BODY_LAYERS = {"resnet50": [3, 4, 6, 3], "resnet101": [3, 4, 23, 3], "resnet152": [3, 8, 36, 3]}     # utilities/resnet.py:305-341
+BODY_LAYERS = {"resnet50": [3, 4, 6, 3], "resnet101": [3, 4, 23, 3], "resnet152": [3, 8, 36, 3],     # utilities/resnet.py:305-341
+               "resnext50_32x4d": [3, 4, 6, 3], "resnext101_32x8d": [3, 4, 23, 3],                      # utilities/resnet.py:328-353
+               "wide_resnet50_2": [3, 4, 6, 3], "wide_resnet101_2": [3, 4, 23, 3]}                      # utilities/resnet.py:356-389
+# (groups, width_per_group) of the Bottleneck's 3x3 convolution (resnet.py:109: width = int(planes * (base_width / 64.)) * groups)
+BODY_WIDTH = {"resnext50_32x4d": (32, 4), "resnext101_32x8d": (32, 8), "wide_resnet50_2": (1, 128), "wide_resnet101_2": (1, 128)}
 PLANES = [64, 128, 256, 512]
 STEM_K = 160        # 7*7*3 = 147 im2col columns padded to a multiple of 32
 IMAGE_MEAN = (0.485, 0.456, 0.406)
@@ -35,8 +39,8 @@ SIZE_DIVISIBLE = " (GeneralizedRCNNTransform.batch_images size_divisible)"
 
 
 class Conv:
-    def __init__(self, name, cin, cout, k, stride, bn=None, bias=False, relu=False, trainable=True, head=None):
-        self.name, self.cin, self.cout, self.k, self.stride = name, cin, cout, k, stride
+    def __init__(self, name, cin, cout, k, stride, bn=None, bias=False, relu=False, trainable=True, head=None, groups=1):
+        self.name, self.cin, self.cout, self.k, self.stride, self.groups = name, cin, cout, k, stride, groups
         self.bn, self.bias, self.relu, self.trainable, self.head = bn, bias, relu, trainable, head
         # the data gradient reduces over cout: a multiple of 64 lets it use the 64-deep k-step kernels (igemm8, shared pixel tiles) - with 32 the
         # K = 1204 cls_logits layer (9 * 1204 = 10836 channels) was left to the 128x128x32 tile: 17 ms of a 55 ms step at 314 TFLOP/s
@@ -53,14 +57,16 @@ def arch(num_classes=91, num_anchors=9, trainable_layers=3, body="resnet50", mod
     # 5 also lists 'bn1' (backbone_utils.py:103-104), which is a FrozenBatchNorm2d: buffers only, nothing becomes trainable
     specs = [Conv(B + "conv1", STEM_K, 64, 1, 1, bn=B + "bn1", relu=True, trainable="conv1" in train)]
     inpl = 64
+    groups, base_width = BODY_WIDTH.get(body, (1, 64))
     for li, (planes, nb) in enumerate(zip(PLANES, BODY_LAYERS[body]), 1):
         tr = f"layer{li}" in train
+        width = int(planes * (base_width / 64.)) * groups
         for b in range(nb):
             q = f"{B}layer{li}.{b}"
             s = 2 if (b == 0 and li > 1) else 1
-            specs.append(Conv(q + ".conv1", inpl, planes, 1, 1, bn=q + ".bn1", relu=True, trainable=tr))
-            specs.append(Conv(q + ".conv2", planes, planes, 3, s, bn=q + ".bn2", relu=True, trainable=tr))
-            specs.append(Conv(q + ".conv3", planes, planes * 4, 1, 1, bn=q + ".bn3", relu=True, trainable=tr))
+            specs.append(Conv(q + ".conv1", inpl, width, 1, 1, bn=q + ".bn1", relu=True, trainable=tr))
+            specs.append(Conv(q + ".conv2", width, width, 3, s, bn=q + ".bn2", relu=True, trainable=tr, groups=groups))
+            specs.append(Conv(q + ".conv3", width, planes * 4, 1, 1, bn=q + ".bn3", relu=True, trainable=tr))
             if b == 0:
                 specs.append(Conv(q + ".downsample.0", inpl, planes * 4, 1, s, bn=q + ".downsample.1", trainable=tr))
             inpl = planes * 4
@@ -118,7 +124,7 @@ class RetinaNetEngine:
         offs = {True: 0, False: 0}
         order = {True: [], False: []}
         for s in self.specs:
-            shape = (s.cout_store, s.k, s.k, s.cin)
+            shape = (s.cout_store, s.k, s.k, s.cin // s.groups)
             n = math.prod(shape)
             order[s.trainable].append((s.name + ".weight", offs[s.trainable], n, shape))
             offs[s.trainable] += ops.pad_to(n, 64)
@@ -145,6 +151,12 @@ class RetinaNetEngine:
         self.packed = {}
         for s in self.specs:
             shp = self._shape(s, 1, 8, 8)
+            if s.groups > 1:        # grouped 3x3: the two block-diagonal operand images of csrc/gconv_kernels.hip
+                ne = lib().mi355det_gconv_pack_elems(C.byref(shp), s.groups)
+                if not ne:
+                    check(-1, "gconv_pack_elems " + s.name)
+                self.packed[s.name] = (torch.zeros(ne, device=dev, dtype=torch.bfloat16), torch.zeros(ne, device=dev, dtype=torch.bfloat16))
+                continue
             cp = ops.cout_pad_of(s.cout)
             wf = torch.zeros(cp * s.k * s.k * s.cin, device=dev, dtype=torch.bfloat16)
             wd = torch.zeros(lib().mi355det_dgrad_pack_elems(C.byref(shp)), device=dev, dtype=torch.bfloat16) if s.name != "backbone.body.conv1" else None
@@ -158,7 +170,7 @@ class RetinaNetEngine:
         bias (torchvision FPN), N(0, 0.01) heads with the prior-probability cls bias (retinanet.py:86-97,203-211)."""
         g = torch.Generator(device="cpu").manual_seed(seed)
         for s in self.specs:
-            kk, cin = s.k * s.k, (3 if s.name.endswith("body.conv1") else s.cin)
+            kk, cin = s.k * s.k, (3 if s.name.endswith("body.conv1") else s.cin // s.groups)
             ks = 7 if s.name.endswith("body.conv1") else s.k
             if s.name.startswith("backbone.body."):
                 t = torch.randn((s.cout, cin, ks, ks), generator=g) * math.sqrt(2.0 / (s.cout * ks * ks))
@@ -228,7 +240,20 @@ class RetinaNetEngine:
     def _pack_shape(self, s):
         return self._shape(s, 1, 8, 8), ops.cout_pad_of(s.cout)
 
+    def _gconv_pack_call(self, s, need_dgrad, stream):
+        """(fn, args) that repacks one grouped 3x3 weight from its fp32 master on `stream` (no synchronisation)."""
+        wf, wd = self.packed[s.name]
+        shp = self._shape(s, 1, 8, 8)
+        return (lib().mi355det_gconv_pack_weights, (shp, s.groups, _vp(self.params[s.name + ".weight"]), 1, _vp(wf), _vp(wd) if need_dgrad else None,
+                                                    stream))
+
     def _pack(self, specs, need_dgrad):
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        for s in specs:
+            if s.groups > 1:
+                fn, args = self._gconv_pack_call(s, need_dgrad, st)
+                check(fn(*args), "gconv_pack_weights")
+        specs = [s for s in specs if s.groups == 1]
         if not specs:
             return
         tab, ne, nb = build_pack_table(lib(), self, specs, self._pack_shape, need_dgrad)
@@ -389,7 +414,11 @@ class RetinaPlan(PlanBase):
             shift = _vp(aff[1]) if aff is not None else (_vp(eng.params[name + ".bias"]) if s.bias else None)
             needs = s.trainable or x.needs_grad or (res is not None and res.needs_grad)
             rec = dict(kind="conv", name=name, spec=s, x=x, res=res, level=level, scale=aff[0] if aff is not None else None)
-            if s.head:
+            if s.groups > 1:
+                a = new_act(x.n, shp_f.ho, shp_f.wo, s.cout, needs)
+                e = _lib.ConvEpilogue(scale, shift, None, 0, int(s.relu), 0)
+                self.fwd.append((L.mi355det_gconv_fwd_ex, (C.byref(shp_f), s.groups, x.ptr, _vp(wf), C.byref(e), a.ptr, 0, self.stream)))
+            elif s.head:
                 k = K if s.head == "cls_logits" else 4
                 out = self.logits if s.head == "cls_logits" else self.bbox_reg
                 row0 = sum(self.level_rows[:level])
@@ -493,9 +522,12 @@ class RetinaPlan(PlanBase):
                     conv(f"head.{hname}.{last_name}", t, level=lvl)
 
         # ---- weight packing of the trainable convolutions (every step: the optimizer changes the fp32 masters)
-        tr = [s for s in eng.specs if s.trainable]
+        tr = [s for s in eng.specs if s.trainable and s.groups == 1]
         if tr:
             self.build_pack_table(tr, eng._pack_shape, need_dgrad=training)
+        for s in eng.specs:
+            if s.trainable and s.groups > 1:
+                self.pack.append(eng._gconv_pack_call(s, training, self.stream))
         if training:
             self._build_backward()
             self._autotune()
@@ -521,12 +553,13 @@ class RetinaPlan(PlanBase):
                 if key == "bbox_reg":
                     self.cast_box.append(call)
         dz_elems = max(r["shp"].n * r["shp"].ho * r["shp"].wo * r["shp"].cout for r in self.ops if r["kind"] == "conv")
-        ws_need = max(L.mi355det_conv_wgrad_workspace(C.byref(r["shp"])) for r in self.ops if r["kind"] == "conv")
+        ws_need = max(L.mi355det_gconv_wgrad_workspace(C.byref(r["shp"]), r["spec"].groups) if r["spec"].groups > 1
+                      else L.mi355det_conv_wgrad_workspace(C.byref(r["shp"])) for r in self.ops if r["kind"] == "conv")
         sched = BackwardSchedule(self, dev, bf, dz_elems, ws_need)
 
         # split-K data gradients (few pixels, deep reduction: the LVIS cls_logits on the small levels) share one fp32 workspace; they run
         # one after the other on the main stream
-        dws_need = max(L.mi355det_conv_dgrad_workspace(C.byref(r["shp"])) for r in self.ops if r["kind"] == "conv")
+        dws_need = max(L.mi355det_conv_dgrad_workspace(C.byref(r["shp"])) for r in self.ops if r["kind"] == "conv" and r["spec"].groups == 1)
         self.dgrad_ws = torch.empty(max(dws_need, 16), device=dev, dtype=torch.uint8) if dws_need else None
 
         def dgrad_call(shp, dy_ptr, wd, g, rptr, rld):
@@ -550,8 +583,10 @@ class RetinaPlan(PlanBase):
         producer = {id(r["a"]): r for r in self.ops if r["kind"] == "conv" and r.get("a") is not None}
         fuse_ok = True
 
-        def mask_fusable(x, shp):
+        def mask_fusable(x, shp, groups=1):
             pr = producer.get(id(x))
+            if groups > 1:
+                return None                            # the grouped data gradient has no fused form
             if not fuse_ok or pr is None or uses.get(id(x), 0) != 1 or shp.stride != 1 or x.parts or x.grad_written:
                 return None
             ps = pr["spec"]
@@ -563,8 +598,16 @@ class RetinaPlan(PlanBase):
                 return None                            # the split-K form keeps its own epilogue
             return pr
 
-        def add_dgrad(x, shp, dy_ptr, wd):
-            pr = mask_fusable(x, shp) if x.needs_grad else None
+        def add_dgrad(x, shp, dy_ptr, wd, groups=1):
+            pr = mask_fusable(x, shp, groups) if x.needs_grad else None
+            if groups > 1:
+                # grouped 3x3 (mi355det_gconv_dgrad writes every element of dx and takes no residual): its own dense tensor, which joins the
+                # activation's other contributions like any tensor - conv1's output has this one consumer, so it becomes the gradient itself
+                if x.needs_grad:
+                    d = dense(x)
+                    self.bwd.append((L.mi355det_gconv_dgrad, (C.byref(shp), groups, dy_ptr, _vp(wd), d.ptr, self.stream)))
+                    add_tensor(x, d)
+                return
             if pr is None:
                 return acc.add_dgrad(x, shp, dy_ptr, wd)
             acc.add_dgrad(x, shp, dy_ptr, wd, lambda shp, dy_ptr, wd, g, _rptr, _rld: (
@@ -650,10 +693,11 @@ class RetinaPlan(PlanBase):
                     continue
             rec["dy_ptr"] = dy_ptr
             if s.trainable:
-                sched.wgrad(shp, x.ptr, dy_ptr, eng.grads[name + ".weight"], eng.grads[name + ".bias"] if s.bias else None, dz_index=fresh_dz)
+                sched.wgrad(shp, x.ptr, dy_ptr, eng.grads[name + ".weight"], eng.grads[name + ".bias"] if s.bias else None, dz_index=fresh_dz,
+                            groups=s.groups)
             if x.needs_grad:
                 _, wd = eng.packed[name]
-                add_dgrad(x, shp, dy_ptr, wd)
+                add_dgrad(x, shp, dy_ptr, wd, s.groups)
             if s.trainable:
                 self.bwd_marks.append((len(self.bwd), first_off[name + ".weight"]))
         sched.close(self)
@@ -692,8 +736,9 @@ class RetinaPlan(PlanBase):
             self.side.wait_stream(torch.cuda.current_stream())
             self._run(self.bwd)
         torch.cuda.synchronize()
+        # (the grouped 3x3 kernels are no tuner candidates: their launches above ignore the autotune mode, their weight gradients are left out here)
         self.autotune_wgrads((r["shp"], r["x"].ptr, r["dy_ptr"], eng.grads[r["name"] + ".weight"])
-                             for r in self.ops if r["kind"] == "conv" and r["spec"].trainable and "dy_ptr" in r)
+                             for r in self.ops if r["kind"] == "conv" and r["spec"].trainable and "dy_ptr" in r and r["spec"].groups == 1)
         self.glogits.zero_()
         self.gbbox.zero_()
 

@@ -18,6 +18,7 @@ def main():
     ap.add_argument("--px", type=int, default=800)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--body", default="resnet50")
     ap.add_argument("--reuse-rpn-targets", action="store_true", help="MEASUREMENT ONLY: prepare the RPN targets once and reuse them (the "
                     "targets are constant in this bench) - the step time that kernels for RPNTargets.prepare could reach at most; not a valid step")
     ap.add_argument("--tune-record", default="auto", help="tune record to load locked before the plan build: a path, 'none', or 'auto' = "
@@ -33,7 +34,7 @@ def main():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     rec = args.tune_record
     if rec == "auto":
-        rec = os.path.join(root, "object_detectors_amd", "tune_records", f"fasterrcnn_resnet50_bs{args.batch}_{args.px}.json")
+        rec = os.path.join(root, "object_detectors_amd", "tune_records", f"fasterrcnn_{args.body}_bs{args.batch}_{args.px}.json")
         if not os.path.exists(rec):
             rec = "none"
     if rec != "none":
@@ -44,7 +45,7 @@ def main():
     from object_detectors_amd.parallel import step_stream
     torch.cuda.set_stream(step_stream(dev))      # dependency chain above the side stream (weight gradients), as bench.py
     torch.manual_seed(0)
-    model = fasterrcnn_resnet50_fpn(num_classes=91, device=dev)
+    model = fasterrcnn_resnet50_fpn(num_classes=91, device=dev, body=args.body)
     eng = model.engine
     for sp in eng.specs:          # stable random-init residual stack (see tools/bench_retina.py)
         if sp.bn and sp.bn.endswith(".bn3"):
@@ -101,7 +102,7 @@ def main():
             det = model(imgs)
         torch.cuda.synchronize()
     de = (time.perf_counter() - t0) / args.steps
-    print(json.dumps({"bench": "fasterrcnn_resnet50_fpn" + ("_REUSED_RPN_TARGETS_not_a_valid_step" if args.reuse_rpn_targets else ""), "batch": args.batch, "px": args.px, "train_images_per_s": round(args.batch / dt, 2),
+    print(json.dumps({"bench": f"fasterrcnn_{args.body}_fpn" + ("_REUSED_RPN_TARGETS_not_a_valid_step" if args.reuse_rpn_targets else ""), "batch": args.batch, "px": args.px, "train_images_per_s": round(args.batch / dt, 2),
                       "train_ms_per_step": round(dt * 1e3, 2), "eval_images_per_s": round(args.batch / de, 2), "eval_ms_per_batch": round(de * 1e3, 2),
                       "losses_first": {k: round(float(v), 4) for k, v in l0.items()}, "losses_last": {k: round(float(v), 4) for k, v in l1.items()},
                       "detections_img0": int(det[0]["boxes"].shape[0]),
