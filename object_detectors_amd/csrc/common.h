@@ -63,6 +63,30 @@ typedef __bf16 st16_scalar_t;
 __device__ __forceinline__ float s2f(bf16_t v) { return bf2f(v); }
 __device__ __forceinline__ bf16_t f2s(float f) { return f2bf(f); }
 #endif
+// eight stored elements = one 16-byte access: as floats, and as their raw bits (element 2i in the low half of dword i)
+struct f32x8 {
+  float v[8];
+};
+__device__ __forceinline__ f32x8 unpack8(const uint4 u) {
+  f32x8 r;
+  r.v[0] = s2f((bf16_t)(u.x & 0xFFFF)); r.v[1] = s2f((bf16_t)(u.x >> 16));
+  r.v[2] = s2f((bf16_t)(u.y & 0xFFFF)); r.v[3] = s2f((bf16_t)(u.y >> 16));
+  r.v[4] = s2f((bf16_t)(u.z & 0xFFFF)); r.v[5] = s2f((bf16_t)(u.z >> 16));
+  r.v[6] = s2f((bf16_t)(u.w & 0xFFFF)); r.v[7] = s2f((bf16_t)(u.w >> 16));
+  return r;
+}
+__device__ __forceinline__ uint4 pack8_bits(const unsigned short (&v)[8]) {
+  uint4 u;
+  u.x = v[0] | ((unsigned)v[1] << 16);
+  u.y = v[2] | ((unsigned)v[3] << 16);
+  u.z = v[4] | ((unsigned)v[5] << 16);
+  u.w = v[6] | ((unsigned)v[7] << 16);
+  return u;
+}
+__device__ __forceinline__ uint4 pack8(const f32x8& r) {
+  const unsigned short b[8] = {f2s(r.v[0]), f2s(r.v[1]), f2s(r.v[2]), f2s(r.v[3]), f2s(r.v[4]), f2s(r.v[5]), f2s(r.v[6]), f2s(r.v[7])};
+  return pack8_bits(b);
+}
 typedef __attribute__((ext_vector_type(8))) st16_scalar_t st16x8_t;
 typedef __attribute__((ext_vector_type(4))) st16_scalar_t st16x4_t;
 typedef __attribute__((ext_vector_type(4))) float mi355_f32x4_t;

@@ -9,77 +9,104 @@ using namespace mi355;
 
 namespace {
 
-struct bf8 {
-  float v[8];
-};
-__device__ __forceinline__ bf8 unpack8(const uint4 u) {
-  bf8 r;
-  r.v[0] = s2f((bf16_t)(u.x & 0xFFFF)); r.v[1] = s2f((bf16_t)(u.x >> 16));
-  r.v[2] = s2f((bf16_t)(u.y & 0xFFFF)); r.v[3] = s2f((bf16_t)(u.y >> 16));
-  r.v[4] = s2f((bf16_t)(u.z & 0xFFFF)); r.v[5] = s2f((bf16_t)(u.z >> 16));
-  r.v[6] = s2f((bf16_t)(u.w & 0xFFFF)); r.v[7] = s2f((bf16_t)(u.w >> 16));
-  return r;
-}
-__device__ __forceinline__ bf8 ld8(const bf16_t* p) {
-  const uint4 u = *(const uint4*)p;
-  bf8 r;
-  r.v[0] = s2f((bf16_t)(u.x & 0xFFFF)); r.v[1] = s2f((bf16_t)(u.x >> 16));
-  r.v[2] = s2f((bf16_t)(u.y & 0xFFFF)); r.v[3] = s2f((bf16_t)(u.y >> 16));
-  r.v[4] = s2f((bf16_t)(u.z & 0xFFFF)); r.v[5] = s2f((bf16_t)(u.z >> 16));
-  r.v[6] = s2f((bf16_t)(u.w & 0xFFFF)); r.v[7] = s2f((bf16_t)(u.w >> 16));
-  return r;
-}
-__device__ __forceinline__ void st8(bf16_t* p, const bf8& r) {
-  uint4 u;
-  u.x = (unsigned)f2s(r.v[0]) | ((unsigned)f2s(r.v[1]) << 16);
-  u.y = (unsigned)f2s(r.v[2]) | ((unsigned)f2s(r.v[3]) << 16);
-  u.z = (unsigned)f2s(r.v[4]) | ((unsigned)f2s(r.v[5]) << 16);
-  u.w = (unsigned)f2s(r.v[6]) | ((unsigned)f2s(r.v[7]) << 16);
-  *(uint4*)p = u;
+__device__ __forceinline__ void add8(f32x8& a, const f32x8& b) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) a.v[k] += b.v[k];
 }
 
-// stats partials [rows][2][c_pad] -> scale/shift/mean/invstd (+ running stats, nn.BatchNorm2d momentum rule)
-__global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ partial, int rows, int c, int c_pad, double count,
-                                                          const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
-                                                          float momentum, float* __restrict__ rmean, float* __restrict__ rvar,
-                                                          float* __restrict__ ss) {
-  __shared__ double sh[8][32][2];
+// ---- training BatchNorm + LeakyReLU: every piece of its arithmetic is stated once, here.  (The MFMA epilogue EPI_BNRED in igemm_common.h
+// and the stem kernels carry their own copies of dy and xhat; tests hold them to these.)
+
+// Column fold of partial rows [rows][2][c_pad] (sum | sum of squares, or sum dy | sum dy*xhat) by 256 threads = 8 row lanes x 32 channels:
+// a thread adds rows r0 + rl, r0 + rl + 8, ... < r1 of channel `ch` (none when !load), then row lane 0 adds LDS slots 1..7 in that
+// order.  The sums are complete in the threads with rl == 0.
+template <typename T>
+__device__ __forceinline__ void bn_fold_rows(const float* __restrict__ partial, int r0, int r1, int c_pad, int ch, bool load, T& s1, T& s2) {
+  __shared__ T sh[8][32][2];
   const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5;
-  const int ch = blockIdx.x * 32 + cl;
-  double s1 = 0, s2 = 0;
-  if (ch < c)
-    for (int r = rl; r < rows; r += 8) {
-      s1 += (double)partial[(size_t)r * 2 * c_pad + ch];
-      s2 += (double)partial[(size_t)r * 2 * c_pad + c_pad + ch];
+  s1 = 0;
+  s2 = 0;
+  if (load)
+    for (int r = r0 + rl; r < r1; r += 8) {
+      s1 += (T)partial[(size_t)r * 2 * c_pad + ch];
+      s2 += (T)partial[(size_t)r * 2 * c_pad + c_pad + ch];
     }
   sh[rl][cl][0] = s1;
   sh[rl][cl][1] = s2;
   __syncthreads();
-  if (rl == 0 && ch < c) {
+  if (rl == 0)
     for (int r = 1; r < 8; ++r) {
       s1 += sh[r][cl][0];
       s2 += sh[r][cl][1];
     }
-    const double mean = s1 / count;
-    double var = s2 / count - mean * mean;
-    if (var < 0) var = 0;
-    const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float sc = gamma[ch] * invstd;
-    ss[ch] = sc;
-    ss[c + ch] = beta[ch] - (float)mean * sc;
-    ss[2 * c + ch] = (float)mean;
-    ss[3 * c + ch] = invstd;
-    if (rmean) {
-      rmean[ch] = (1.f - momentum) * rmean[ch] + momentum * (float)mean;
-      const double unb = count > 1 ? var * count / (count - 1) : var;
-      rvar[ch] = (1.f - momentum) * rvar[ch] + momentum * (float)unb;
-    }
+}
+
+// One channel from (sum, sum of squares, count): ss = scale | shift | mean | invstd (each [c]) and the running statistics by
+// nn.BatchNorm2d's momentum rule (unbiased variance)
+__device__ __forceinline__ void bn_finalize_channel(double s1, double s2, double count, int ch, int c, const float* __restrict__ gamma,
+                                                    const float* __restrict__ beta, float eps, float momentum, float* __restrict__ rmean,
+                                                    float* __restrict__ rvar, float* __restrict__ ss) {
+  const double mean = s1 / count;
+  double var = s2 / count - mean * mean;
+  if (var < 0) var = 0;
+  const float invstd = (float)(1.0 / sqrt(var + (double)eps));
+  const float sc = gamma[ch] * invstd;
+  ss[ch] = sc;
+  ss[c + ch] = beta[ch] - (float)mean * sc;
+  ss[2 * c + ch] = (float)mean;
+  ss[3 * c + ch] = invstd;
+  if (rmean) {
+    rmean[ch] = (1.f - momentum) * rmean[ch] + momentum * (float)mean;
+    const double unb = count > 1 ? var * count / (count - 1) : var;
+    rvar[ch] = (1.f - momentum) * rvar[ch] + momentum * (float)unb;
   }
+}
+
+// The per-element formulas over 8 channels (sc, sh, mu, is: the channels' rows of ss)
+// a = lrelu(z * scale + shift)
+__device__ __forceinline__ f32x8 bn_act8(const f32x8& z, const float (&sc)[8], const float (&sh)[8], float slope) {
+  f32x8 a;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const float y = z.v[k] * sc[k] + sh[k];
+    a.v[k] = y > 0.f ? y : y * slope;
+  }
+  return a;
+}
+// dy = g * lrelu'(y)
+__device__ __forceinline__ f32x8 bn_dy8(const f32x8& g, const f32x8& z, const float (&sc)[8], const float (&sh)[8], float slope) {
+  f32x8 dy;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const float y = z.v[k] * sc[k] + sh[k];
+    dy.v[k] = y > 0.f ? g.v[k] : g.v[k] * slope;
+  }
+  return dy;
+}
+__device__ __forceinline__ float bn_xhat(float z, float mu, float is) { return (z - mu) * is; }
+// dz = scale * (dy - mean(dy) - xhat * mean(dy * xhat))
+__device__ __forceinline__ f32x8 bn_dz8(const f32x8& dy, const f32x8& z, const float (&sc)[8], const float (&mu)[8], const float (&is)[8],
+                                        const float (&m1)[8], const float (&m2)[8]) {
+  f32x8 dz;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) dz.v[k] = sc[k] * (dy.v[k] - m1[k] - bn_xhat(z.v[k], mu[k], is[k]) * m2[k]);
+  return dz;
+}
+
+// stats partials [rows][2][c_pad] -> scale/shift/mean/invstd (+ running stats)
+__global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ partial, int rows, int c, int c_pad, double count,
+                                                          const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                          float momentum, float* __restrict__ rmean, float* __restrict__ rvar,
+                                                          float* __restrict__ ss) {
+  const int ch = blockIdx.x * 32 + (threadIdx.x & 31);
+  double s1, s2;
+  bn_fold_rows<double>(partial, 0, rows, c_pad, ch, ch < c, s1, s2);
+  if (threadIdx.x < 32 && ch < c) bn_finalize_channel(s1, s2, count, ch, c, gamma, beta, eps, momentum, rmean, rvar, ss);
 }
 
 // The same finalisation in ONE launch for 32 < rows <= 8192 (all but the three 320-px layers of YOLOv3 at batch 32 / 640 px): 8 channels x 128 row parts
 // per workgroup, every thread's loads independent (<= 16 rows each, 4 in flight), double accumulation, fixed-order LDS fold.  The
-// two-launch form below (bn_partial_kernel + bn_finalize_kernel) costs 6 + 7 us of pure launch latency per layer in the forward chain
+// two-launch form (bn_partial_kernel + bn_finalize_kernel) costs 6 + 7 us of pure launch latency per layer in the forward chain
 // conv -> statistics -> activation, where nothing else can run.
 __global__ __launch_bounds__(1024) void bn_finalize_wide_kernel(const float* __restrict__ partial, int rows, int c, int c_pad, double count,
                                                                 const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
@@ -131,72 +158,34 @@ __global__ __launch_bounds__(1024) void bn_finalize_wide_kernel(const float* __r
       s1 += sh[q][cl][0];
       s2 += sh[q][cl][1];
     }
-    const double mean = s1 / count;
-    double var = s2 / count - mean * mean;
-    if (var < 0) var = 0;
-    const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float sc = gamma[ch] * invstd;
-    ss[ch] = sc;
-    ss[c + ch] = beta[ch] - (float)mean * sc;
-    ss[2 * c + ch] = (float)mean;
-    ss[3 * c + ch] = invstd;
-    if (rmean) {
-      rmean[ch] = (1.f - momentum) * rmean[ch] + momentum * (float)mean;
-      const double unb = count > 1 ? var * count / (count - 1) : var;
-      rvar[ch] = (1.f - momentum) * rvar[ch] + momentum * (float)unb;
-    }
+    bn_finalize_channel(s1, s2, count, ch, c, gamma, beta, eps, momentum, rmean, rvar, ss);
   }
 }
 
-// stage 1 of the statistics reduction for layers with many pixel tiles: [rows][2][c_pad] -> [chunks][2][c_pad]
-__global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict__ partial, int rows, int c_pad, int chunk,
+// Float fold of row chunk blockIdx.y: [rows][2][c_pad] -> out[chunks][2][c_out], channels < c_out.  Stage 1 of every reduction over
+// many rows (64 chunks, c_out = c_pad), and with one chunk and c_out = c the final stage of the fused BN-backward reduction
+// (sums[2 * c]: sum dy | sum dy*xhat).
+__global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict__ partial, int rows, int c_pad, int chunk, int c_out,
                                                          float* __restrict__ out) {
-  __shared__ float sh[8][32][2];
-  const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5;
-  const int ch = blockIdx.x * 32 + cl;
-  const int r0 = blockIdx.y * chunk, r1 = min(rows, r0 + chunk);
-  float s1 = 0.f, s2 = 0.f;
-  if (ch < c_pad)
-    for (int r = r0 + rl; r < r1; r += 8) {
-      s1 += partial[(size_t)r * 2 * c_pad + ch];
-      s2 += partial[(size_t)r * 2 * c_pad + c_pad + ch];
-    }
-  sh[rl][cl][0] = s1;
-  sh[rl][cl][1] = s2;
-  __syncthreads();
-  if (rl == 0 && ch < c_pad) {
-    for (int r = 1; r < 8; ++r) {
-      s1 += sh[r][cl][0];
-      s2 += sh[r][cl][1];
-    }
-    out[(size_t)blockIdx.y * 2 * c_pad + ch] = s1;
-    out[(size_t)blockIdx.y * 2 * c_pad + c_pad + ch] = s2;
+  const int ch = blockIdx.x * 32 + (threadIdx.x & 31);
+  const int r0 = blockIdx.y * chunk;
+  float s1, s2;
+  bn_fold_rows<float>(partial, r0, min(rows, r0 + chunk), c_pad, ch, ch < c_out, s1, s2);
+  if (threadIdx.x < 32 && ch < c_out) {
+    out[(size_t)blockIdx.y * 2 * c_out + ch] = s1;
+    out[(size_t)blockIdx.y * 2 * c_out + c_out + ch] = s2;
   }
 }
 
-// SyncBN forward: the same fold as bn_finalize_kernel's first half (double accumulation over the partial rows), but the per-channel
-// sums leave as doubles so that the cross-rank all-reduce and the finalisation keep the local path's precision
-// (sums64 [2][c_pad]: sum x | sum x*x)
+// SyncBN forward: bn_finalize_kernel's fold, but the per-channel sums leave as doubles so that the cross-rank all-reduce and the
+// finalisation keep the local path's precision (sums64 [2][c_pad]: sum x | sum x*x; the pad channels fold nothing and store 0)
 __global__ __launch_bounds__(256) void bn_fold_f64_kernel(const float* __restrict__ partial, int rows, int c, int c_pad, double* __restrict__ sums64) {
-  __shared__ double sh[8][32][2];
-  const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5;
-  const int ch = blockIdx.x * 32 + cl;
-  double s1 = 0, s2 = 0;
-  if (ch < c)
-    for (int r = rl; r < rows; r += 8) {
-      s1 += (double)partial[(size_t)r * 2 * c_pad + ch];
-      s2 += (double)partial[(size_t)r * 2 * c_pad + c_pad + ch];
-    }
-  sh[rl][cl][0] = s1;
-  sh[rl][cl][1] = s2;
-  __syncthreads();
-  if (rl == 0 && ch < c_pad) {
-    for (int r = 1; r < 8; ++r) {
-      s1 += sh[r][cl][0];
-      s2 += sh[r][cl][1];
-    }
-    sums64[ch] = ch < c ? s1 : 0.0;
-    sums64[c_pad + ch] = ch < c ? s2 : 0.0;
+  const int ch = blockIdx.x * 32 + (threadIdx.x & 31);
+  double s1, s2;
+  bn_fold_rows<double>(partial, 0, rows, c_pad, ch, ch < c, s1, s2);
+  if (threadIdx.x < 32 && ch < c_pad) {
+    sums64[ch] = s1;
+    sums64[c_pad + ch] = s2;
   }
 }
 
@@ -204,48 +193,10 @@ __global__ __launch_bounds__(256) void bn_finalize_f64_kernel(const double* __re
                                                               const float* __restrict__ gamma, const float* __restrict__ beta, float eps, float momentum,
                                                               float* __restrict__ rmean, float* __restrict__ rvar, float* __restrict__ ss) {
   const int ch = blockIdx.x * 256 + threadIdx.x;
-  if (ch >= c) return;
-  const double mean = sums64[ch] / count;
-  double var = sums64[c_pad + ch] / count - mean * mean;
-  if (var < 0) var = 0;
-  const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-  const float sc = gamma[ch] * invstd;
-  ss[ch] = sc;
-  ss[c + ch] = beta[ch] - (float)mean * sc;
-  ss[2 * c + ch] = (float)mean;
-  ss[3 * c + ch] = invstd;
-  if (rmean) {
-    rmean[ch] = (1.f - momentum) * rmean[ch] + momentum * (float)mean;
-    const double unb = count > 1 ? var * count / (count - 1) : var;
-    rvar[ch] = (1.f - momentum) * rvar[ch] + momentum * (float)unb;
-  }
+  if (ch < c) bn_finalize_channel(sums64[ch], sums64[c_pad + ch], count, ch, c, gamma, beta, eps, momentum, rmean, rvar, ss);
 }
 
-// final stage of the fused BN-backward reduction: [rows<=256][2][c_pad] -> sums[2*c] (sum dy | sum dy*xhat)
-__global__ __launch_bounds__(256) void bn_bwd_sum_kernel(const float* __restrict__ partial, int rows, int c, int c_pad, float* __restrict__ sums) {
-  __shared__ float sh[8][32][2];
-  const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5;
-  const int ch = blockIdx.x * 32 + cl;
-  float s1 = 0.f, s2 = 0.f;
-  if (ch < c)
-    for (int r = rl; r < rows; r += 8) {
-      s1 += partial[(size_t)r * 2 * c_pad + ch];
-      s2 += partial[(size_t)r * 2 * c_pad + c_pad + ch];
-    }
-  sh[rl][cl][0] = s1;
-  sh[rl][cl][1] = s2;
-  __syncthreads();
-  if (rl == 0 && ch < c) {
-    for (int r = 1; r < 8; ++r) {
-      s1 += sh[r][cl][0];
-      s2 += sh[r][cl][1];
-    }
-    sums[ch] = s1;
-    sums[c + ch] = s2;
-  }
-}
-
-// eval-mode scale/shift from running stats
+// eval-mode scale/shift from running stats (float arithmetic of its own: no batch statistics, no double)
 __global__ void bn_eval_kernel(int c, const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ rmean,
                                const float* __restrict__ rvar, float eps, float* __restrict__ ss) {
   const int ch = blockIdx.x * blockDim.x + threadIdx.x;
@@ -256,34 +207,6 @@ __global__ void bn_eval_kernel(int c, const float* __restrict__ gamma, const flo
   ss[c + ch] = beta[ch] - rmean[ch] * sc;
   ss[2 * c + ch] = rmean[ch];
   ss[3 * c + ch] = invstd;
-}
-
-// a = lrelu(z*scale+shift) [+ residual]
-__global__ __launch_bounds__(256) void bn_act_fwd_kernel(const bf16_t* __restrict__ z, int z_ld, const float* __restrict__ ss, int c,
-                                                         long long pixels, float slope, const bf16_t* __restrict__ res, int res_ld,
-                                                         bf16_t* __restrict__ out, int out_ld) {
-  const int groups = c >> 3;
-  const long long total = pixels * groups;
-  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    const long long m = i / groups;
-    const int c0 = (int)(i - m * groups) << 3;
-    bf8 v = ld8(z + m * z_ld + c0);
-    const float4 sa = *(const float4*)(ss + c0), sb = *(const float4*)(ss + c0 + 4);
-    const float4 ha = *(const float4*)(ss + c + c0), hb = *(const float4*)(ss + c + c0 + 4);
-    const float sc[8] = {sa.x, sa.y, sa.z, sa.w, sb.x, sb.y, sb.z, sb.w};
-    const float sh[8] = {ha.x, ha.y, ha.z, ha.w, hb.x, hb.y, hb.z, hb.w};
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const float y = v.v[k] * sc[k] + sh[k];
-      v.v[k] = y > 0.f ? y : y * slope;
-    }
-    if (res) {
-      const bf8 r = ld8(res + m * res_ld + c0);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) v.v[k] += r.v[k];
-    }
-    st8(out + m * out_ld + c0, v);
-  }
 }
 
 // per-channel sums of dy and dy*xhat, dy = (g1 [+ g2]) * lrelu'(y).  Block = (c/8) channel groups x
@@ -321,19 +244,14 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const bf16_t* __rest
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      bf8 g = unpack8(gu[u]);
-      if (g2) {
-        const bf8 h = unpack8(hu[u]);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) g.v[k] += h.v[k];
-      }
-      const bf8 zz = unpack8(zu[u]);
+      f32x8 g = unpack8(gu[u]);
+      if (g2) add8(g, unpack8(hu[u]));
+      const f32x8 zz = unpack8(zu[u]);
+      const f32x8 dy = bn_dy8(g, zz, sc, sh, slope);   // zero-filled tail lanes contribute dy = 0
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        const float y = zz.v[k] * sc[k] + sh[k];
-        const float dy = y > 0.f ? g.v[k] : g.v[k] * slope;   // zero-filled tail lanes contribute dy = 0
-        a1[k] += dy;
-        a2[k] += dy * ((zz.v[k] - mu[k]) * is[k]);
+        a1[k] += dy.v[k];
+        a2[k] += dy.v[k] * bn_xhat(zz.v[k], mu[k], is[k]);
       }
     }
   }
@@ -394,55 +312,40 @@ __global__ __launch_bounds__(256) void bn_bwd_fold_rows_kernel(const float* __re
   }
 }
 
-// dz = scale * (dy - mean(dy) - xhat * mean(dy*xhat));  also dgamma/dbeta (block 0)
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const bf16_t* __restrict__ g1, int g1_ld, const bf16_t* __restrict__ g2, int g2_ld,
-                                                           const bf16_t* __restrict__ z, int z_ld, const float* __restrict__ ss,
-                                                           const float* __restrict__ sums, int c, long long pixels, float slope,
-                                                           bf16_t* __restrict__ dz, int dz_ld, float* __restrict__ dgamma,
-                                                           float* __restrict__ dbeta) {
-  const int groups = c >> 3;
-  const long long total = pixels * groups;
-  const float inv = 1.0f / (float)pixels;
-  if (blockIdx.x == 0 && dgamma)
-    for (int ch = threadIdx.x; ch < c; ch += 256) {
-      dbeta[ch] += sums[ch];
-      dgamma[ch] += sums[c + ch];
-    }
-  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    const long long m = i / groups;
-    const int c0 = (int)(i - m * groups) << 3;
-    bf8 g = ld8(g1 + m * g1_ld + c0);
-    if (g2) {
-      const bf8 h = ld8(g2 + m * g2_ld + c0);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) g.v[k] += h.v[k];
-    }
-    const bf8 zz = ld8(z + m * z_ld + c0);
-    bf8 o;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int ch = c0 + k;
-      const float sc = ss[ch], sh = ss[c + ch], mu = ss[2 * c + ch], is = ss[3 * c + ch];
-      const float y = zz.v[k] * sc + sh;
-      const float dy = y > 0.f ? g.v[k] : g.v[k] * slope;
-      const float xh = (zz.v[k] - mu) * is;
-      o.v[k] = sc * (dy - sums[ch] * inv - xh * sums[c + ch] * inv);
-    }
-    st8(dz + m * dz_ld + c0, o);
+// Element mapping of the two elementwise passes: a thread keeps ONE group of 8 channels and walks over pixels, so the per-channel
+// constants live in registers (re-loading them per 16 bytes of data filled the vector-memory pipe with table loads: 3.6 TB/s against
+// 5.4 for the forward pass).  A workgroup = `groups` channel groups x 256 / groups pixel lanes; groups = c / 8 up to 256, beyond
+// that blockIdx.y picks a slab of 256 groups.  gshift = log2(groups) when groups is a power of two (every Darknet layer), else -1:
+// then 256 % groups threads and the channel groups past c in the last slab are idle (!live) and leave at once: neither kernel has a barrier.
+struct RowLane {
+  int c0, pl, npl;
+  bool live;
+};
+__device__ __forceinline__ RowLane row_lane(int c, int groups, int gshift) {
+  RowLane t;
+  int gl;
+  if (gshift >= 0) {
+    gl = threadIdx.x & (groups - 1);
+    t.pl = threadIdx.x >> gshift;
+    t.npl = 256 >> gshift;
+  } else {
+    gl = threadIdx.x % groups;
+    t.pl = threadIdx.x / groups;
+    t.npl = 256 / groups;
   }
+  t.c0 = (blockIdx.y * groups + gl) << 3;
+  t.live = t.pl < t.npl && t.c0 < c;
+  return t;
 }
 
-// Row-mapped forms of the two elementwise passes (channels/8 a power of two <= 256, every Darknet layer): a thread keeps ONE
-// group of 8 channels and walks over pixels, so the per-channel constants live in registers.  The grid-stride forms above
-// re-load 32 (forward) / 48 (backward) table dwords per 16 bytes of data and pay a 64-bit division per element group;
-// their table loads, not the tensor, filled the vector-memory pipe (3.6 TB/s against 5.4 for the forward pass).
+// a = lrelu(z*scale+shift) [+ residual]
 template <int U>
 __global__ __launch_bounds__(256) void bn_act_fwd_rows_kernel(const bf16_t* __restrict__ z, int z_ld, const float* __restrict__ ss, int c,
                                                               long long pixels, float slope, const bf16_t* __restrict__ res, int res_ld,
-                                                              bf16_t* __restrict__ out, int out_ld, int pix_per_block, int gshift) {
-  const int groups = 1 << gshift, npl = 256 >> gshift;
-  const int gl = threadIdx.x & (groups - 1), pl = threadIdx.x >> gshift;
-  const int c0 = gl << 3;
+                                                              bf16_t* __restrict__ out, int out_ld, int pix_per_block, int groups, int gshift) {
+  const RowLane t = row_lane(c, groups, gshift);
+  if (!t.live) return;
+  const int c0 = t.c0, npl = t.npl;
   float sc[8], sh[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
@@ -450,7 +353,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_rows_kernel(const bf16_t* __re
     sh[k] = ss[c + c0 + k];
   }
   const long long mA = (long long)blockIdx.x * pix_per_block, mB = min(pixels, mA + pix_per_block);
-  for (long long m = mA + pl; m < mB; m += U * npl) {
+  for (long long m = mA + t.pl; m < mB; m += U * npl) {
     uint4 zu[U], ru[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -464,37 +367,29 @@ __global__ __launch_bounds__(256) void bn_act_fwd_rows_kernel(const bf16_t* __re
     for (int u = 0; u < U; ++u) {
       const long long mm = m + (long long)u * npl;
       if (mm >= mB) break;
-      bf8 v = unpack8(zu[u]);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const float y = v.v[k] * sc[k] + sh[k];
-        v.v[k] = y > 0.f ? y : y * slope;
-      }
-      if (res) {
-        const bf8 r = unpack8(ru[u]);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v.v[k] += r.v[k];
-      }
-      st8(out + mm * out_ld + c0, v);
+      f32x8 v = bn_act8(unpack8(zu[u]), sc, sh, slope);
+      if (res) add8(v, unpack8(ru[u]));
+      *(uint4*)(out + mm * out_ld + c0) = pack8(v);
     }
   }
 }
 
+// dz = scale * (dy - mean(dy) - xhat * mean(dy*xhat));  also dgamma/dbeta (one workgroup)
 template <int U>
 __global__ __launch_bounds__(256) void bn_bwd_apply_rows_kernel(const bf16_t* __restrict__ g1, int g1_ld, const bf16_t* __restrict__ g2, int g2_ld,
                                                                 const bf16_t* __restrict__ z, int z_ld, const float* __restrict__ ss,
                                                                 const float* __restrict__ sums, int c, long long pixels, float slope,
                                                                 bf16_t* __restrict__ dz, int dz_ld, float* __restrict__ dgamma,
-                                                                float* __restrict__ dbeta, int pix_per_block, int gshift) {
-  const int groups = 1 << gshift, npl = 256 >> gshift;
-  const int gl = threadIdx.x & (groups - 1), pl = threadIdx.x >> gshift;
-  const int c0 = gl << 3;
+                                                                float* __restrict__ dbeta, int pix_per_block, int groups, int gshift) {
+  const RowLane t = row_lane(c, groups, gshift);
+  const int c0 = t.c0, npl = t.npl;
   const float inv = 1.0f / (float)pixels;
-  if (blockIdx.x == 0 && dgamma)
+  if (blockIdx.x == 0 && blockIdx.y == 0 && dgamma)
     for (int ch = threadIdx.x; ch < c; ch += 256) {
       dbeta[ch] += sums[ch];
       dgamma[ch] += sums[c + ch];
     }
+  if (!t.live) return;
   float sc[8], sh[8], mu[8], is[8], m1[8], m2[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
@@ -506,7 +401,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_rows_kernel(const bf16_t* __
     m2[k] = sums[c + c0 + k] * inv;
   }
   const long long mA = (long long)blockIdx.x * pix_per_block, mB = min(pixels, mA + pix_per_block);
-  for (long long m = mA + pl; m < mB; m += U * npl) {
+  for (long long m = mA + t.pl; m < mB; m += U * npl) {
     uint4 gu[U], hu[U], zu[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -521,22 +416,10 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_rows_kernel(const bf16_t* __
     for (int u = 0; u < U; ++u) {
       const long long mm = m + (long long)u * npl;
       if (mm >= mB) break;
-      bf8 g = unpack8(gu[u]);
-      if (g2) {
-        const bf8 h = unpack8(hu[u]);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) g.v[k] += h.v[k];
-      }
-      const bf8 zz = unpack8(zu[u]);
-      bf8 o;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const float y = zz.v[k] * sc[k] + sh[k];
-        const float dy = y > 0.f ? g.v[k] : g.v[k] * slope;
-        const float xh = (zz.v[k] - mu[k]) * is[k];
-        o.v[k] = sc[k] * (dy - m1[k] - xh * m2[k]);
-      }
-      st8(dz + mm * dz_ld + c0, o);
+      f32x8 g = unpack8(gu[u]);
+      if (g2) add8(g, unpack8(hu[u]));
+      const f32x8 zz = unpack8(zu[u]);
+      *(uint4*)(dz + mm * dz_ld + c0) = pack8(bn_dz8(bn_dy8(g, zz, sc, sh, slope), zz, sc, mu, is, m1, m2));
     }
   }
 }
@@ -562,18 +445,14 @@ __global__ __launch_bounds__(256) void upsample2x_bwd_kernel(const bf16_t* __res
     const int g = (int)(i % groups);
     const long long p = i / groups;
     const int x = (int)(p % w), y = (int)((p / w) % h), b = (int)(p / ((long long)w * h));
-    bf8 a;
+    f32x8 a;
 #pragma unroll
     for (int k = 0; k < 8; ++k) a.v[k] = 0.f;
 #pragma unroll
     for (int dy = 0; dy < 2; ++dy)
 #pragma unroll
-      for (int dx = 0; dx < 2; ++dx) {
-        const bf8 v = ld8(gq + ((long long)(b * 2 * h + 2 * y + dy) * (2 * w) + 2 * x + dx) * g_ld + g * 8);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) a.v[k] += v.v[k];
-      }
-    st8(out + p * out_ld + g * 8, a);
+      for (int dx = 0; dx < 2; ++dx) add8(a, unpack8(*(const uint4*)(gq + ((long long)(b * 2 * h + 2 * y + dy) * (2 * w) + 2 * x + dx) * g_ld + g * 8)));
+    *(uint4*)(out + p * out_ld + g * 8) = pack8(a);
   }
 }
 
@@ -585,11 +464,9 @@ __global__ __launch_bounds__(256) void add_kernel(const bf16_t* __restrict__ a, 
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const long long m = i / groups;
     const int c0 = (int)(i - m * groups) << 3;
-    bf8 v = ld8(a + m * a_ld + c0);
-    const bf8 w = ld8(b + m * b_ld + c0);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v.v[k] += w.v[k];
-    st8(out + m * out_ld + c0, v);
+    f32x8 v = unpack8(*(const uint4*)(a + m * a_ld + c0));
+    add8(v, unpack8(*(const uint4*)(b + m * b_ld + c0)));
+    *(uint4*)(out + m * out_ld + c0) = pack8(v);
   }
 }
 
@@ -618,13 +495,18 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const void* __restric
   }
 }
 
-// row-mapped elementwise forms: channels/8 a power of two <= 256; 16 pixels per pixel lane, at most 16384 workgroups
-inline bool rows_form(int c, long long pixels, int* gshift, int* ppb, int* blocks) {
-  const int groups = c / 8;
-  if (c <= 0 || c % 8 != 0 || groups > 256 || (groups & (groups - 1)) != 0) return false;
+// geometry of the two elementwise passes (row_lane): 16 pixels per pixel lane, at most 16384 workgroups per channel slab
+struct RowsGeom {
+  int groups, gshift, slabs, ppb, blocks;
+};
+inline bool rows_geom(int c, long long pixels, RowsGeom* g) {
+  if (c <= 0 || c % 8 != 0 || pixels <= 0) return false;
+  g->groups = min(c / 8, 256);
+  g->slabs = (c / 8 + g->groups - 1) / g->groups;
   int sh = 0;
-  while ((1 << sh) < groups) ++sh;
-  const int npl = 256 / groups;
+  while ((1 << sh) < g->groups) ++sh;
+  g->gshift = (1 << sh) == g->groups ? sh : -1;
+  const int npl = 256 / g->groups;
   long long per = (long long)npl * 16;
   long long nb = (pixels + per - 1) / per;
   if (nb > 16384) {
@@ -632,9 +514,8 @@ inline bool rows_form(int c, long long pixels, int* gshift, int* ppb, int* block
     nb = (pixels + per - 1) / per;
   }
   if (per > 0x7FFFFFFFll) return false;
-  *gshift = sh;
-  *ppb = (int)per;
-  *blocks = (int)nb;
+  g->ppb = (int)per;
+  g->blocks = (int)nb;
   return true;
 }
 
@@ -722,6 +603,21 @@ __global__ __launch_bounds__(256) void nonfinite_kernel(const float* __restrict_
 
 #endif
 
+#if !MI355_F16
+// rows > 256: two stages (deterministic).  64 row chunks are reduced in parallel into the 64 spare rows behind the partials, which the
+// caller's fold then reads instead.  (One launch whose last workgroup per channel slab finalises was measured too: the device-scope
+// stores / loads it needs make it 15 us against 7 + 6 us for the two launches, 1011-1017 vs 1020 images/s on the same box; with
+// __threadfence() it writes the L2 back: -5 %.)
+static void bn_fold_many_rows(const float*& partial, int32_t& rows, int c_pad, void* stream) {
+  if (rows <= 256) return;
+  const int chunks = 64, chunk = (rows + chunks - 1) / chunks;
+  float* spare = const_cast<float*>(partial) + (size_t)rows * 2 * c_pad;
+  hipLaunchKernelGGL(bn_partial_kernel, dim3((c_pad + 31) / 32, chunks), dim3(256), 0, S(stream), partial, rows, c_pad, chunk, c_pad, spare);
+  partial = spare;
+  rows = chunks;
+}
+#endif
+
 extern "C" {
 
 #if !MI355_F16
@@ -733,16 +629,7 @@ int mi355det_bn_finalize(const float* stats, int32_t rows, int32_t c, int32_t c_
                        momentum, running_mean, running_var, scale_shift);
     return check_launch("bn_finalize");
   }
-  if (rows > 256) {
-    // two stages (deterministic): 64 row-chunks reduced in parallel into the 64 spare rows behind the partials.  (One launch whose
-    // last workgroup per channel slab finalises was measured too: the device-scope stores / loads it needs make it 15 us against
-    // 7 + 6 us for the two launches, 1011-1017 vs 1020 images/s on the same box; with __threadfence() it writes the L2 back: -5 %.)
-    const int chunks = 64, chunk = (rows + chunks - 1) / chunks;
-    float* scratch = const_cast<float*>(stats) + (size_t)rows * 2 * c_pad;
-    hipLaunchKernelGGL(bn_partial_kernel, dim3((c_pad + 31) / 32, chunks), dim3(256), 0, S(stream), stats, rows, c_pad, chunk, scratch);
-    stats = scratch;
-    rows = chunks;
-  }
+  bn_fold_many_rows(stats, rows, c_pad, stream);
   hipLaunchKernelGGL(bn_finalize_kernel, dim3((c + 31) / 32), dim3(256), 0, S(stream), stats, rows, c, c_pad, (double)count, gamma, beta, eps,
                      momentum, running_mean, running_var, scale_shift);
   return check_launch("bn_finalize");
@@ -750,26 +637,14 @@ int mi355det_bn_finalize(const float* stats, int32_t rows, int32_t c, int32_t c_
 
 int mi355det_bn_bwd_sum_partials(const float* partials, int32_t rows, int32_t c, int32_t c_pad, float* sums, void* stream) {
   if (c <= 0 || rows <= 0 || c_pad < c) return fail(MI355DET_EINVAL, "%s: bad arguments", "bn_bwd_sum_partials");
-  if (rows > 256) {
-    const int chunks = 64, chunk = (rows + chunks - 1) / chunks;
-    float* scratch = const_cast<float*>(partials) + (size_t)rows * 2 * c_pad;     // the 64 spare rows behind the partials
-    hipLaunchKernelGGL(bn_partial_kernel, dim3((c_pad + 31) / 32, chunks), dim3(256), 0, S(stream), partials, rows, c_pad, chunk, scratch);
-    partials = scratch;
-    rows = chunks;
-  }
-  hipLaunchKernelGGL(bn_bwd_sum_kernel, dim3((c + 31) / 32), dim3(256), 0, S(stream), partials, rows, c, c_pad, sums);
+  bn_fold_many_rows(partials, rows, c_pad, stream);
+  hipLaunchKernelGGL(bn_partial_kernel, dim3((c + 31) / 32), dim3(256), 0, S(stream), partials, rows, c_pad, rows, c, sums);
   return check_launch("bn_bwd_sum_partials");
 }
 
 int mi355det_bn_fold_partials_f64(const float* stats, int32_t rows, int32_t c, int32_t c_pad, double* sums64, void* stream) {
   if (c <= 0 || rows <= 0 || c_pad < c || !stats || !sums64) return fail(MI355DET_EINVAL, "%s: bad arguments", "bn_fold_partials_f64");
-  if (rows > 256) {
-    const int chunks = 64, chunk = (rows + chunks - 1) / chunks;
-    float* scratch = const_cast<float*>(stats) + (size_t)rows * 2 * c_pad;       // the 64 spare rows behind the partials, as bn_finalize
-    hipLaunchKernelGGL(bn_partial_kernel, dim3((c_pad + 31) / 32, chunks), dim3(256), 0, S(stream), stats, rows, c_pad, chunk, scratch);
-    stats = scratch;
-    rows = chunks;
-  }
+  bn_fold_many_rows(stats, rows, c_pad, stream);
   hipLaunchKernelGGL(bn_fold_f64_kernel, dim3((c_pad + 31) / 32), dim3(256), 0, S(stream), stats, rows, c, c_pad, sums64);
   return check_launch("bn_fold_partials_f64");
 }
@@ -793,15 +668,10 @@ int mi355det_bn_eval_scale_shift(int32_t c, const float* gamma, const float* bet
 
 int mi355det_bn_act_fwd(const void* z, int32_t z_ld, const float* scale_shift, int32_t c, int64_t pixels, float slope, const void* residual,
                         int32_t res_ld, void* out, int32_t out_ld, void* stream) {
-  if (c <= 0 || c % 8 != 0 || pixels <= 0) return fail(MI355DET_EINVAL, "%s: channels must be a multiple of 8", "bn_act_fwd");
-  int gshift, ppb, blocks;
-  if (rows_form(c, pixels, &gshift, &ppb, &blocks)) {
-    hipLaunchKernelGGL(bn_act_fwd_rows_kernel<4>, dim3(blocks), dim3(256), 0, S(stream), (const bf16_t*)z, z_ld, scale_shift, c, (long long)pixels,
-                       slope, (const bf16_t*)residual, res_ld, (bf16_t*)out, out_ld, ppb, gshift);
-    return check_launch("bn_act_fwd");
-  }
-  hipLaunchKernelGGL(bn_act_fwd_kernel, dim3(grid_for(pixels * (c / 8))), dim3(256), 0, S(stream), (const bf16_t*)z, z_ld, scale_shift, c,
-                     (long long)pixels, slope, (const bf16_t*)residual, res_ld, (bf16_t*)out, out_ld);
+  RowsGeom g;
+  if (!rows_geom(c, pixels, &g)) return fail(MI355DET_EINVAL, "%s: channels must be a multiple of 8", "bn_act_fwd");
+  hipLaunchKernelGGL(bn_act_fwd_rows_kernel<4>, dim3(g.blocks, g.slabs), dim3(256), 0, S(stream), (const bf16_t*)z, z_ld, scale_shift, c,
+                     (long long)pixels, slope, (const bf16_t*)residual, res_ld, (bf16_t*)out, out_ld, g.ppb, g.groups, g.gshift);
   return check_launch("bn_act_fwd");
 }
 
@@ -871,15 +741,11 @@ int mi355det_bn_act_bwd_apply(const void* g1, int32_t g1_ld, const void* g2, int
                               const float* sums, const float* gamma, int32_t c, int64_t pixels, float slope, void* dz, int32_t dz_ld, float* dgamma,
                               float* dbeta, void* stream) {
   (void)gamma;
-  if (c <= 0 || c % 8 != 0 || pixels <= 0) return fail(MI355DET_EINVAL, "%s: channels must be a multiple of 8", "bn_act_bwd_apply");
-  int gshift, ppb, blocks;
-  if (rows_form(c, pixels, &gshift, &ppb, &blocks)) {
-    hipLaunchKernelGGL(bn_bwd_apply_rows_kernel<4>, dim3(blocks), dim3(256), 0, S(stream), (const bf16_t*)g1, g1_ld, (const bf16_t*)g2, g2_ld,
-                       (const bf16_t*)z, z_ld, scale_shift, sums, c, (long long)pixels, slope, (bf16_t*)dz, dz_ld, dgamma, dbeta, ppb, gshift);
-    return check_launch("bn_act_bwd_apply");
-  }
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(pixels * (c / 8))), dim3(256), 0, S(stream), (const bf16_t*)g1, g1_ld, (const bf16_t*)g2,
-                     g2_ld, (const bf16_t*)z, z_ld, scale_shift, sums, c, (long long)pixels, slope, (bf16_t*)dz, dz_ld, dgamma, dbeta);
+  RowsGeom g;
+  if (!rows_geom(c, pixels, &g)) return fail(MI355DET_EINVAL, "%s: channels must be a multiple of 8", "bn_act_bwd_apply");
+  hipLaunchKernelGGL(bn_bwd_apply_rows_kernel<4>, dim3(g.blocks, g.slabs), dim3(256), 0, S(stream), (const bf16_t*)g1, g1_ld, (const bf16_t*)g2, g2_ld,
+                     (const bf16_t*)z, z_ld, scale_shift, sums, c, (long long)pixels, slope, (bf16_t*)dz, dz_ld, dgamma, dbeta, g.ppb, g.groups,
+                     g.gshift);
   return check_launch("bn_act_bwd_apply");
 }
 

@@ -416,7 +416,7 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, f32x4_t (&a
               const int k = q * 2 + hsel;
               const float gv = s2f((bf16_t)(hsel ? gi[q] >> 16 : gi[q] & 0xFFFF));
               const float zv = s2f((bf16_t)(hsel ? zi[q] >> 16 : zi[q] & 0xFFFF));
-              const float yv = zv * bn_sc[k] + bn_sh[k];
+              const float yv = zv * bn_sc[k] + bn_sh[k];                  // dy, xhat: a copy of bn_dy8 / bn_xhat (elem_kernels.hip), held to them by tests
               const float dy = yv > 0.f ? gv : gv * p.slope;
               bn_a1[k] += dy;
               bn_a2[k] += dy * ((zv - bn_mu[k]) * bn_is[k]);

@@ -16,26 +16,6 @@ using namespace mi355;
 
 namespace {
 
-struct bf8 {
-  float v[8];
-};
-__device__ __forceinline__ bf8 unpack8(const uint4 u) {
-  bf8 r;
-  r.v[0] = bf2f((bf16_t)(u.x & 0xFFFF)); r.v[1] = bf2f((bf16_t)(u.x >> 16));
-  r.v[2] = bf2f((bf16_t)(u.y & 0xFFFF)); r.v[3] = bf2f((bf16_t)(u.y >> 16));
-  r.v[4] = bf2f((bf16_t)(u.z & 0xFFFF)); r.v[5] = bf2f((bf16_t)(u.z >> 16));
-  r.v[6] = bf2f((bf16_t)(u.w & 0xFFFF)); r.v[7] = bf2f((bf16_t)(u.w >> 16));
-  return r;
-}
-__device__ __forceinline__ uint4 pack8(const bf8& r) {
-  uint4 u;
-  u.x = (unsigned)f2bf(r.v[0]) | ((unsigned)f2bf(r.v[1]) << 16);
-  u.y = (unsigned)f2bf(r.v[2]) | ((unsigned)f2bf(r.v[3]) << 16);
-  u.z = (unsigned)f2bf(r.v[4]) | ((unsigned)f2bf(r.v[5]) << 16);
-  u.w = (unsigned)f2bf(r.v[6]) | ((unsigned)f2bf(r.v[7]) << 16);
-  return u;
-}
-
 inline int grid_for(long long total) { return (int)min((long long)256 * 16, max(1ll, (total + 255) / 256)); }
 
 // one thread per (output pixel, 8-wide k chunk): k = (kh*ks + kw)*c + ch.  The k -> (kh, kw, ch) decode is a per-block LDS table
@@ -64,7 +44,7 @@ __global__ __launch_bounds__(256) void im2col_nchw_kernel(const float* __restric
     const int oy = (int)(r / wo), ox = (int)(r - (r / wo) * wo);
     const int iy0 = oy * stride - pad, ix0 = ox * stride - pad;
     const float* ib = img + (size_t)b * c * h * w;
-    bf8 rr;
+    f32x8 rr;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int e = ktab[q * 8 + j];
@@ -91,7 +71,7 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const bf16_t* __restr
     const int g = (int)(i % groups);
     const long long p = i / groups;
     const int ox = (int)(p % wo), oy = (int)((p / wo) % ho), b = (int)(p / ((long long)wo * ho));
-    bf8 m;
+    f32x8 m;
 #pragma unroll
     for (int j = 0; j < 8; ++j) m.v[j] = -__builtin_inff();
     for (int kh = 0; kh < 3; ++kh) {
@@ -100,7 +80,7 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const bf16_t* __restr
       for (int kw = 0; kw < 3; ++kw) {
         const int ix = 2 * ox - 1 + kw;
         if (ix < 0 || ix >= w) continue;
-        const bf8 v = unpack8(*(const uint4*)(x + ((long long)(b * h + iy) * w + ix) * x_ld + g * 8));
+        const f32x8 v = unpack8(*(const uint4*)(x + ((long long)(b * h + iy) * w + ix) * x_ld + g * 8));
 #pragma unroll
         for (int j = 0; j < 8; ++j) m.v[j] = fmaxf(m.v[j], v.v[j]);
       }
@@ -120,8 +100,8 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_bwd_kernel(const bf16_t* __r
     const int gq = (int)(i % groups);
     const long long p = i / groups;
     const int ix = (int)(p % w), iy = (int)((p / w) % h), b = (int)(p / ((long long)w * h));
-    const bf8 me = unpack8(*(const uint4*)(x + p * x_ld + gq * 8));
-    bf8 acc;
+    const f32x8 me = unpack8(*(const uint4*)(x + p * x_ld + gq * 8));
+    f32x8 acc;
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc.v[j] = 0.f;
     const int oy0 = iy >> 1, oy1 = (iy + 1) >> 1, ox0 = ix >> 1, ox1 = (ix + 1) >> 1;      // windows with 2*o - 1 <= i <= 2*o + 1
@@ -139,13 +119,13 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_bwd_kernel(const bf16_t* __r
           for (int kw = 0; kw < 3; ++kw) {
             const int xx = 2 * ox - 1 + kw;
             if (xx < 0 || xx >= w || (kh == my && kw == mx)) continue;
-            const bf8 v = unpack8(*(const uint4*)(x + ((long long)(b * h + yy) * w + xx) * x_ld + gq * 8));
+            const f32x8 v = unpack8(*(const uint4*)(x + ((long long)(b * h + yy) * w + xx) * x_ld + gq * 8));
             const bool earlier = kh < my || (kh == my && kw < mx);
 #pragma unroll
             for (int j = 0; j < 8; ++j) win[j] = win[j] && (earlier ? v.v[j] < me.v[j] : v.v[j] <= me.v[j]) ;
           }
         }
-        const bf8 gv = unpack8(*(const uint4*)(g + ((long long)(b * ho + oy) * wo + ox) * g_ld + gq * 8));
+        const f32x8 gv = unpack8(*(const uint4*)(g + ((long long)(b * ho + oy) * wo + ox) * g_ld + gq * 8));
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc.v[j] += win[j] ? gv.v[j] : 0.f;
       }
@@ -163,14 +143,14 @@ __global__ __launch_bounds__(256) void relu_affine_bwd_kernel(const bf16_t* __re
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int g = (int)(i % groups);
     const long long p = i / groups;
-    bf8 d = unpack8(*(const uint4*)(g1 + p * g1_ld + g * 8));
+    f32x8 d = unpack8(*(const uint4*)(g1 + p * g1_ld + g * 8));
     if (g2) {
-      const bf8 e = unpack8(*(const uint4*)(g2 + p * g2_ld + g * 8));
+      const f32x8 e = unpack8(*(const uint4*)(g2 + p * g2_ld + g * 8));
 #pragma unroll
       for (int j = 0; j < 8; ++j) d.v[j] = bf2f(f2bf(d.v[j] + e.v[j]));   // the sum is what an eager framework would have materialised
     }
     if (relu) {
-      const bf8 av = unpack8(*(const uint4*)(a + p * a_ld + g * 8));
+      const f32x8 av = unpack8(*(const uint4*)(a + p * a_ld + g * 8));
 #pragma unroll
       for (int j = 0; j < 8; ++j) d.v[j] = av.v[j] > 0.f ? d.v[j] : 0.f;
     }
@@ -197,9 +177,9 @@ __global__ __launch_bounds__(256) void upsample_nearest_add_kernel(const bf16_t*
     const long long p = i / groups;
     const int X = (int)(p % W), Y = (int)((p / W) % H), b = (int)(p / ((long long)W * H));
     const int sy = min((int)((long long)Y * h / H), h - 1), sx = min((int)((long long)X * w / W), w - 1);
-    bf8 v = unpack8(*(const uint4*)(x + ((long long)(b * h + sy) * w + sx) * x_ld + g * 8));
+    f32x8 v = unpack8(*(const uint4*)(x + ((long long)(b * h + sy) * w + sx) * x_ld + g * 8));
     if (lat) {
-      const bf8 l = unpack8(*(const uint4*)(lat + p * lat_ld + g * 8));
+      const f32x8 l = unpack8(*(const uint4*)(lat + p * lat_ld + g * 8));
 #pragma unroll
       for (int j = 0; j < 8; ++j) v.v[j] += l.v[j];
     }
@@ -220,13 +200,13 @@ __global__ __launch_bounds__(256) void upsample_nearest_bwd_kernel(const bf16_t*
     // destination rows Y with floor(Y*h/H) == y  <=>  Y in [ceil(y*H/h), ceil((y+1)*H/h))
     const int Y0 = (int)(((long long)y * H + h - 1) / h), Y1 = min(H, (int)(((long long)(y + 1) * H + h - 1) / h));
     const int X0 = (int)(((long long)x * W + w - 1) / w), X1 = min(W, (int)(((long long)(x + 1) * W + w - 1) / w));
-    bf8 s;
+    f32x8 s;
 #pragma unroll
     for (int j = 0; j < 8; ++j) s.v[j] = 0.f;
     if (acc) s = unpack8(*(const uint4*)(acc + p * acc_ld + g * 8));
     for (int Y = Y0; Y < Y1; ++Y)
       for (int X = X0; X < X1; ++X) {
-        const bf8 v = unpack8(*(const uint4*)(gq + ((long long)(b * H + Y) * W + X) * g_ld + g * 8));
+        const f32x8 v = unpack8(*(const uint4*)(gq + ((long long)(b * H + Y) * W + X) * g_ld + g * 8));
 #pragma unroll
         for (int j = 0; j < 8; ++j) s.v[j] += v.v[j];
       }

@@ -288,7 +288,7 @@ __global__ __launch_bounds__(256, (MODE == 4 ? 2 : MODE >= 2 ? 3 : 4)) void stem
           const float z = acc[k >> 2][k & 3];
           const float gg = s2f((bf16_t)((k & 1) ? gi[k >> 1] >> 16 : gi[k >> 1] & 0xFFFFu));
           const float y = z * sc[k] + sh[k];
-          const float dy = y > 0.f ? gg : gg * p.slope;
+          const float dy = y > 0.f ? gg : gg * p.slope;               // bn_dy8 (elem_kernels.hip); xhat here is z*is - mu*is, rounding of its own
           s1[k] += dy;
           s2[k] += dy * (z * ca[k] + cb[k]);
         }
@@ -302,7 +302,7 @@ __global__ __launch_bounds__(256, (MODE == 4 ? 2 : MODE >= 2 ? 3 : 4)) void stem
           const float z = acc[k >> 2][k & 3];
           const float gg = s2f((bf16_t)((k & 1) ? gi[k >> 1] >> 16 : gi[k >> 1] & 0xFFFFu));
           const float y = z * sc[k] + sh[k];
-          const float dy = y > 0.f ? gg : gg * p.slope;
+          const float dy = y > 0.f ? gg : gg * p.slope;               // bn_dy8 / bn_dz8 (elem_kernels.hip) in the folded form ca*dy + cb*z + cc
           o[k] = f2s(MODE == 4 ? dy : ca[k] * dy + (cb[k] * z + cc[k]));
         }
         uint4 w4;

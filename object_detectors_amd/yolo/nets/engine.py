@@ -368,6 +368,7 @@ class Plan(PlanBase):
 
         def sync_sum(t):
             dist.all_reduce(t, op=dist.ReduceOp.SUM, group=eng.process_group)
+        self._sync_sum = sync_sum
 
         def sync_avg(t):
             # backward sums: the apply pass divides by the LOCAL element count, so the rank average gives the global mean (equal shards);
@@ -396,9 +397,7 @@ class Plan(PlanBase):
                 shp.out_ld = a.ld
                 e = _lib.ConvEpilogue(_vp(ss), _vp(ss, 4 * shp.cout), res.ptr if res else None, res.ld if res else 0, 2, 0, SLOPE)
                 self.keep += [shp, ss, e]
-                self.fwd_const.append((L.mi355det_bn_eval_scale_shift, (shp.cout, _vp(eng.params[b + ".weight"]), _vp(eng.params[b + ".bias"]),
-                                                                  _vp(eng.buffers[b + ".running_mean"]),
-                                                                  _vp(eng.buffers[b + ".running_var"]), BN_EPS, _vp(ss), self.stream)))
+                self._bn_stats(None, 0, shp.cout, cp, pixels, b, ss)
                 if fused:
                     fused[1](a, ss)            # stem activation + this convolution + its folded BN / LeakyReLU in one launch
                 else:
@@ -417,22 +416,7 @@ class Plan(PlanBase):
                 fused[1](z, stats)
             else:
                 self.fwd.append((L.mi355det_conv_fwd, (C.byref(shp), x.ptr, _vp(wf), None, _vp(z), 0, _vp(stats), cp, self.stream)))
-            if world > 1:
-                # SyncBN: fold the partial rows into ONE row [sum | sum of squares] (the generic row reduction), all-reduce it, and
-                # finalise from that row with the global element count
-                row = torch.zeros((2, cp), device=dev, dtype=torch.float64)      # folded, all-reduced and finalised in double (the local path's precision)
-                self.keep.append(row)
-                self.fwd.append((L.mi355det_bn_fold_partials_f64, (_vp(stats), rows, shp.cout, cp, _vp(row), self.stream)))
-                self.fwd.append((comm_hook, (sync_sum, row)))
-                self.fwd.append((L.mi355det_bn_finalize_f64, (_vp(row), shp.cout, cp, pixels * world, _vp(eng.params[b + ".weight"]),
-                                                              _vp(eng.params[b + ".bias"]), BN_EPS, BN_MOM,
-                                                              _vp(eng.buffers[b + ".running_mean"]), _vp(eng.buffers[b + ".running_var"]),
-                                                              _vp(ss), self.stream)))
-            else:
-                self.fwd.append((L.mi355det_bn_finalize, (_vp(stats), rows, shp.cout, cp, pixels, _vp(eng.params[b + ".weight"]),
-                                                          _vp(eng.params[b + ".bias"]), BN_EPS, BN_MOM,
-                                                          _vp(eng.buffers[b + ".running_mean"]), _vp(eng.buffers[b + ".running_var"]),
-                                                          _vp(ss), self.stream)))
+            self._bn_stats(stats, rows, shp.cout, cp, pixels, b, ss)
             self.fwd.append((L.mi355det_bn_act_fwd, (_vp(z), shp.cout, _vp(ss), shp.cout, pixels, SLOPE, res.ptr if res else None,
                                                      res.ld if res else 0, a.ptr, a.ld, self.stream)))
             self.dz_elems = max(self.dz_elems, pixels * shp.cout)
@@ -456,7 +440,7 @@ class Plan(PlanBase):
 
         # stem (darknet.py:41-43,74-76): recompute kernels straight from the fp32 image, no stored z / im2col matrix (csrc/stem_kernels.hip)
         self.img_args = []       # argument lists whose first entry is the image pointer of the current step
-        x = self._stem(n, H, W, new_act, sync_sum)
+        x = self._stem(n, H, W, new_act)
         stem_fused = self.layers["backbone.conv1"].get("fused_l1")
         feats = {}
         for li, nb in enumerate(BLOCKS[eng.backbone], 1):
@@ -503,7 +487,28 @@ class Plan(PlanBase):
         else:
             self._autotune_eval()
 
-    def _stem(self, n, H, W, new_act, sync_sum):
+    def _bn_stats(self, stats, rows, c, c_pad, pixels, b, ss):
+        """Append the calls that fill `ss` (scale | shift | mean | invstd) of BatchNorm layer `b`.  Inference: from the running statistics, into
+        fwd_const (stats is None).  Training: from the `rows` partial rows of `stats` [rows + 64, 2, c_pad], locally or (SyncBN) across ranks."""
+        eng, L = self.eng, self.eng.L
+        gamma, beta = _vp(eng.params[b + ".weight"]), _vp(eng.params[b + ".bias"])
+        rmean, rvar = _vp(eng.buffers[b + ".running_mean"]), _vp(eng.buffers[b + ".running_var"])
+        if not self.training:
+            self.fwd_const.append((L.mi355det_bn_eval_scale_shift, (c, gamma, beta, rmean, rvar, BN_EPS, _vp(ss), self.stream)))
+        elif self.sync_world > 1:
+            # SyncBN: fold the partial rows into ONE row [sum | sum of squares], all-reduce it, and finalise from that row with the global
+            # element count; folded, all-reduced and finalised in double (the local path's precision)
+            row = torch.zeros((2, c_pad), device=eng.device, dtype=torch.float64)
+            self.keep.append(row)
+            self.fwd.append((L.mi355det_bn_fold_partials_f64, (_vp(stats), rows, c, c_pad, _vp(row), self.stream)))
+            self.fwd.append((comm_hook, (self._sync_sum, row)))
+            self.fwd.append((L.mi355det_bn_finalize_f64, (_vp(row), c, c_pad, pixels * self.sync_world, gamma, beta, BN_EPS, BN_MOM, rmean, rvar,
+                                                          _vp(ss), self.stream)))
+        else:
+            self.fwd.append((L.mi355det_bn_finalize, (_vp(stats), rows, c, c_pad, pixels, gamma, beta, BN_EPS, BN_MOM, rmean, rvar, _vp(ss),
+                                                      self.stream)))
+
+    def _stem(self, n, H, W, new_act):
         eng, L, dev = self.eng, self.eng.L, self.eng.device
         name, b = "backbone.conv1", "backbone.bn1"
         s = eng.by_name[name]
@@ -520,24 +525,12 @@ class Plan(PlanBase):
             args = [None] + list(args)
             self.img_args.append(args)
             return (fn, args)
-        if not self.training:
-            self.fwd_const.append((L.mi355det_bn_eval_scale_shift, (32, _vp(eng.params[b + ".weight"]), _vp(eng.params[b + ".bias"]),
-                                                              _vp(eng.buffers[b + ".running_mean"]), _vp(eng.buffers[b + ".running_var"]),
-                                                              BN_EPS, _vp(ss), self.stream)))
-        else:
+        part = None
+        if self.training:
             part = torch.zeros((rows + 64, 2, 32), device=dev, dtype=torch.float32)
             self.keep.append(part)
             self.fwd.append(img_call(L.mi355det_stem_fwd_stats, (_vp(wf), _vp(part), n, H, W, self.stream)))
-            fin = (_vp(eng.params[b + ".weight"]), _vp(eng.params[b + ".bias"]), BN_EPS, BN_MOM, _vp(eng.buffers[b + ".running_mean"]),
-                   _vp(eng.buffers[b + ".running_var"]), _vp(ss), self.stream)
-            if self.sync_world > 1:
-                row = torch.zeros((2, 32), device=dev, dtype=torch.float64)
-                self.keep.append(row)
-                self.fwd.append((L.mi355det_bn_fold_partials_f64, (_vp(part), rows, 32, 32, _vp(row), self.stream)))
-                self.fwd.append((comm_hook, (sync_sum, row)))
-                self.fwd.append((L.mi355det_bn_finalize_f64, (_vp(row), 32, 32, pixels * self.sync_world) + fin))
-            else:
-                self.fwd.append((L.mi355det_bn_finalize, (_vp(part), rows, 32, 32, pixels) + fin))
+        self._bn_stats(part, rows, 32, 32, pixels, b, ss)
         fused = None
         l1_rows = L.mi355det_stem_l1_rows(n, H, W)
         if self.training and l1_rows > 0:

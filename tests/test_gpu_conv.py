@@ -129,6 +129,16 @@ def test_head_conv_f32_bias_255():
 @pytest.mark.parametrize("c,pixels,res", [(32, 1000, False), (64, 4096, True), (256, 777, True), (1024, 300, False),
                                           (24, 500, False), (96, 1500, True), (328, 600, False), (2056, 130, True)])      # channel counts that are not 8 * 2^k
 def test_bn_lrelu_fwd_bwd(c, pixels, res):
+    _bn_lrelu_fwd_bwd(c, pixels, res, c)
+
+
+def test_bn_lrelu_fwd_bwd_pitched():
+    """Pixel pitches above the channel count: z, res, out, g and dz are 24-channel slices of 40-wide buffers; the 16 neighbouring channels
+    of the inputs hold NaN (reading them shows) and those of the outputs a sentinel that must survive."""
+    _bn_lrelu_fwd_bwd(24, 500, True, 40)
+
+
+def _bn_lrelu_fwd_bwd(c, pixels, res, ld):
     from object_detectors_amd._lib import check, lib, ptr, stream_ptr
     z = rnd((pixels, c), 11, 2.0) + 0.3
     z = z.bfloat16().float()
@@ -146,7 +156,14 @@ def test_bn_lrelu_fwd_bwd(c, pixels, res):
     out_ref = y.reshape(c, pixels).t() + (r if res else 0)
     out_ref.backward(g)
     d = dev()
-    zd = z.to(d).bfloat16()
+    SENTINEL = 7.0
+
+    def wide(x, fill):
+        buf = torch.full((pixels, ld), fill, dtype=torch.bfloat16, device=d)
+        if x is not None:
+            buf[:, :c] = x.to(d).bfloat16()
+        return buf
+    zd = wide(z, float("nan"))
     rows = 3
     part = torch.zeros(rows, 2, c, device=d)
     part[0, 0] = z.sum(0).to(d)
@@ -158,18 +175,20 @@ def test_bn_lrelu_fwd_bwd(c, pixels, res):
                                      ptr(ss), stream_ptr()))
     np.testing.assert_allclose(rmd.cpu(), rm, rtol=1e-3, atol=1e-4)
     np.testing.assert_allclose(rvd.cpu(), rv, rtol=1e-3, atol=1e-4)
-    out = torch.empty(pixels, c, dtype=torch.bfloat16, device=d)
-    rd = r.to(d).bfloat16() if res else None
-    check(lib().mi355det_bn_act_fwd(ptr(zd), c, ptr(ss), c, pixels, 0.1, ptr(rd), c, ptr(out), c, stream_ptr()))
-    assert (out.float().cpu() - out_ref.detach()).abs().max().item() < 2e-2 * out_ref.abs().max().item()
-    gd = g.to(d).bfloat16()
+    out = wide(None, SENTINEL)
+    rd = wide(r, float("nan")) if res else None
+    check(lib().mi355det_bn_act_fwd(ptr(zd), ld, ptr(ss), c, pixels, 0.1, ptr(rd), ld, ptr(out), ld, stream_ptr()))
+    assert (out[:, :c].float().cpu() - out_ref.detach()).abs().max().item() < 2e-2 * out_ref.abs().max().item()
+    assert bool((out[:, c:] == SENTINEL).all())
+    gd = wide(g, float("nan"))
     sums = torch.zeros(2 * c, device=d)
-    check(lib().mi355det_bn_act_bwd_reduce(ptr(gd), c, None, 0, ptr(zd), c, ptr(ss), c, pixels, 0.1, ptr(sums), stream_ptr()))
-    dz = torch.empty(pixels, c, dtype=torch.bfloat16, device=d)
+    check(lib().mi355det_bn_act_bwd_reduce(ptr(gd), ld, None, 0, ptr(zd), ld, ptr(ss), c, pixels, 0.1, ptr(sums), stream_ptr()))
+    dz = wide(None, SENTINEL)
     dg, db = torch.zeros(c, device=d), torch.zeros(c, device=d)
-    check(lib().mi355det_bn_act_bwd_apply(ptr(gd), c, None, 0, ptr(zd), c, ptr(ss), ptr(sums), None, c, pixels, 0.1, ptr(dz), c, ptr(dg),
+    check(lib().mi355det_bn_act_bwd_apply(ptr(gd), ld, None, 0, ptr(zd), ld, ptr(ss), ptr(sums), None, c, pixels, 0.1, ptr(dz), ld, ptr(dg),
                                           ptr(db), stream_ptr()))
-    assert (dz.float().cpu() - zr.grad).abs().max().item() < 2e-2 * zr.grad.abs().max().item()
+    assert (dz[:, :c].float().cpu() - zr.grad).abs().max().item() < 2e-2 * zr.grad.abs().max().item()
+    assert bool((dz[:, c:] == SENTINEL).all())
     np.testing.assert_allclose(dg.cpu(), gr.grad, rtol=2e-2, atol=2e-2 * gr.grad.abs().max().item())
     np.testing.assert_allclose(db.cpu(), br.grad, rtol=2e-2, atol=2e-2 * br.grad.abs().max().item())
 
@@ -608,19 +627,17 @@ def test_stride2_dgrad_single_launch_matches_class_launches(case):
     assert (outs[0] - outs[1]).abs().max().item() < 1e-2 * ref.abs().max().item()
 
 
-@pytest.mark.parametrize("rows,c,c_pad", [(1600, 256, 256), (300, 96, 128), (257, 32, 32), (5000, 1024, 1024)])
+@pytest.mark.parametrize("rows,c,c_pad", [(1600, 256, 256), (300, 96, 128), (257, 32, 32), (5000, 1024, 1024), (8200, 32, 32), (20, 40, 64)])
 def test_bn_finalize_many_rows(rows, c, c_pad):
-    """rows > 256: two-stage reduction through the 64 spare rows; repeated launches on fresh data match a float64 reduction of the
-    same partial rows."""
+    """Every row-count path of mi355det_bn_finalize: rows <= 32 one direct fold, 32 < rows <= 8192 the one-launch wide kernel, rows > 8192
+    two stages through the 64 spare rows; repeated launches on fresh data match a float64 reduction of the same partial rows."""
     from object_detectors_amd._lib import check, lib, ptr, stream_ptr
     d = dev()
     count = rows * 128
     gamma = (rnd((c,), 31, 0.3) + 1.0).to(d)
     beta = rnd((c,), 32, 0.2).to(d)
     for rep in range(3):
-        part = torch.zeros(rows + 64, 2, c_pad)
-        part[:rows, 0, :c] = rnd((rows, c), 40 + rep, 30.0) + 5.0
-        part[:rows, 1, :c] = rnd((rows, c), 50 + rep, 20.0).abs() * 40 + 900.0
+        part = _bn_partial_rows(rows, c, c_pad, rep)
         pd = part.to(d)
         ss = torch.zeros(4 * c, device=d)
         rm, rv = torch.zeros(c, device=d), torch.ones(c, device=d)
@@ -635,6 +652,74 @@ def test_bn_finalize_many_rows(rows, c, c_pad):
         np.testing.assert_allclose(got[3 * c:], invstd, rtol=1e-4)
         np.testing.assert_allclose(got[:c], gamma.cpu().double() * invstd, rtol=1e-4)
         np.testing.assert_allclose(rm.cpu().double(), 0.1 * mean, rtol=1e-4, atol=1e-6)
+
+
+def _bn_partial_rows(rows, c, c_pad, seed):
+    part = torch.zeros(rows + 64, 2, c_pad)
+    part[:rows, 0, :c] = rnd((rows, c), 40 + seed, 30.0) + 5.0
+    part[:rows, 1, :c] = rnd((rows, c), 50 + seed, 20.0).abs() * 40 + 900.0
+    return part
+
+
+@pytest.mark.parametrize("rows,c,c_pad", [(20, 40, 64), (300, 96, 128), (8200, 32, 32)])
+def test_bn_syncbn_fold_matches_local_finalize(rows, c, c_pad):
+    """SyncBN route (mi355det_bn_fold_partials_f64 + mi355det_bn_finalize_f64 with the local count) against mi355det_bn_finalize on the same
+    partial rows: both match the float64 evaluation, the pad channels of the folded row are exactly 0, and for rows <= 32 (both routes add
+    the same doubles in the same order and share one finalisation) the two routes agree bit for bit."""
+    from object_detectors_amd._lib import check, lib, ptr, stream_ptr
+    d = dev()
+    L = lib()
+    count = rows * 128
+    gamma = (rnd((c,), 31, 0.3) + 1.0).to(d)
+    beta = rnd((c,), 32, 0.2).to(d)
+    part = _bn_partial_rows(rows, c, c_pad, 7)
+    s1 = part[:rows, 0, :c].double().sum(0)
+    s2 = part[:rows, 1, :c].double().sum(0)
+    mean = s1 / count
+    var = (s2 / count - mean * mean).clamp_min(0)
+    invstd = 1.0 / torch.sqrt(var + 1e-5)
+    unb = var * count / (count - 1)
+    routes = []
+    for sync in (False, True):
+        pd = part.to(d)
+        ss = torch.zeros(4 * c, device=d)
+        rm, rv = torch.zeros(c, device=d), torch.ones(c, device=d)
+        if sync:
+            sums64 = torch.full((2, c_pad), float("nan"), dtype=torch.float64, device=d)
+            check(L.mi355det_bn_fold_partials_f64(ptr(pd), rows, c, c_pad, ptr(sums64), stream_ptr()))
+            check(L.mi355det_bn_finalize_f64(ptr(sums64), c, c_pad, count, ptr(gamma), ptr(beta), 1e-5, 0.1, ptr(rm), ptr(rv), ptr(ss), stream_ptr()))
+            assert bool((sums64[:, c:] == 0).all())
+        else:
+            check(L.mi355det_bn_finalize(ptr(pd), rows, c, c_pad, count, ptr(gamma), ptr(beta), 1e-5, 0.1, ptr(rm), ptr(rv), ptr(ss), stream_ptr()))
+        got = ss.cpu().double()
+        sc = gamma.cpu().double() * invstd
+        np.testing.assert_allclose(got[2 * c:3 * c], mean, rtol=1e-5, atol=1e-6)
+        np.testing.assert_allclose(got[3 * c:], invstd, rtol=1e-4)
+        np.testing.assert_allclose(got[:c], sc, rtol=1e-4)
+        np.testing.assert_allclose(got[c:2 * c], beta.cpu().double() - mean * sc, rtol=1e-4, atol=1e-6)
+        np.testing.assert_allclose(rm.cpu().double(), 0.1 * mean, rtol=1e-4, atol=1e-6)
+        np.testing.assert_allclose(rv.cpu().double(), 0.9 + 0.1 * unb, rtol=1e-4)
+        routes.append((ss, rm, rv))
+    if rows <= 32:
+        for a, b in zip(*routes):
+            assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("rows,c,c_pad", [(300, 24, 32), (40, 24, 32)])
+def test_bn_bwd_sum_partials(rows, c, c_pad):
+    """mi355det_bn_bwd_sum_partials on random partial rows (two stages for rows > 256, one fold below) against the float64 column sums.  The
+    64 spare rows start as NaN bit patterns: a fold that reads beyond `rows`, or a spare row the first stage left unwritten, shows."""
+    from object_detectors_amd._lib import check, lib, ptr, stream_ptr
+    d = dev()
+    g = torch.Generator().manual_seed(rows + c)
+    part = torch.randn((rows, 2, c_pad), generator=g)
+    pd = torch.full((rows + 64, 2, c_pad), float("nan"), device=d)
+    pd[:rows] = part.to(d)
+    sums = torch.full((2 * c,), float("nan"), device=d)          # written, not accumulated
+    check(lib().mi355det_bn_bwd_sum_partials(ptr(pd), rows, c, c_pad, ptr(sums), stream_ptr()), "bn_bwd_sum_partials")
+    want = part[:, :, :c].double().sum(0).reshape(-1)
+    tol = 2e-5 * float(part[:, :, :c].double().abs().sum(0).max()) + 1e-6
+    assert float((sums.cpu().double() - want).abs().max()) < tol
 
 
 def test_stride2_dgrad_single_launch_full_size():
