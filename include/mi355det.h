@@ -746,6 +746,38 @@ int mi355det_mask_resize_nearest(const uint8_t* in, int32_t planes, int32_t h, i
 int mi355det_paste_masks(const float* masks, const float* boxes, int32_t num_masks, int32_t m, int32_t padding, int32_t im_h, int32_t im_w,
                          float* out, void* stream);
 
+/* ---- Mask results as COCO run-length encodings (csrc/rle_kernels.hip, csrc/rle_codec.cpp; torchvision_models/detection/coco_eval.py:107-140
+ * prepare_for_coco_segmentation = `masks > 0.5` + pycocotools mask.encode + counts.decode).  Run lengths follow pycocotools rleEncode: the
+ * pixels of one mask in column-major order i = x*im_h + y, counts = lengths of alternating runs beginning with a run of zeros (which may be
+ * 0), so an all-zero mask is [im_h*im_w], an all-one mask [0, im_h*im_w], and a run goes on from the bottom of one column into the top of
+ * the next.  A mask with T transitions has T + 1 counts.  Two sources of the bit at (d, y, x), chosen by `dense`:
+ *   dense != NULL   dense[d][y][x] > threshold for fp32 [D, im_h, im_w] (the reference's contract: pasted masks); masks / boxes unused.
+ *   dense == NULL   the value mi355det_paste_masks would write at (d, y, x) (same float32 bits: csrc/mask_paste.h) > threshold, from the
+ *                   m x m probabilities masks [D, m, m] and boxes [D, 4]; the full-size mask is never stored, and only the columns and
+ *                   rows of the clipped box are evaluated (outside it the bit is 0, hence threshold >= 0 is required).
+ *   mask_rle_count  counts every column's transitions and scans them: run_offsets [D + 1] int64 on the device (run_offsets[d] = index of
+ *                   mask d's first count, run_offsets[D] = the number of counts in all), and leaves the column tables in the workspace.
+ *   mask_rle_emit   needs the workspace mask_rle_count left for the SAME source: writes counts [run_offsets[D]] int32, area [D] int64
+ *                   (set pixels = the sum of the odd-indexed counts; pycocotools area) and bbox [D, 4] int32 = [xmin, ymin, xmax - xmin + 1,
+ *                   ymax - ymin + 1] of the set pixels, zeros for an empty mask (pycocotools toBbox); area / bbox nullable.  total_runs is
+ *                   the caller's host copy of run_offsets[D] (it sizes counts by it anyway); capacity < total_runs is an error, and no
+ *                   count is ever written at an index >= capacity.
+ * No atomics; the output is bit-identical from run to run.  im_h*im_w must be below 2^31.  workspace: mi355det_mask_rle_workspace bytes.
+ *   rle_to_string / rle_from_string   pycocotools rleToString / rleFrString on the host (no GPU call): each count (from the fourth on, its
+ *                   difference to the count two before) as 5-bit groups, low group first, bit 0x20 = more groups follow, char = group + 48.
+ *                   to_string writes the characters and a terminating NUL and returns the number of characters; out == NULL only sizes.
+ *                   from_string returns the number of counts; counts == NULL only sizes.  A negative status when cap is too small (nothing
+ *                   is written past cap) or the string is malformed. */
+size_t mi355det_mask_rle_workspace(int32_t num_masks, int32_t im_w);
+int mi355det_mask_rle_count(const float* dense, const float* masks, const float* boxes, int32_t num_masks, int32_t m, int32_t padding,
+                            int32_t im_h, int32_t im_w, float threshold, int64_t* run_offsets, void* workspace, size_t workspace_bytes,
+                            void* stream);
+int mi355det_mask_rle_emit(const float* dense, const float* masks, const float* boxes, int32_t num_masks, int32_t m, int32_t padding,
+                           int32_t im_h, int32_t im_w, float threshold, const int64_t* run_offsets, int64_t total_runs, int32_t* counts,
+                           int64_t capacity, int64_t* area, int32_t* bbox, void* workspace, size_t workspace_bytes, void* stream);
+int64_t mi355det_rle_to_string(const int32_t* counts, int64_t n, char* out, int64_t cap);
+int64_t mi355det_rle_from_string(const char* s, int32_t* counts, int64_t cap);
+
 /* layout / dtype converters at the module boundary */
 int mi355det_nhwc_to_nchw_f32(const void* x, int x_is_bf16, int32_t x_ld, int32_t n, int32_t c, int32_t h,
                               int32_t w, float* out, void* stream);

@@ -183,6 +183,11 @@ PROTOTYPES = {
     "mi355det_mask_probs": (C.c_int, [vp, i32, vp, vp, vp, i32, i32, vp, vp]),
     "mi355det_mask_resize_nearest": (C.c_int, [vp, i32, i32, i32, vp, i32, i32, vp]),
     "mi355det_paste_masks": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp, vp]),
+    "mi355det_mask_rle_workspace": (sz, [i32, i32]),
+    "mi355det_mask_rle_count": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, sz, vp]),
+    "mi355det_mask_rle_emit": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, i64, vp, i64, vp, vp, vp, sz, vp]),
+    "mi355det_rle_to_string": (i64, [vp, i64, C.c_char_p, i64]),
+    "mi355det_rle_from_string": (i64, [C.c_char_p, vp, i64]),
 }
 
 def _f16_twins():

@@ -19,6 +19,7 @@ ARCH = "gfx950"
 # decisions; the MFMA files are free to contract.
 SOURCES = [
     ("lib.cpp", []),
+    ("rle_codec.cpp", []),                               # host only: the COCO counts string
     ("yolo_kernels.hip", ["-ffp-contract=off"]),
     ("box_kernels.hip", ["-ffp-contract=off"]),
     ("roi_kernels.hip", ["-ffp-contract=off"]),
@@ -26,6 +27,7 @@ SOURCES = [
     ("frcnn_kernels.hip", ["-ffp-contract=off"]),
     ("transform_kernels.hip", ["-ffp-contract=off"]),
     ("mask_kernels.hip", ["-ffp-contract=off"]),
+    ("rle_kernels.hip", ["-ffp-contract=off"]),          # shares the paste pixel rule with mask_kernels.hip (csrc/mask_paste.h): no twin
     ("resnet_kernels.hip", []),
     ("conv_kernels.hip", []),
     ("igemm8_kernels.hip", []),

@@ -19,6 +19,7 @@
 // Compiled with -ffp-contract=off (build.py): the targets (on the RoIAlign rules of roi_sample.h), the nearest index and the paste follow
 // torch's CPU float32 operation order.
 #include "common.h"
+#include "mask_paste.h"
 #include "roi_sample.h"
 
 using namespace mi355;
@@ -184,57 +185,17 @@ __global__ __launch_bounds__(256) void mask_resize_nearest_kernel(const uint8_t*
   }
 }
 
-// linear weights of torch's upsample (align_corners = False, no scale given): src = max(scale*(dst+0.5)-0.5, 0), index floor clamped to
-// in-1, lambda clamped to [0,1], the second tap one further unless at the border
-__device__ __forceinline__ void lin_tap(int dst, int in, float scale, int& i0, int& i1, float& l0, float& l1) {
-  float src = scale * ((float)dst + 0.5f) - 0.5f;
-  if (src < 0.f) src = 0.f;
-  i0 = min((int)floorf(src), in - 1);
-  float lam = src - (float)i0;
-  lam = fminf(fmaxf(lam, 0.f), 1.f);
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l1 = lam;
-  l0 = 1.f - lam;
-}
-
-// paste_masks_in_image for the D detections of one image: out [D, H, W], every pixel written once.
+// paste_masks_in_image for the D detections of one image: out [D, H, W], every pixel written once (the per-pixel rule: mask_paste.h).
 __global__ __launch_bounds__(256) void paste_masks_kernel(const float* __restrict__ masks, const float* __restrict__ boxes, int D, int M, int pad,
                                                           int H, int W, float* __restrict__ out) {
   const long long total = (long long)D * H * W;
-  const int Mp = M + 2 * pad;
-  const float scale = (float)((double)Mp / (double)M);            // expand_masks: float(M + 2*pad) / M, applied to float32 boxes
+  const float scale = paste_scale(M, pad);
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int x = (int)(i % W);
     const int y = (int)((i / W) % H);
     const int d = (int)(i / ((long long)W * H));
-    const float* bx = boxes + 4 * (size_t)d;
-    // expand_boxes, then .to(int64) (truncation)
-    float w_half = (bx[2] - bx[0]) * 0.5f, h_half = (bx[3] - bx[1]) * 0.5f;
-    const float x_c = (bx[2] + bx[0]) * 0.5f, y_c = (bx[3] + bx[1]) * 0.5f;
-    w_half *= scale;
-    h_half *= scale;
-    const long long b0 = (long long)(x_c - w_half), b2 = (long long)(x_c + w_half);
-    const long long b1 = (long long)(y_c - h_half), b3 = (long long)(y_c + h_half);
-    const long long bw = max(b2 - b0 + 1, 1ll), bh = max(b3 - b1 + 1, 1ll);
-    const long long x0 = max(b0, 0ll), x1 = min(b2 + 1, (long long)W), y0 = max(b1, 0ll), y1 = min(b3 + 1, (long long)H);
-    float v = 0.f;
-    if (x >= x0 && x < x1 && y >= y0 && y < y1) {
-      const int iy = (int)(y - b1), ix = (int)(x - b0);
-      int ya, yb, xa, xb;
-      float wy0, wy1, wx0, wx1;
-      lin_tap(iy, Mp, (float)Mp / (float)bh, ya, yb, wy0, wy1);
-      lin_tap(ix, Mp, (float)Mp / (float)bw, xa, xb, wx0, wx1);
-      const float* m = masks + (size_t)d * M * M;
-      auto at = [&](int yy, int xx) -> float {          // the zero-padded (M + 2 pad)^2 mask of expand_masks
-        yy -= pad;
-        xx -= pad;
-        return (yy >= 0 && yy < M && xx >= 0 && xx < M) ? m[yy * M + xx] : 0.f;
-      };
-      const float t0 = at(ya, xa) * wx0 + at(ya, xb) * wx1;
-      const float t1 = at(yb, xa) * wx0 + at(yb, xb) * wx1;
-      v = t0 * wy0 + t1 * wy1;
-    }
-    out[i] = v;
+    const PasteBox B = paste_box(boxes + 4 * (size_t)d, scale, H, W);
+    out[i] = paste_value(masks + (size_t)d * M * M, M, pad, B, x, y);
   }
 }
 

@@ -879,3 +879,52 @@ def paste_masks(masks, boxes, img_shape, padding=1):
     out = torch.empty((D, 1, H, W), dtype=torch.float32, device=m.device)
     check(lib().mi355det_paste_masks(ptr(m), ptr(_f32c(boxes)), D, M, int(padding), H, W, ptr(out), stream_ptr()), "paste_masks")
     return out
+
+
+def _mask_rle(dense, masks, boxes, D, M, padding, H, W, threshold, dev, capacity=None):
+    """count -> ONE host read of the offsets -> emit into exactly sized counts (mi355det_mask_rle_count / _emit)."""
+    from .rle import RLEBatch
+    L = lib()
+    if D == 0:
+        # the argument checks still run (no launch: num_masks == 0 succeeds)
+        check(L.mi355det_mask_rle_count(ptr(dense), ptr(masks), ptr(boxes), 0, M, padding, H, W, threshold, None, None, 0, stream_ptr()), "mask_rle_count")
+        return RLEBatch((H, W), torch.empty(0, dtype=torch.int32, device=dev), [0], torch.empty(0, dtype=torch.int64, device=dev),
+                        torch.empty((0, 4), dtype=torch.int32, device=dev))
+    nbytes = L.mi355det_mask_rle_workspace(D, W)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    run_offsets = torch.empty(D + 1, dtype=torch.int64, device=dev)
+    src = (ptr(dense), ptr(masks), ptr(boxes), D, M, padding, H, W, threshold)
+    check(L.mi355det_mask_rle_count(*src, ptr(run_offsets), ptr(ws), nbytes, stream_ptr()), "mask_rle_count")
+    offsets = run_offsets.tolist()                         # the one host read: the strings are built from these numbers anyway
+    total = offsets[-1]
+    cap = total if capacity is None else int(capacity)
+    counts = torch.empty(max(cap, 0), dtype=torch.int32, device=dev)
+    area = torch.empty(D, dtype=torch.int64, device=dev)
+    bbox = torch.empty((D, 4), dtype=torch.int32, device=dev)
+    check(L.mi355det_mask_rle_emit(*src, ptr(run_offsets), total, ptr(counts), cap, ptr(area), ptr(bbox), ptr(ws), nbytes, stream_ptr()),
+          "mask_rle_emit")
+    return RLEBatch((H, W), counts, offsets, area, bbox)
+
+
+def mask_rle_dense(masks, threshold=0.5, capacity=None):
+    """`masks > threshold` as COCO run lengths (coco_eval.py:117-125 without the host bitmap): masks fp32 [D, H, W] or [D, 1, H, W] ->
+    RLEBatch.  `capacity` (elements of the counts buffer) defaults to the exact size."""
+    m = _f32c(masks)
+    if m.dim() == 4 and m.shape[1] == 1:
+        m = m[:, 0]
+    if m.dim() != 3:
+        raise ValueError("mask_rle_dense: masks must be [D, H, W] or [D, 1, H, W]")
+    D, H, W = (int(v) for v in m.shape)
+    return _mask_rle(m, None, None, D, 1, 0, H, W, float(threshold), m.device, capacity)
+
+
+def mask_rle_paste(masks, boxes, img_shape, padding=1, threshold=0.5, capacity=None):
+    """The run lengths of `paste_masks(masks, boxes, img_shape, padding) > threshold` straight from the [D, 1, M, M] probabilities and the
+    boxes: the [D, H, W] mask is never written (threshold >= 0).  -> RLEBatch."""
+    m = _f32c(masks)
+    D, M = int(m.shape[0]), int(m.shape[-1])
+    b = _f32c(boxes)
+    if b.shape != (D, 4):
+        raise ValueError("mask_rle_paste: boxes must be [D, 4]")
+    H, W = int(img_shape[0]), int(img_shape[1])
+    return _mask_rle(None, m, b, D, M, int(padding), H, W, float(threshold), m.device, capacity)

@@ -1,0 +1,91 @@
+"""COCO run-length encodings of instance masks: the batch the run-length kernels return (`ops.mask_rle_dense`, `ops.mask_rle_paste`) and the
+`counts` string codec of the library (mi355det_rle_to_string / mi355det_rle_from_string = pycocotools rleToString / rleFrString).
+
+A mask's counts are the lengths of its alternating runs of 0 and 1 over the pixels in column-major order, beginning with a run of zeros
+(pycocotools rleEncode); `{"size": [H, W], "counts": str}` is what pycocotools `mask.encode(...)` + `counts.decode("utf-8")` hands to
+`COCO.loadRes` (torchvision_models/detection/coco_eval.py:107-140)."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from ._lib import Mi355detError, lib
+
+
+def _status(n, what):
+    if n < 0:
+        msg = lib().mi355det_last_error().decode()
+        if n == -1:
+            raise ValueError(f"mi355det {what}: {msg}")
+        raise Mi355detError(f"mi355det {what} failed ({n}): {msg}")
+    return n
+
+
+def counts_to_string(counts, cap=None):
+    """int32 run lengths of one mask -> the compressed ASCII string.  `cap` (bytes of the output buffer, the terminating NUL included) is
+    7 characters per count + 1 unless given."""
+    c = np.ascontiguousarray(counts, dtype=np.int32)
+    n = int(c.shape[0])
+    cap = 7 * n + 1 if cap is None else int(cap)
+    buf = C.create_string_buffer(max(cap, 1))
+    wrote = _status(lib().mi355det_rle_to_string(c.ctypes.data_as(C.c_void_p), n, buf, cap), "rle_to_string")
+    return buf.raw[:wrote].decode("ascii")
+
+
+def string_to_counts(s, cap=None):
+    """The inverse: the compressed string -> int32 numpy run lengths.  `cap` (room for that many counts) is one per character unless given."""
+    raw = s.encode("ascii") if isinstance(s, str) else bytes(s)
+    cap = len(raw) if cap is None else int(cap)
+    out = np.empty(max(cap, 1), np.int32)
+    n = _status(lib().mi355det_rle_from_string(raw, out.ctypes.data_as(C.c_void_p), cap), "rle_from_string")
+    return out[:n].copy()
+
+
+class RLEBatch:
+    """The run-length encodings of the D masks of one image.
+
+    size      (H, W)
+    counts    int32 tensor [offsets[D]]: the masks' counts one after the other (on the device when a kernel made them)
+    offsets   host list [D + 1]: mask d owns counts[offsets[d]:offsets[d + 1]]
+    area      int64 tensor [D]: set pixels (pycocotools `area`), or None
+    bbox      int32 tensor [D, 4]: [x, y, w, h] of the set pixels, zeros for an empty mask (pycocotools `toBbox`), or None
+    """
+
+    def __init__(self, size, counts, offsets, area=None, bbox=None):
+        self.size = (int(size[0]), int(size[1]))
+        self.counts = counts
+        self.offsets = [int(o) for o in offsets]
+        self.area, self.bbox = area, bbox
+        if not self.offsets or self.offsets[0] != 0 or self.offsets[-1] != int(counts.shape[0]) or \
+                any(b <= a for a, b in zip(self.offsets, self.offsets[1:])):
+            raise ValueError("RLEBatch: offsets must rise from 0 to len(counts), at least one count per mask")
+        self._host = None
+
+    def __len__(self):
+        return len(self.offsets) - 1
+
+    def counts_host(self):
+        """The counts as one int32 numpy array (copied from the device once)."""
+        if self._host is None:
+            self._host = np.ascontiguousarray(self.counts.detach().cpu().numpy(), dtype=np.int32)
+        return self._host
+
+    def counts_of(self, d):
+        return self.counts_host()[self.offsets[d]:self.offsets[d + 1]]
+
+    def to_coco(self):
+        """[{"size": [H, W], "counts": str}] - the `segmentation` field of a COCO result, one per mask."""
+        h, w = self.size
+        return [{"size": [h, w], "counts": counts_to_string(self.counts_of(d))} for d in range(len(self))]
+
+    def decode(self):
+        """The bitmaps back: uint8 [D, H, W] on the host."""
+        h, w = self.size
+        out = np.zeros((len(self), h, w), np.uint8)
+        for d in range(len(self)):
+            c = self.counts_of(d).astype(np.int64)
+            if int(c.sum()) != h * w or (c < 0).any():
+                raise ValueError(f"RLEBatch.decode: the counts of mask {d} do not add up to {h}x{w}")
+            bits = np.repeat(np.arange(c.shape[0], dtype=np.int64) & 1, c).astype(np.uint8)
+            out[d] = bits.reshape(w, h).T                  # column-major pixel order
+        return torch.from_numpy(out)

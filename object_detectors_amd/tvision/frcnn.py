@@ -71,6 +71,8 @@ class FastRCNNPredictor(nn.Module):
 
 
 class FasterRCNN(nn.Module):
+    _postprocess_kw = {}                      # extra arguments of transform.postprocess (MaskRCNN: mask_format)
+
     def __init__(self, num_classes=91, trainable_backbone_layers=3, tfidf=None,
                  rpn_pre_nms_top_n_train=2000, rpn_pre_nms_top_n_test=1000, rpn_post_nms_top_n_train=2000, rpn_post_nms_top_n_test=1000,
                  rpn_nms_thresh=0.7, rpn_fg_iou_thresh=0.7, rpn_bg_iou_thresh=0.3, rpn_batch_size_per_image=256, rpn_positive_fraction=0.5,
@@ -221,7 +223,7 @@ class FasterRCNN(nn.Module):
             if det is not None:
                 det = self._roi_extra_eval(self.engine.feature_maps_nhwc(4), det, image_shapes)
                 if original_image_sizes is not None:
-                    det = self.transform.postprocess(det, image_shapes, original_image_sizes)      # generalized_rcnn.py:110
+                    det = self.transform.postprocess(det, image_shapes, original_image_sizes, **self._postprocess_kw)      # generalized_rcnn.py:110
                 return det
         fused = self.training and _RPN_FUSED and _ROI_FUSED and self.roi_targets.fused_ok(n, self.rpn_post["training"], targets)
         if fused:     # proposals stay padded on the device; their counts are read together with the sampler's counts (one host read in all)
@@ -239,7 +241,7 @@ class FasterRCNN(nn.Module):
             det = [{"boxes": bb, "labels": ll, "scores": ss} for bb, ll, ss in zip(b, l, s)]
             det = self._roi_extra_eval(feats, det, image_shapes)
             if original_image_sizes is not None:
-                det = self.transform.postprocess(det, image_shapes, original_image_sizes)      # generalized_rcnn.py:110
+                det = self.transform.postprocess(det, image_shapes, original_image_sizes, **self._postprocess_kw)      # generalized_rcnn.py:110
             return det
         # ---- RoI heads (roi_heads.py:783-848): sample, pool, two FC layers, predictor, Fast R-CNN loss
         if fused:

@@ -4,6 +4,8 @@
     model = maskrcnn_resnet50_fpn(num_classes=91)
     losses = model(images, targets)     # + 'loss_mask'; targets[i]['masks'] = uint8 [G_i, H_i, W_i]; backward already done
     detections = model(images)          # eval: [{'boxes','labels','scores','masks'}], masks [D,1,H0,W0] (list input) or [D,1,28,28]
+    MaskRCNN(mask_format="rle")         # eval on a list input: masks = RLEBatch, the COCO run lengths of `masks > 0.5` at H0 x W0, made
+                                        # from the 28x28 probabilities by one fused kernel pair (mi355det_mask_rle_count / _emit)
 
 Everything of Faster R-CNN (tvision/frcnn.py) is inherited unchanged; the mask branch runs as
   * mask_roi_pool   MultiScaleRoIAlign(['0'..'3'], 14, 2) into bf16 NHWC [R, 14, 14, 256] (mi355det_mask_roi_pool; backward: fp32 atomics);
@@ -115,8 +117,12 @@ class MaskRCNNPredictor(nn.Module):
 class MaskRCNN(FasterRCNN):
     """mask_rcnn.py:21-223 over tvision/frcnn.py:FasterRCNN (same constructor arguments)."""
 
-    def __init__(self, num_classes=91, trainable_backbone_layers=3, tfidf=None, mask_roi_pool=None, mask_head=None, mask_predictor=None, **kw):
+    def __init__(self, num_classes=91, trainable_backbone_layers=3, tfidf=None, mask_roi_pool=None, mask_head=None, mask_predictor=None,
+                 mask_format="dense", **kw):
         super().__init__(num_classes, trainable_backbone_layers, tfidf=tfidf, **kw)
+        if mask_format not in ("dense", "rle"):
+            raise ValueError("MaskRCNN: mask_format must be 'dense' or 'rle'")
+        self.mask_format = mask_format
         dev = self.engine.device
         if mask_roi_pool is not None and (not isinstance(mask_roi_pool, MultiScaleRoIAlign) or mask_roi_pool.output_size != (14, 14)):
             raise NotImplementedError("MaskRCNN: mask_roi_pool must be a 14x14 MultiScaleRoIAlign")
@@ -125,6 +131,10 @@ class MaskRCNN(FasterRCNN):
         self.mask_predictor = (mask_predictor or MaskRCNNPredictor(256, 256, num_classes)).to(dev)
         self.last_mask_rows = None
         self.keep_mask_inputs, self.last_mask_inputs = False, None
+
+    @property
+    def _postprocess_kw(self):
+        return {} if self.mask_format == "dense" else {"mask_format": self.mask_format}
 
     def head_parameters(self):
         return super().head_parameters() + list(self.mask_head.parameters()) + list(self.mask_predictor.parameters())

@@ -117,15 +117,22 @@ class GeneralizedRCNNTransform(torch.nn.Module):
                 targets[i]["masks"] = mask_resize_nearest(targets[i]["masks"], (oh, ow))
         return ImageList(batch, sizes), targets
 
-    def postprocess(self, result, image_shapes, original_image_sizes):
-        """transform.py:228-247 (boxes, and masks when the result has them; no keypoint branch on this path)."""
+    def postprocess(self, result, image_shapes, original_image_sizes, mask_format="dense"):
+        """transform.py:228-247 (boxes, and masks when the result has them; no keypoint branch on this path).  mask_format "dense" is the
+        reference's [D, 1, H0, W0] float masks; "rle" gives their `> 0.5` run lengths (an RLEBatch) at the original image size instead."""
+        if mask_format not in ("dense", "rle"):
+            raise ValueError("mask_format must be 'dense' or 'rle'")
         if self.training:
             return result
         for i, (pred, im_s, o_im_s) in enumerate(zip(result, image_shapes, original_image_sizes)):
             boxes = resize_boxes(pred["boxes"], im_s, o_im_s)
             result[i]["boxes"] = boxes
             if "masks" in pred:
-                result[i]["masks"] = paste_masks(pred["masks"], boxes, o_im_s)
+                if mask_format == "dense":
+                    result[i]["masks"] = paste_masks(pred["masks"], boxes, o_im_s)
+                else:              # `paste_masks(...) > 0.5` as run lengths, without the full-size masks
+                    from ..ops import mask_rle_paste
+                    result[i]["masks"] = mask_rle_paste(pred["masks"], boxes, o_im_s)
         return result
 
 
