@@ -778,6 +778,51 @@ int mi355det_mask_rle_emit(const float* dense, const float* masks, const float* 
 int64_t mi355det_rle_to_string(const int32_t* counts, int64_t n, char* out, int64_t cap);
 int64_t mi355det_rle_from_string(const char* s, int32_t* counts, int64_t cap);
 
+/* ---- COCO evaluation (csrc/cocoeval_kernels.hip): pycocotools maskUtils.iou, COCOeval.evaluateImg and COCOeval.accumulate for `bbox` and
+ * `segm`.  A group is one (image, category) pair: D detections in descending score order (stable, cut to the largest maxDets by the caller)
+ * and G ground truths in annotation order.  dt_offsets / gt_offsets / iou_offsets [num_groups + 1] int64 ON THE DEVICE: group j owns the
+ * detection slots dt_offsets[j]..dt_offsets[j + 1], the ground-truth slots likewise and the row-major [D, G] float64 matrix at
+ * iou[iou_offsets[j]].  num_dt / num_gt / iou_size are the caller's host copies of the last offsets: they size every array below, and a
+ * group that does not fit them is skipped, never written past.  All floating point is float64 without contraction; no atomics, every output
+ * element has one writer, so the output is bit-identical from run to run.  No entry point needs a workspace; each validates its arguments
+ * on the host and returns without a launch when there are no groups (categories).
+ *   coco_iou         boxes [x, y, w, h] float64: da = dw*dh, ga = gw*gh, w = min(dx+dw, gx+gw) - max(dx, gx) (<= 0: IoU 0), h likewise,
+ *                    i = w*h, u = gt_crowd ? da : da + ga - i, iou = i/u.  rle_mode = 0: dt_boxes [num_dt, 4], gt_boxes [num_gt, 4] are the
+ *                    boxes.  rle_mode = 1: they are the masks' tight boxes (toBbox, zeros for an empty mask) and reject first (box IoU 0 ->
+ *                    0); otherwise one lane walks both run lists (mi355det_mask_rle_* format: column-major, a zero run first) and counts
+ *                    i and both areas; i == 0 -> 0, else the same i/u.  The run lists are counts + runs [masks + 1] as RLEBatch holds
+ *                    them; index (nullable = identity) maps a slot to its mask.  dt_sizes / gt_sizes are HOST arrays [num_groups, 2] of
+ *                    [h, w], [0, 0] for a side without masks: differing sizes within a group are MI355DET_EINVAL before any launch.
+ *   coco_match       lane a*num_thrs + t of the group's wavefront runs the greedy match of area range a at IoU threshold t (num_areas *
+ *                    num_thrs <= 64).  iou_thrs [num_thrs], area_rngs [num_areas, 2] float64 on the device, built by the caller (never
+ *                    recomputed here).  gt_ignore [num_areas, num_gt] uint8 = crowd, or area outside the range.  Per detection in score
+ *                    order: best = min(thr, 1 - 1e-10); walk the non-ignored ground truths, then (only while unmatched) the ignored
+ *                    ones, each in annotation order; skip one already matched unless crowd; skip iou < best (strict); else take it.
+ *                    dt_match [num_areas, num_thrs, num_dt] int32 = 0 or the ground truth's index in its group + 1; gt_match [num_areas,
+ *                    num_thrs, num_gt] int32 = 0 or the detection's index in its group + 1; dt_ignore [num_areas, num_thrs, num_dt] uint8 =
+ *                    the matched ground truth's flag, or for an unmatched detection dt_area outside the range.
+ *   coco_accumulate  the slots are category-major: category k owns cat_dt_offsets[k]..[k + 1] and cat_gt_offsets[k]..[k + 1] (int64
+ *                    [num_cats + 1] on the device).  order [num_dt] int64: per category its slots in descending score order (stable);
+ *                    dt_rank [num_dt] int32: the slot's rank within its group; max_dets is a HOST array (at most 8).  Per (k, a, m, t):
+ *                    detections with rank < max_dets[m] in `order`; npig = non-ignored ground truths; tp / fp cumulative sums; rc =
+ *                    tp/npig; pr = tp/(fp + tp + 2^-52) made non-increasing from the right; recall [num_thrs, K, A, M] = the last rc (0
+ *                    without detections); precision / scores [num_thrs, num_recs, K, A, M] = pr / score at the first index with rc >=
+ *                    rec_thrs[r] (float64 on the device), 0 past the end; everything -1 where npig == 0. */
+int mi355det_coco_iou(int32_t rle_mode, int64_t num_groups, const int64_t* dt_offsets, const int64_t* gt_offsets, const int64_t* iou_offsets,
+                      int64_t num_dt, int64_t num_gt, int64_t iou_size, const double* dt_boxes, const double* gt_boxes, const uint8_t* gt_crowd,
+                      const int32_t* dt_counts, const int64_t* dt_runs, const int64_t* dt_index, int64_t dt_masks, int64_t dt_num_counts,
+                      const int32_t* gt_counts, const int64_t* gt_runs, const int64_t* gt_index, int64_t gt_masks, int64_t gt_num_counts,
+                      const int32_t* dt_sizes, const int32_t* gt_sizes, double* iou, void* stream);
+int mi355det_coco_match(int64_t num_groups, const int64_t* dt_offsets, const int64_t* gt_offsets, const int64_t* iou_offsets, int64_t num_dt,
+                        int64_t num_gt, int64_t iou_size, const double* iou, const double* dt_area, const double* gt_area,
+                        const uint8_t* gt_crowd, const double* iou_thrs, int32_t num_thrs, const double* area_rngs, int32_t num_areas,
+                        int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore, void* stream);
+int mi355det_coco_accumulate(int32_t num_cats, const int64_t* cat_dt_offsets, const int64_t* cat_gt_offsets, int64_t num_dt, int64_t num_gt,
+                             const int64_t* order, const int32_t* dt_rank, const double* dt_score, const int32_t* dt_match,
+                             const uint8_t* dt_ignore, const uint8_t* gt_ignore, int32_t num_thrs, int32_t num_areas, const int32_t* max_dets,
+                             int32_t num_max_dets, const double* rec_thrs, int32_t num_recs, double* precision, double* recall, double* scores,
+                             void* stream);
+
 /* layout / dtype converters at the module boundary */
 int mi355det_nhwc_to_nchw_f32(const void* x, int x_is_bf16, int32_t x_ld, int32_t n, int32_t c, int32_t h,
                               int32_t w, float* out, void* stream);

@@ -28,6 +28,7 @@ SOURCES = [
     ("transform_kernels.hip", ["-ffp-contract=off"]),
     ("mask_kernels.hip", ["-ffp-contract=off"]),
     ("rle_kernels.hip", ["-ffp-contract=off"]),          # shares the paste pixel rule with mask_kernels.hip (csrc/mask_paste.h): no twin
+    ("cocoeval_kernels.hip", ["-ffp-contract=off"]),     # float64 IoU / precision quotients, compared bit for bit: no twin
     ("resnet_kernels.hip", []),
     ("conv_kernels.hip", []),
     ("igemm8_kernels.hip", []),

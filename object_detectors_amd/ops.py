@@ -928,3 +928,107 @@ def mask_rle_paste(masks, boxes, img_shape, padding=1, threshold=0.5, capacity=N
         raise ValueError("mask_rle_paste: boxes must be [D, 4]")
     H, W = int(img_shape[0]), int(img_shape[1])
     return _mask_rle(None, m, b, D, M, int(padding), H, W, float(threshold), m.device, capacity)
+
+
+# ---- COCO evaluation (csrc/cocoeval_kernels.hip; the evaluator on top of these is object_detectors_amd/cocoeval.py)
+def _f64c(t, dev):
+    return torch.as_tensor(t, dtype=torch.float64, device=dev).contiguous()
+
+
+def coco_iou(dt_offsets, gt_offsets, iou_offsets, iou_size, dt_boxes, gt_boxes, gt_crowd, rle=None):
+    """mi355det_coco_iou over ragged groups: offsets int64 [NG + 1] on the device, boxes float64 [*, 4] as [x, y, w, h], gt_crowd uint8 ->
+    float64 [iou_size].  `rle` switches to run-length mode: a dict with dt / gt = (counts int32, runs int64 [masks + 1], index int64 or None)
+    on the device and dt_sizes / gt_sizes = host int32 [NG, 2]; the boxes are then the masks' tight boxes."""
+    import numpy as np
+    dev = dt_boxes.device
+    if not dt_boxes.is_cuda:
+        raise ValueError("coco_iou needs CUDA/HIP tensors (no CPU fallback)")
+    ng = int(dt_offsets.shape[0]) - 1
+    nd, ngt = int(dt_boxes.shape[0]), int(gt_boxes.shape[0])
+    out = torch.empty(int(iou_size), dtype=torch.float64, device=dev)
+    if rle is None:
+        side = (None, None, None, 0, 0)
+        args = side + side + (None, None)
+        keep = ()
+    else:
+        def one(s):
+            counts, runs, index = s
+            return (ptr(counts), ptr(runs), ptr(index), int(runs.shape[0]) - 1, int(counts.shape[0]))
+        sizes = [np.ascontiguousarray(rle[k], dtype=np.int32).reshape(-1, 2) for k in ("dt_sizes", "gt_sizes")]
+        if any(s.shape[0] != ng for s in sizes):
+            raise ValueError("coco_iou: one [h, w] per group and side")
+        args = one(rle["dt"]) + one(rle["gt"]) + tuple(s.ctypes.data_as(C.c_void_p) for s in sizes)
+        keep = sizes
+    check(lib().mi355det_coco_iou(0 if rle is None else 1, ng, ptr(dt_offsets), ptr(gt_offsets), ptr(iou_offsets), nd, ngt, int(iou_size),
+                                  ptr(dt_boxes), ptr(gt_boxes), ptr(gt_crowd), *args, ptr(out), stream_ptr()), "coco_iou")
+    del keep
+    return out
+
+
+def coco_match(dt_offsets, gt_offsets, iou_offsets, iou, dt_area, gt_area, gt_crowd, iou_thrs, area_rngs):
+    """mi355det_coco_match -> dt_match int32 [A, T, ND], dt_ignore uint8 [A, T, ND], gt_match int32 [A, T, NG], gt_ignore uint8 [A, NG]."""
+    dev = iou.device
+    if not iou.is_cuda:
+        raise ValueError("coco_match needs CUDA/HIP tensors (no CPU fallback)")
+    ng, nd, ngt = int(dt_offsets.shape[0]) - 1, int(dt_area.shape[0]), int(gt_area.shape[0])
+    T, A = int(iou_thrs.shape[0]), int(area_rngs.shape[0])
+    dt_match = torch.zeros((A, T, nd), dtype=torch.int32, device=dev)
+    dt_ignore = torch.zeros((A, T, nd), dtype=torch.uint8, device=dev)
+    gt_match = torch.zeros((A, T, ngt), dtype=torch.int32, device=dev)
+    gt_ignore = torch.zeros((A, ngt), dtype=torch.uint8, device=dev)
+    check(lib().mi355det_coco_match(ng, ptr(dt_offsets), ptr(gt_offsets), ptr(iou_offsets), nd, ngt, int(iou.shape[0]), ptr(iou), ptr(dt_area),
+                                    ptr(gt_area), ptr(gt_crowd), ptr(iou_thrs), T, ptr(area_rngs), A, ptr(dt_match), ptr(dt_ignore),
+                                    ptr(gt_match), ptr(gt_ignore), stream_ptr()), "coco_match")
+    return dt_match, dt_ignore, gt_match, gt_ignore
+
+
+def coco_accumulate(cat_dt_offsets, cat_gt_offsets, order, dt_rank, dt_score, dt_match, dt_ignore, gt_ignore, max_dets, rec_thrs):
+    """mi355det_coco_accumulate -> precision [T, R, K, A, M], recall [T, K, A, M], scores [T, R, K, A, M] (float64)."""
+    dev = rec_thrs.device
+    if not rec_thrs.is_cuda:
+        raise ValueError("coco_accumulate needs CUDA/HIP tensors (no CPU fallback)")
+    K = int(cat_dt_offsets.shape[0]) - 1
+    A, T, nd = (int(v) for v in dt_match.shape)
+    ngt, R, M = int(gt_ignore.shape[1]), int(rec_thrs.shape[0]), len(max_dets)
+    precision = torch.full((T, R, K, A, M), -1.0, dtype=torch.float64, device=dev)
+    recall = torch.full((T, K, A, M), -1.0, dtype=torch.float64, device=dev)
+    scores = torch.full((T, R, K, A, M), -1.0, dtype=torch.float64, device=dev)
+    md = (C.c_int32 * M)(*[int(m) for m in max_dets])
+    check(lib().mi355det_coco_accumulate(K, ptr(cat_dt_offsets), ptr(cat_gt_offsets), nd, ngt, ptr(order), ptr(dt_rank), ptr(dt_score),
+                                         ptr(dt_match), ptr(dt_ignore), ptr(gt_ignore), T, A, md, M, ptr(rec_thrs), R, ptr(precision),
+                                         ptr(recall), ptr(scores), stream_ptr()), "coco_accumulate")
+    return precision, recall, scores
+
+
+def _one_group(d, g, dev):
+    off = lambda n: torch.tensor([0, n], dtype=torch.int64, device=dev)
+    return off(d), off(g), off(d * g)
+
+
+def coco_box_iou(dt_xywh, gt_xywh, iscrowd):
+    """pycocotools maskUtils.iou on boxes: [D, 4] against [G, 4] as [x, y, w, h], iscrowd [G] -> float64 [D, G].  float32 inputs are widened
+    exactly; all arithmetic is float64."""
+    if not (torch.is_tensor(dt_xywh) and dt_xywh.is_cuda):
+        raise ValueError("coco_box_iou needs CUDA/HIP tensors (no CPU fallback)")
+    dev = dt_xywh.device
+    dt, gt = _f64c(dt_xywh, dev).reshape(-1, 4), _f64c(gt_xywh, dev).reshape(-1, 4)
+    crowd = torch.as_tensor(iscrowd, device=dev).to(torch.uint8).contiguous()
+    D, G = int(dt.shape[0]), int(gt.shape[0])
+    if crowd.shape[0] != G:
+        raise ValueError("coco_box_iou: one iscrowd flag per ground truth")
+    return coco_iou(*_one_group(D, G, dev), D * G, dt, gt, crowd).reshape(D, G)
+
+
+def coco_mask_iou(dt, gt, iscrowd):
+    """pycocotools maskUtils.iou on run-length encodings: RLEBatch [D] against RLEBatch [G] of the same [H, W] -> float64 [D, G]."""
+    dev = dt.counts.device
+    if not dt.counts.is_cuda:
+        raise ValueError("coco_mask_iou needs CUDA/HIP tensors (no CPU fallback)")
+    crowd = torch.as_tensor(iscrowd, device=dev).to(torch.uint8).contiguous()
+    D, G = len(dt), len(gt)
+    if crowd.shape[0] != G:
+        raise ValueError("coco_mask_iou: one iscrowd flag per ground truth")
+    side = lambda b: (b.counts.to(dev).contiguous(), torch.tensor(b.offsets, dtype=torch.int64, device=dev), None)
+    rle = {"dt": side(dt), "gt": side(gt), "dt_sizes": [dt.size if D else (0, 0)], "gt_sizes": [gt.size if G else (0, 0)]}
+    boxes = lambda b: b.stats()[1].to(dev).to(torch.float64).contiguous()
+    return coco_iou(*_one_group(D, G, dev), D * G, boxes(dt), boxes(gt), crowd, rle).reshape(D, G)

@@ -41,6 +41,28 @@ def string_to_counts(s, cap=None):
     return out[:n].copy()
 
 
+def counts_stats(counts, offsets, h):
+    """Set pixels (int64 [D]) and tight boxes [xmin, ymin, xmax - xmin + 1, ymax - ymin + 1] (int32 [D, 4], zeros for an empty mask) of
+    run lengths over columns of height h: concatenated int32 counts, mask d owning counts[offsets[d]:offsets[d + 1]]."""
+    n = len(offsets) - 1
+    area, bbox = np.zeros(n, np.int64), np.zeros((n, 4), np.int32)
+    for d in range(n):
+        c = np.asarray(counts[offsets[d]:offsets[d + 1]], np.int64)
+        end = np.cumsum(c)
+        first, last = (end - c)[1::2], end[1::2] - 1           # the runs of ones: first and last pixel index
+        live = last >= first
+        if not live.any():
+            continue
+        first, last = first[live], last[live]
+        area[d] = int((last - first + 1).sum())
+        x0, x1 = first // h, last // h
+        whole = x1 > x0                                          # a run that goes on into the next column covers y = 0 and y = h - 1
+        ymin = 0 if whole.any() else int((first % h).min())
+        ymax = h - 1 if whole.any() else int((last % h).max())
+        bbox[d] = (int(x0.min()), ymin, int(x1.max() - x0.min()) + 1, ymax - ymin + 1)
+    return area, bbox
+
+
 class RLEBatch:
     """The run-length encodings of the D masks of one image.
 
@@ -72,6 +94,14 @@ class RLEBatch:
 
     def counts_of(self, d):
         return self.counts_host()[self.offsets[d]:self.offsets[d + 1]]
+
+    def stats(self):
+        """(area int64 [D], bbox int32 [D, 4]): what the kernels returned, or - for a batch built from counts alone, a ground truth read
+        from json - pycocotools `area` / `toBbox` worked out from the counts on the host."""
+        if self.area is None or self.bbox is None:
+            area, bbox = counts_stats(self.counts_host(), self.offsets, self.size[0])
+            self.area, self.bbox = torch.from_numpy(area).to(self.counts.device), torch.from_numpy(bbox).to(self.counts.device)
+        return self.area, self.bbox
 
     def to_coco(self):
         """[{"size": [H, W], "counts": str}] - the `segmentation` field of a COCO result, one per mask."""
