@@ -801,6 +801,13 @@ int64_t mi355det_rle_from_string(const char* s, int32_t* counts, int64_t cap);
  *                    dt_match [num_areas, num_thrs, num_dt] int32 = 0 or the ground truth's index in its group + 1; gt_match [num_areas,
  *                    num_thrs, num_gt] int32 = 0 or the detection's index in its group + 1; dt_ignore [num_areas, num_thrs, num_dt] uint8 =
  *                    the matched ground truth's flag, or for an unmatched detection dt_area outside the range.
+ *   lvis_match       coco_match under the rules of lvis-api's LVISEval (same kernel body, same outputs and layouts, same guarantees).  LVIS
+ *                    has no crowds: gt_flag [num_gt] uint8 is the annotation's `ignore` flag, gt_ignore = gt_flag, or area outside the
+ *                    range, and a ground truth already matched at this threshold is always skipped (no re-match).
+ *                    group_not_exhaustive [num_groups] uint8 ON THE DEVICE: the group's category is in its image's
+ *                    not_exhaustive_category_ids; dt_ignore of an unmatched detection = dt_area outside the range, or that flag.  A missing
+ *                    group_not_exhaustive with num_groups > 0 is MI355DET_EINVAL.  The IoU comes from coco_iou with an all-zero gt_crowd
+ *                    (never the ignore flags); coco_accumulate takes the outputs as they are, with one max_dets that cuts nothing.
  *   coco_accumulate  the slots are category-major: category k owns cat_dt_offsets[k]..[k + 1] and cat_gt_offsets[k]..[k + 1] (int64
  *                    [num_cats + 1] on the device).  order [num_dt] int64: per category its slots in descending score order (stable);
  *                    dt_rank [num_dt] int32: the slot's rank within its group; max_dets is a HOST array (at most 8).  Per (k, a, m, t):
@@ -817,6 +824,11 @@ int mi355det_coco_match(int64_t num_groups, const int64_t* dt_offsets, const int
                         int64_t num_gt, int64_t iou_size, const double* iou, const double* dt_area, const double* gt_area,
                         const uint8_t* gt_crowd, const double* iou_thrs, int32_t num_thrs, const double* area_rngs, int32_t num_areas,
                         int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore, void* stream);
+int mi355det_lvis_match(int64_t num_groups, const int64_t* dt_offsets, const int64_t* gt_offsets, const int64_t* iou_offsets, int64_t num_dt,
+                        int64_t num_gt, int64_t iou_size, const double* iou, const double* dt_area, const double* gt_area,
+                        const uint8_t* gt_flag, const uint8_t* group_not_exhaustive, const double* iou_thrs, int32_t num_thrs,
+                        const double* area_rngs, int32_t num_areas, int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore,
+                        void* stream);
 int mi355det_coco_accumulate(int32_t num_cats, const int64_t* cat_dt_offsets, const int64_t* cat_gt_offsets, int64_t num_dt, int64_t num_gt,
                              const int64_t* order, const int32_t* dt_rank, const double* dt_score, const int32_t* dt_match,
                              const uint8_t* dt_ignore, const uint8_t* gt_ignore, int32_t num_thrs, int32_t num_areas, const int32_t* max_dets,

@@ -14,7 +14,8 @@ within a group the detections are in descending score order (stable, cut to 100)
 `gt_offsets[j]:gt_offsets[j + 1]` and the row-major [D, G] matrix at `iou[iou_offsets[j]]`.  `dt_index` / `gt_index` map a slot back to the
 detection's position in the order it was added and to the annotation's position in the dataset.
 
-Out of scope: LVIS rules, keypoints / OKS, and polygon ground truth (no polygon-to-mask conversion here: DESIGN.md)."""
+The LVIS rules (federated annotations, APr / APc / APf) are lviseval.py: another front end and match rule on the same layout and kernels.
+Out of scope: keypoints / OKS, and polygon ground truth (no polygon-to-mask conversion here: DESIGN.md)."""
 import json
 
 import numpy as np
@@ -139,6 +140,29 @@ def _image_sizes(sizes, img, num_images, what):
     return out
 
 
+# ---- plain helpers of the slot layout, shared with lviseval.py
+def sort_ground_truth(anns, cat_index, img_index, num_images):
+    """[(position, annotation)] -> (their group keys category index * num_images + image index, sorted; the stable order that sorts them)."""
+    key = np.asarray([cat_index[a["category_id"]] * num_images + img_index[a["image_id"]] for _j, a in anns], np.int64)
+    order = np.argsort(key, kind="mergesort")
+    return key[order], order
+
+
+def group_offsets(keys, k):
+    """Sorted unique group keys [ng] and the (sorted) keys of one side's slots -> slots per group [ng], offsets [ng + 1]."""
+    ng, dev = int(keys.shape[0]), keys.device
+    c = torch.bincount(torch.searchsorted(keys, k), minlength=ng) if ng else torch.zeros(0, dtype=torch.int64, device=dev)
+    return c, torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(c, 0)])
+
+
+def category_order(cat_dt_offsets, dt_score):
+    """Per category its detection slots in descending score order (stable over the image order the slots are in): coco_accumulate's `order`."""
+    cat_of = torch.searchsorted(cat_dt_offsets, torch.arange(int(dt_score.shape[0]), device=dt_score.device), right=True) - 1
+    o1 = torch.sort(-dt_score, stable=True).indices
+    o2 = torch.sort(cat_of[o1], stable=True).indices
+    return o1[o2].contiguous()
+
+
 class COCOEval:
     """COCOeval for `bbox` or `segm` on the device.  `gt`: see load_dataset.  Detections come in through add() (one image, device tensors) or
     add_results() (COCO result dicts); evaluate(), accumulate() and summarize() then follow pycocotools' protocol."""
@@ -231,9 +255,8 @@ class COCOEval:
             return self._gt
         dev, I = self.device, len(self.img_ids)
         anns = self._anns
-        key = np.asarray([self._cat_index[a["category_id"]] * I + self._img_index[a["image_id"]] for _j, a in anns], np.int64)
-        order = np.argsort(key, kind="mergesort")
-        gt = {"key": key[order], "index": np.asarray([anns[o][0] for o in order], np.int64),
+        key, order = sort_ground_truth(anns, self._cat_index, self._img_index, I)
+        gt = {"key": key, "index": np.asarray([anns[o][0] for o in order], np.int64),
               "area": np.asarray([float(anns[o][1]["area"]) for o in order], np.float64),
               "crowd": np.asarray([1 if anns[o][1].get("iscrowd", 0) else 0 for o in order], np.uint8)}
         if self.iou_type == "bbox":
@@ -279,12 +302,8 @@ class COCOEval:
         # the groups: every (category, image) with a detection or a ground truth
         keys = torch.unique(torch.cat([key, gt["key_dev"]]))
         ng = int(keys.shape[0])
-
-        def offsets(k):
-            c = torch.bincount(torch.searchsorted(keys, k), minlength=ng) if ng else torch.zeros(0, dtype=torch.int64, device=dev)
-            return c, torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(c, 0)])
-        dc, self.dt_offsets = offsets(key)
-        gc, self.gt_offsets = offsets(gt["key_dev"])
+        dc, self.dt_offsets = group_offsets(keys, key)
+        gc, self.gt_offsets = group_offsets(keys, gt["key_dev"])
         self.iou_offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(dc * gc, 0)])
         iou_size = int(self.iou_offsets[-1])                      # the one host read: it sizes the IoU buffer
         self.group_keys, self.gt_index = keys, gt["index"]
@@ -318,11 +337,7 @@ class COCOEval:
         if self.iou is None:
             raise RuntimeError("COCOEval.accumulate: call evaluate() first")
         dev = self.device
-        # per category, its detection slots in descending score order (stable over the image order the slots are in)
-        cat_of = torch.searchsorted(self.cat_dt_offsets, torch.arange(self.num_dt, device=dev), right=True) - 1
-        o1 = torch.sort(-self.dt_score, stable=True).indices
-        o2 = torch.sort(cat_of[o1], stable=True).indices
-        self.order = o1[o2].contiguous()
+        self.order = category_order(self.cat_dt_offsets, self.dt_score)
         rec = torch.from_numpy(np.ascontiguousarray(self.rec_thrs, np.float64)).to(dev)
         p, r, s = ops.coco_accumulate(self.cat_dt_offsets, self.cat_gt_offsets, self.order, self.dt_rank, self.dt_score, self.dt_match,
                                       self.dt_ignore, self.gt_ignore, self.max_dets, rec)

@@ -8,6 +8,9 @@
 //   coco_match_kernel       wave = group, lane a*T + t = one (area range, IoU threshold): the sequential greedy match.  The ground truths are
 //                           walked non-ignored first, ignored second, each in annotation order - the stable partition by the ignore flag,
 //                           never stored.  The "already matched" state is gt_match itself.
+//                           One body, two rules (template switch): COCO re-matches a taken crowd; LVIS (lvis-api's LVISEval) has no
+//                           crowds, takes the annotation's ignore flag in their place and ignores an unmatched detection of a group whose
+//                           category is not exhaustively annotated in its image.
 //   coco_accumulate_kernel  wave = (category, area range, maxDets, threshold): a forward walk over the category's detections in score order
 //                           for the totals, then a backward walk that rebuilds the cumulative sums from the totals (integers: exact), carries
 //                           the running maximum of the precision and lets every detection that raises the recall write the recall thresholds
@@ -120,20 +123,25 @@ __global__ __launch_bounds__(WAVE) void coco_iou_kernel(Groups S, const double* 
   }
 }
 
-// gt_ignore [A, num_gt]; dt_match / dt_ignore [A, T, num_dt]; gt_match [A, T, num_gt] (zeroed by the entry point)
+// gt_ignore [A, num_gt]; dt_match / dt_ignore [A, T, num_dt]; gt_match [A, T, num_gt] (zeroed by the entry point).  gt_flag [num_gt]: COCO's
+// iscrowd, or (LVIS) the annotation's ignore flag; group_nel [num_groups], read by the LVIS variant only: the group's category is not
+// exhaustively annotated in its image.
+template <bool LVIS>
 __global__ __launch_bounds__(WAVE) void coco_match_kernel(Groups S, const double* __restrict__ iou, const double* __restrict__ dt_area,
-                                                          const double* __restrict__ gt_area, const unsigned char* __restrict__ gt_crowd,
-                                                          const double* __restrict__ iou_thrs, int T, const double* __restrict__ area_rngs, int A,
-                                                          int* __restrict__ dt_match, unsigned char* __restrict__ dt_ignore,
-                                                          int* __restrict__ gt_match, unsigned char* __restrict__ gt_ignore) {
+                                                          const double* __restrict__ gt_area, const unsigned char* __restrict__ gt_flag,
+                                                          const unsigned char* __restrict__ group_nel, const double* __restrict__ iou_thrs, int T,
+                                                          const double* __restrict__ area_rngs, int A, int* __restrict__ dt_match,
+                                                          unsigned char* __restrict__ dt_ignore, int* __restrict__ gt_match,
+                                                          unsigned char* __restrict__ gt_ignore) {
   GroupView v;
   if (!group_view(S, blockIdx.x, v)) return;                              // uniform over the block: nobody waits at the barrier below
   const int lane = threadIdx.x;
+  const bool nel = LVIS && group_nel[blockIdx.x] != 0;                    // one value per block
   for (long long e = lane; e < (long long)A * v.G; e += WAVE) {
     const int a = (int)(e / v.G);
     const long long g = v.g0 + e % v.G;
     const double ar = gt_area[g];
-    gt_ignore[(size_t)a * S.num_gt + g] = (gt_crowd[g] != 0 || ar < area_rngs[2 * a] || ar > area_rngs[2 * a + 1]) ? 1 : 0;
+    gt_ignore[(size_t)a * S.num_gt + g] = (gt_flag[g] != 0 || ar < area_rngs[2 * a] || ar > area_rngs[2 * a + 1]) ? 1 : 0;
   }
   __syncthreads();
   if (lane >= A * T) return;
@@ -141,7 +149,7 @@ __global__ __launch_bounds__(WAVE) void coco_match_kernel(Groups S, const double
   const double lo = area_rngs[2 * a], hi = area_rngs[2 * a + 1];
   const double thr = fmin(iou_thrs[t], 1 - 1e-10);
   const unsigned char* gi = gt_ignore + (size_t)a * S.num_gt + v.g0;
-  const unsigned char* gc = gt_crowd + v.g0;
+  const unsigned char* gc = gt_flag + v.g0;
   int* gm = gt_match + ((size_t)a * T + t) * S.num_gt + v.g0;
   int* dm = dt_match + ((size_t)a * T + t) * S.num_dt + v.d0;
   unsigned char* di = dt_ignore + ((size_t)a * T + t) * S.num_dt + v.d0;
@@ -153,7 +161,7 @@ __global__ __launch_bounds__(WAVE) void coco_match_kernel(Groups S, const double
       if (phase == 1 && m > -1) break;                 // a non-ignored match stands: the walk stops at the first ignored ground truth
       for (int g = 0; g < v.G; ++g) {
         if (gi[g] != phase) continue;
-        if (gm[g] > 0 && !gc[g]) continue;             // taken at this threshold, and no crowd
+        if (gm[g] > 0 && (LVIS || !gc[g])) continue;   // taken at this threshold, and no crowd (LVIS: taken is taken)
         const double x = row[g];
         if (x < best) continue;                        // strict: an IoU equal to the threshold matches, an equal later one takes over
         best = x;
@@ -167,7 +175,7 @@ __global__ __launch_bounds__(WAVE) void coco_match_kernel(Groups S, const double
       ig = gi[m];
     } else {
       const double ar = dt_area[v.d0 + d];
-      ig = (ar < lo || ar > hi) ? 1 : 0;
+      ig = (ar < lo || ar > hi || nel) ? 1 : 0;
     }
     di[d] = ig;
   }
@@ -317,6 +325,34 @@ int check_groups(const char* what, long long num_groups, const void* dt_off, con
   return MI355DET_OK;
 }
 
+// the two match entry points: `lvis` picks the rule, `group_nel` is read by the LVIS rule only
+int match_entry(const char* what, bool lvis, int64_t num_groups, const int64_t* dt_offsets, const int64_t* gt_offsets, const int64_t* iou_offsets,
+                int64_t num_dt, int64_t num_gt, int64_t iou_size, const double* iou, const double* dt_area, const double* gt_area,
+                const uint8_t* gt_flag, const uint8_t* group_nel, const double* iou_thrs, int32_t num_thrs, const double* area_rngs,
+                int32_t num_areas, int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore, void* stream) {
+  const int st = check_groups(what, num_groups, dt_offsets, gt_offsets, iou_offsets, num_dt, num_gt, iou_size);
+  if (st != MI355DET_OK) return st;
+  if (num_thrs <= 0 || num_areas <= 0 || (long long)num_thrs * num_areas > WAVE)
+    return fail(MI355DET_EINVAL, "%s: thresholds x area ranges = %lld must be 1..64 (one lane each)", what, (long long)num_thrs * num_areas);
+  if (num_groups == 0) return MI355DET_OK;
+  if (!iou_thrs || !area_rngs) return fail(MI355DET_EINVAL, "%s: missing parameters", what);
+  if (lvis && !group_nel) return fail(MI355DET_EINVAL, "%s: missing group_not_exhaustive", what);
+  if ((num_dt > 0 && (!dt_area || !dt_match || !dt_ignore)) || (num_gt > 0 && (!gt_area || !gt_flag || !gt_match || !gt_ignore)) ||
+      (iou_size > 0 && !iou))
+    return fail(MI355DET_EINVAL, "%s: missing operand", what);
+  const size_t cells = (size_t)num_thrs * num_areas;
+  if (num_dt > 0 && hipMemsetAsync(dt_match, 0, cells * num_dt * sizeof(int32_t), S(stream)) != hipSuccess) return check_launch(what);
+  if (num_gt > 0 && hipMemsetAsync(gt_match, 0, cells * num_gt * sizeof(int32_t), S(stream)) != hipSuccess) return check_launch(what);
+  const Groups G{(const long long*)dt_offsets, (const long long*)gt_offsets, (const long long*)iou_offsets, num_dt, num_gt, iou_size};
+  if (lvis)
+    hipLaunchKernelGGL(coco_match_kernel<true>, dim3((unsigned)num_groups), dim3(WAVE), 0, S(stream), G, iou, dt_area, gt_area, gt_flag, group_nel,
+                       iou_thrs, num_thrs, area_rngs, num_areas, dt_match, dt_ignore, gt_match, gt_ignore);
+  else
+    hipLaunchKernelGGL(coco_match_kernel<false>, dim3((unsigned)num_groups), dim3(WAVE), 0, S(stream), G, iou, dt_area, gt_area, gt_flag, group_nel,
+                       iou_thrs, num_thrs, area_rngs, num_areas, dt_match, dt_ignore, gt_match, gt_ignore);
+  return check_launch(what);
+}
+
 }  // namespace
 
 extern "C" {
@@ -358,23 +394,17 @@ int mi355det_coco_match(int64_t num_groups, const int64_t* dt_offsets, const int
                         int64_t num_gt, int64_t iou_size, const double* iou, const double* dt_area, const double* gt_area,
                         const uint8_t* gt_crowd, const double* iou_thrs, int32_t num_thrs, const double* area_rngs, int32_t num_areas,
                         int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore, void* stream) {
-  const char* what = "coco_match";
-  const int st = check_groups(what, num_groups, dt_offsets, gt_offsets, iou_offsets, num_dt, num_gt, iou_size);
-  if (st != MI355DET_OK) return st;
-  if (num_thrs <= 0 || num_areas <= 0 || (long long)num_thrs * num_areas > WAVE)
-    return fail(MI355DET_EINVAL, "%s: thresholds x area ranges = %lld must be 1..64 (one lane each)", what, (long long)num_thrs * num_areas);
-  if (num_groups == 0) return MI355DET_OK;
-  if (!iou_thrs || !area_rngs) return fail(MI355DET_EINVAL, "%s: missing parameters", what);
-  if ((num_dt > 0 && (!dt_area || !dt_match || !dt_ignore)) || (num_gt > 0 && (!gt_area || !gt_crowd || !gt_match || !gt_ignore)) ||
-      (iou_size > 0 && !iou))
-    return fail(MI355DET_EINVAL, "%s: missing operand", what);
-  const size_t cells = (size_t)num_thrs * num_areas;
-  if (num_dt > 0 && hipMemsetAsync(dt_match, 0, cells * num_dt * sizeof(int32_t), S(stream)) != hipSuccess) return check_launch(what);
-  if (num_gt > 0 && hipMemsetAsync(gt_match, 0, cells * num_gt * sizeof(int32_t), S(stream)) != hipSuccess) return check_launch(what);
-  const Groups G{(const long long*)dt_offsets, (const long long*)gt_offsets, (const long long*)iou_offsets, num_dt, num_gt, iou_size};
-  hipLaunchKernelGGL(coco_match_kernel, dim3((unsigned)num_groups), dim3(WAVE), 0, S(stream), G, iou, dt_area, gt_area, gt_crowd, iou_thrs,
-                     num_thrs, area_rngs, num_areas, dt_match, dt_ignore, gt_match, gt_ignore);
-  return check_launch(what);
+  return match_entry("coco_match", false, num_groups, dt_offsets, gt_offsets, iou_offsets, num_dt, num_gt, iou_size, iou, dt_area, gt_area,
+                     gt_crowd, nullptr, iou_thrs, num_thrs, area_rngs, num_areas, dt_match, dt_ignore, gt_match, gt_ignore, stream);
+}
+
+int mi355det_lvis_match(int64_t num_groups, const int64_t* dt_offsets, const int64_t* gt_offsets, const int64_t* iou_offsets, int64_t num_dt,
+                        int64_t num_gt, int64_t iou_size, const double* iou, const double* dt_area, const double* gt_area,
+                        const uint8_t* gt_flag, const uint8_t* group_not_exhaustive, const double* iou_thrs, int32_t num_thrs,
+                        const double* area_rngs, int32_t num_areas, int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore,
+                        void* stream) {
+  return match_entry("lvis_match", true, num_groups, dt_offsets, gt_offsets, iou_offsets, num_dt, num_gt, iou_size, iou, dt_area, gt_area,
+                     gt_flag, group_not_exhaustive, iou_thrs, num_thrs, area_rngs, num_areas, dt_match, dt_ignore, gt_match, gt_ignore, stream);
 }
 
 int mi355det_coco_accumulate(int32_t num_cats, const int64_t* cat_dt_offsets, const int64_t* cat_gt_offsets, int64_t num_dt, int64_t num_gt,

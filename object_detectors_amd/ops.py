@@ -982,6 +982,27 @@ def coco_match(dt_offsets, gt_offsets, iou_offsets, iou, dt_area, gt_area, gt_cr
     return dt_match, dt_ignore, gt_match, gt_ignore
 
 
+def lvis_match(dt_offsets, gt_offsets, iou_offsets, iou, dt_area, gt_area, gt_flag, group_not_exhaustive, iou_thrs, area_rngs):
+    """mi355det_lvis_match (the match under LVISEval's rules: gt_flag uint8 [NG] = the annotations' ignore flags, group_not_exhaustive uint8
+    [groups]) -> the four arrays of coco_match, same layouts."""
+    dev = iou.device
+    if not (iou.is_cuda and group_not_exhaustive.is_cuda):
+        raise ValueError("lvis_match needs CUDA/HIP tensors (no CPU fallback)")
+    ng, nd, ngt = int(dt_offsets.shape[0]) - 1, int(dt_area.shape[0]), int(gt_area.shape[0])
+    if group_not_exhaustive.dtype != torch.uint8 or int(group_not_exhaustive.shape[0]) != ng:
+        raise ValueError("lvis_match: group_not_exhaustive must be uint8, one flag per group")
+    nel = group_not_exhaustive.contiguous()
+    T, A = int(iou_thrs.shape[0]), int(area_rngs.shape[0])
+    dt_match = torch.zeros((A, T, nd), dtype=torch.int32, device=dev)
+    dt_ignore = torch.zeros((A, T, nd), dtype=torch.uint8, device=dev)
+    gt_match = torch.zeros((A, T, ngt), dtype=torch.int32, device=dev)
+    gt_ignore = torch.zeros((A, ngt), dtype=torch.uint8, device=dev)
+    check(lib().mi355det_lvis_match(ng, ptr(dt_offsets), ptr(gt_offsets), ptr(iou_offsets), nd, ngt, int(iou.shape[0]), ptr(iou), ptr(dt_area),
+                                    ptr(gt_area), ptr(gt_flag), ptr(nel), ptr(iou_thrs), T, ptr(area_rngs), A,
+                                    ptr(dt_match), ptr(dt_ignore), ptr(gt_match), ptr(gt_ignore), stream_ptr()), "lvis_match")
+    return dt_match, dt_ignore, gt_match, gt_ignore
+
+
 def coco_accumulate(cat_dt_offsets, cat_gt_offsets, order, dt_rank, dt_score, dt_match, dt_ignore, gt_ignore, max_dets, rec_thrs):
     """mi355det_coco_accumulate -> precision [T, R, K, A, M], recall [T, K, A, M], scores [T, R, K, A, M] (float64)."""
     dev = rec_thrs.device
