@@ -778,6 +778,59 @@ int mi355det_mask_rle_emit(const float* dense, const float* masks, const float* 
 int64_t mi355det_rle_to_string(const int32_t* counts, int64_t n, char* out, int64_t cap);
 int64_t mi355det_rle_from_string(const char* s, int32_t* counts, int64_t cap);
 
+/* ---- Polygon ground truth as COCO run-length encodings (csrc/poly_kernels.hip; torchvision_models/detection/coco_utils.py:33-47
+ * convert_coco_poly_to_mask = pycocotools frPyObjects + decode + any over the parts).  One polygon is k >= 3 points xy (float64, x then y);
+ * its annotation's image is h x w.  The rules of pycocotools rleFrPoly, then rleMerge as a union:
+ *   scale     X[j] = (int)(5*x[j] + .5), Y[j] likewise (the C cast: truncation toward zero, also for negatives); X[k] = X[0] closes the ring.
+ *   walk      every edge j -> j+1: dx = |xe-xs|, dy = |ye-ys|, flip = (dx >= dy && xs > xe) || (dx < dy && ys > ye), the end points swapped
+ *             when flipped, s = dx >= dy ? (double)(ye-ys)/dx : (double)(xe-xs)/dy.  dx >= dy: for d = 0..dx, t = flip ? dx-d : d,
+ *             u = t + xs, v = (int)(ys + s*t + .5).  Otherwise for d = 0..dy, t = flip ? dy-d : d, v = t + ys, u = (int)(xs + s*t + .5).
+ *             The edges' points one after the other; a zero-length edge gives its one point.
+ *   points    each consecutive pair with u[j] != u[j-1]: xd = u[j] < u[j-1] ? u[j] : u[j]-1, xd = (xd+.5)/5 - .5, dropped unless
+ *             floor(xd) == xd and 0 <= xd <= w-1; yd = min(v[j], v[j-1]), yd = (yd+.5)/5 - .5, clamped to [0, h], then ceil;
+ *             a = (int)xd*h + (int)yd.
+ *   runs      h*w appended, sorted, differences (the first from 0): the first difference is the first count, a positive one the next count,
+ *             a zero one is skipped and the difference after it added to the last count.  Equivalently the run boundaries are the
+ *             positions below h*w that occur an odd number of times, which is what the kernels use.
+ *   union     an annotation's mask is the union of its parts' masks, canonical (no zero count except possibly the first); without parts
+ *             it is the all-zero mask [h*w].
+ * All arithmetic is float64 without contraction, divisions IEEE.  The caller validates the input (finite coordinates, |c| < 2^24, k >= 3,
+ * h, w >= 1, h*w < 2^31, rising offsets): the kernels only promise to write nothing outside the stated capacities.
+ * Tables ON THE DEVICE: xy float64 [2 * points]; poly_offsets int64 [num_polys + 1] in points; ann_offsets int64 [num_anns + 1] in polygons
+ * (annotation a owns the polygons ann_offsets[a]..ann_offsets[a + 1]); sizes int32 [num_anns, 2] = [h, w], which may differ between
+ * annotations.
+ *   poly_points_count  point_offsets int64 [num_polys + 1]: the index of polygon p's first kept point, [num_polys] = their number.
+ *   poly_points_emit   keys int64 [total_points] = polygon index << 32 | a, each polygon's in its slots in a fixed order.  total_points is
+ *                      the caller's host copy of point_offsets[num_polys].  THE CALLER SORTS the keys ascending before the passes below.
+ *   poly_events        for every polygon of an annotation with two or more parts: its r-th run boundary (rising) as the event
+ *                      annotation << 32 | position << 1 | (r & 1) at events[event_base[p] + r]; the rest of the polygon's
+ *                      point_offsets[p + 1] - point_offsets[p] slots is filled with INT64_MAX.  event_base int64 [num_polys] (the caller's
+ *                      exclusive sum of the point counts of such polygons; < 0 = skip).  toggle_offsets int64 [num_polys + 1]: the
+ *                      exclusive sum of the events per polygon.  THE CALLER SORTS events ascending.
+ *   poly_runs_count    run_offsets int64 [num_anns + 1], as mi355det_mask_rle_count gives them.
+ *   poly_runs_emit     counts int32 [run_offsets[num_anns]], area int64 [num_anns] and bbox int32 [num_anns, 4] (nullable) as
+ *                      mi355det_mask_rle_emit gives them; a run of ones that goes on into the next column makes the box span y = 0..h-1.
+ *                      capacity < total_runs is an error and no count is written at an index >= capacity.
+ *   rle_decode         counts + run_offsets [num_masks + 1] (ON THE DEVICE) of masks of one size -> uint8 [num_masks, im_h, im_w] row-major,
+ *                      1 inside the odd-indexed runs; counts past im_h*im_w are cut there.
+ * No atomics; every output is bit-identical from run to run.  No entry point needs a workspace. */
+int mi355det_poly_points_count(const double* xy, const int64_t* poly_offsets, const int64_t* ann_offsets, const int32_t* sizes,
+                               int32_t num_polys, int32_t num_anns, int64_t* point_offsets, void* stream);
+int mi355det_poly_points_emit(const double* xy, const int64_t* poly_offsets, const int64_t* ann_offsets, const int32_t* sizes,
+                              int32_t num_polys, int32_t num_anns, const int64_t* point_offsets, int64_t total_points, int64_t* keys,
+                              int64_t capacity, void* stream);
+int mi355det_poly_events(const int64_t* keys, const int64_t* point_offsets, const int64_t* ann_offsets, const int32_t* sizes,
+                         const int64_t* event_base, int32_t num_polys, int32_t num_anns, int64_t* events, int64_t capacity,
+                         int64_t* toggle_offsets, void* stream);
+int mi355det_poly_runs_count(const int64_t* keys, const int64_t* point_offsets, const int64_t* events, const int64_t* toggle_offsets,
+                             const int64_t* ann_offsets, const int32_t* sizes, int32_t num_polys, int32_t num_anns, int64_t* run_offsets,
+                             void* stream);
+int mi355det_poly_runs_emit(const int64_t* keys, const int64_t* point_offsets, const int64_t* events, const int64_t* toggle_offsets,
+                            const int64_t* ann_offsets, const int32_t* sizes, int32_t num_polys, int32_t num_anns, const int64_t* run_offsets,
+                            int64_t total_runs, int32_t* counts, int64_t capacity, int64_t* area, int32_t* bbox, void* stream);
+int mi355det_rle_decode(const int32_t* counts, const int64_t* run_offsets, int32_t num_masks, int32_t im_h, int32_t im_w, uint8_t* out,
+                        void* stream);
+
 /* ---- COCO evaluation (csrc/cocoeval_kernels.hip): pycocotools maskUtils.iou, COCOeval.evaluateImg and COCOeval.accumulate for `bbox` and
  * `segm`.  A group is one (image, category) pair: D detections in descending score order (stable, cut to the largest maxDets by the caller)
  * and G ground truths in annotation order.  dt_offsets / gt_offsets / iou_offsets [num_groups + 1] int64 ON THE DEVICE: group j owns the

@@ -930,6 +930,130 @@ def mask_rle_paste(masks, boxes, img_shape, padding=1, threshold=0.5, capacity=N
     return _mask_rle(None, m, b, D, M, int(padding), H, W, float(threshold), m.device, capacity)
 
 
+# ---- COCO polygons as run lengths, and run lengths as bitmaps (csrc/poly_kernels.hip; the readers on top are object_detectors_amd/polygons.py)
+POLY_MAX_COORD = float(1 << 24)
+
+
+def _poly_tables(xy, poly_offsets, ann_offsets, sizes):
+    """The host side of poly_rle's contract: every refusal is a ValueError before anything reaches the device."""
+    import numpy as np
+    po = np.ascontiguousarray(poly_offsets, dtype=np.int64).reshape(-1)
+    ao = np.ascontiguousarray(ann_offsets, dtype=np.int64).reshape(-1)
+    sz = np.ascontiguousarray(sizes, dtype=np.int64).reshape(-1, 2)
+    if po.size < 1 or po[0] != 0 or ao.size < 1 or ao[0] != 0:
+        raise ValueError("poly_rle: offsets must begin with 0")
+    if (np.diff(po) < 3).any():
+        raise ValueError("poly_rle: a polygon needs at least 3 points")
+    if (np.diff(ao) < 0).any() or ao[-1] != po.size - 1:
+        raise ValueError("poly_rle: ann_offsets must rise from 0 to the number of polygons")
+    if sz.shape[0] != ao.size - 1:
+        raise ValueError("poly_rle: sizes must be [number of annotations, 2]")
+    if (sz < 1).any() or (sz[:, 0] * sz[:, 1] >= (1 << 31)).any():
+        raise ValueError("poly_rle: every size needs h, w >= 1 and h*w < 2^31")
+    if po.size - 1 >= (1 << 31) or ao.size - 1 >= (1 << 31):
+        raise ValueError("poly_rle: too many polygons")
+    n = int(xy.numel()) if torch.is_tensor(xy) else int(np.asarray(xy).size)
+    if n != 2 * int(po[-1]):
+        raise ValueError("poly_rle: xy must hold 2 coordinates per point of poly_offsets")
+    if torch.is_tensor(xy):
+        bad = n > 0 and not bool((torch.isfinite(xy) & (xy.abs() < POLY_MAX_COORD)).all())
+    else:
+        xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1)
+        bad = n > 0 and not bool((np.isfinite(xy) & (np.abs(xy) < POLY_MAX_COORD)).all())
+    if bad:
+        raise ValueError("poly_rle: every coordinate must be finite with |c| < 2^24")
+    return xy, po, ao, sz.astype(np.int32)
+
+
+def poly_rle(xy, poly_offsets, ann_offsets, sizes, capacity=None, device=None, mark=None, out=None):
+    """pycocotools merge(frPyObjects(polygons, h, w)) of many annotations at once (mi355det_poly_*): xy float64 [2 * points] (host array, or
+    a tensor already on the device), poly_offsets [NP + 1] in points, ann_offsets [A + 1] in polygons and sizes [A, 2] = [h, w] on the host
+    -> (counts int32 on the device, run_offsets host list [A + 1], area int64 [A], bbox int32 [A, 4]).  Two host reads: the point offsets
+    (they size the keys) and the run offsets (they size the counts).  `capacity` (elements of the counts buffer) defaults to the exact size; `out` is a counts buffer of the caller's;
+    `mark(name)` is called after the stages "points", "sort", "events" and "runs" (tools/bench_poly_rle.py times them with it)."""
+    import numpy as np
+    xy, po, ao, sz = _poly_tables(xy, poly_offsets, ann_offsets, sizes)
+    NP, A = int(po.size) - 1, int(ao.size) - 1
+    dev = xy.device if torch.is_tensor(xy) and xy.is_cuda else torch.device("cuda" if device is None else device)
+    mark = mark or (lambda name: None)
+    i64 = dict(dtype=torch.int64, device=dev)
+    if A == 0:
+        return (torch.empty(0, dtype=torch.int32, device=dev), [0], torch.empty(0, **i64), torch.empty((0, 4), dtype=torch.int32, device=dev))
+    L = lib()
+    d_xy = torch.as_tensor(xy, dtype=torch.float64).to(dev).contiguous().reshape(-1)
+    d_po, d_ao, d_sz = torch.from_numpy(po).to(dev), torch.from_numpy(ao).to(dev), torch.from_numpy(sz).to(dev)
+    keys = events = pt_off = tog_off = None
+    if NP > 0:
+        tables = (ptr(d_po), ptr(d_ao), ptr(d_sz), NP, A)
+        pt_off = torch.empty(NP + 1, **i64)
+        check(L.mi355det_poly_points_count(ptr(d_xy), *tables, ptr(pt_off), stream_ptr()), "poly_points_count")
+        pts = pt_off.cpu().numpy()                         # host read 1 of 2
+        total = int(pts[-1])
+        keys = torch.empty(total, **i64)
+        check(L.mi355det_poly_points_emit(ptr(d_xy), *tables, ptr(pt_off), total, ptr(keys), total, stream_ptr()), "poly_points_emit")
+        mark("points")
+        keys = torch.sort(keys).values
+        mark("sort")
+        # the parts of annotations with two or more parts become coverage events; their slots are sized by their point counts
+        parts = np.diff(ao)
+        multi = np.repeat(parts >= 2, parts)
+        slots = np.where(multi, np.diff(pts), 0)
+        base = np.where(multi, np.cumsum(slots) - slots, -1).astype(np.int64)
+        cap_ev = int(slots.sum())
+        events = torch.empty(cap_ev, **i64)
+        tog_off = torch.empty(NP + 1, **i64)
+        check(L.mi355det_poly_events(ptr(keys), ptr(pt_off), ptr(d_ao), ptr(d_sz), ptr(torch.from_numpy(base).to(dev)), NP, A, ptr(events),
+                                     cap_ev, ptr(tog_off), stream_ptr()), "poly_events")
+        if cap_ev:
+            events = torch.sort(events).values
+        mark("events")
+    src = (ptr(keys), ptr(pt_off), ptr(events), ptr(tog_off), ptr(d_ao), ptr(d_sz), NP, A)
+    run_offsets = torch.empty(A + 1, **i64)
+    check(L.mi355det_poly_runs_count(*src, ptr(run_offsets), stream_ptr()), "poly_runs_count")
+    offsets = run_offsets.tolist()                         # host read 2 of 2
+    total = offsets[-1]
+    cap = total if capacity is None else int(capacity)
+    if out is None:
+        counts = torch.empty(max(cap, 0), dtype=torch.int32, device=dev)
+    else:                                                  # the caller's buffer: nothing is written at or past `capacity`
+        counts = out
+        if counts.dtype != torch.int32 or counts.device != d_ao.device or not counts.is_contiguous() or counts.numel() < cap:
+            raise ValueError("poly_rle: out must be a contiguous int32 device tensor of at least `capacity` elements")
+    area = torch.empty(A, **i64)
+    bbox = torch.empty((A, 4), dtype=torch.int32, device=dev)
+    check(L.mi355det_poly_runs_emit(*src, ptr(run_offsets), total, ptr(counts), cap, ptr(area), ptr(bbox), stream_ptr()), "poly_runs_emit")
+    mark("runs")
+    return counts, offsets, area, bbox
+
+
+def mask_rle_decode(batch_or_counts, run_offsets=None, size=None):
+    """Run lengths -> bitmaps uint8 [D, H, W] on the device (mi355det_rle_decode): an RLEBatch whose counts are on the device, or device
+    counts int32 with run_offsets [D + 1] (host list or tensor) and size = (H, W).  = RLEBatch.decode() without the host."""
+    from .rle import RLEBatch
+    if isinstance(batch_or_counts, RLEBatch):
+        counts, run_offsets, size = batch_or_counts.counts, batch_or_counts.offsets, batch_or_counts.size
+    else:
+        counts = batch_or_counts
+    if run_offsets is None or size is None:
+        raise ValueError("mask_rle_decode: counts need run_offsets and size")
+    if not torch.is_tensor(counts) or not counts.is_cuda:
+        raise ValueError("mi355det ops need CUDA/HIP tensors (no CPU fallback)")
+    H, W = int(size[0]), int(size[1])
+    if not torch.is_tensor(run_offsets):
+        off = [int(o) for o in run_offsets]
+        if not off or off[0] != 0 or off[-1] > int(counts.shape[0]) or any(b < a for a, b in zip(off, off[1:])):
+            raise ValueError("mask_rle_decode: run_offsets must rise from 0 and stay within counts")
+        run_offsets = torch.tensor(off, dtype=torch.int64)
+    run_offsets = run_offsets.to(device=counts.device, dtype=torch.int64).contiguous()
+    D = int(run_offsets.shape[0]) - 1
+    if D < 0:
+        raise ValueError("mask_rle_decode: run_offsets must hold D + 1 entries")
+    c = counts.to(torch.int32).contiguous()
+    out = torch.empty((D, H, W), dtype=torch.uint8, device=c.device)
+    check(lib().mi355det_rle_decode(ptr(c), ptr(run_offsets), D, H, W, ptr(out), stream_ptr()), "rle_decode")
+    return out
+
+
 # ---- COCO evaluation (csrc/cocoeval_kernels.hip; the evaluator on top of these is object_detectors_amd/cocoeval.py)
 def _f64c(t, dev):
     return torch.as_tensor(t, dtype=torch.float64, device=dev).contiguous()
