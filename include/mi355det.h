@@ -688,6 +688,39 @@ int mi355det_resize_bilinear(const float* in, int32_t planes, int32_t c, int32_t
 int mi355det_resize_boxes(const float* boxes, float* out, int64_t n, int32_t orig_h, int32_t orig_w, int32_t new_h, int32_t new_w,
                           void* stream);
 
+/* ---- batched uint8 ingest (csrc/transform_kernels.hip): decoded images to the padded batch in one launch ---------------------
+ * The route of GeneralizedRCNNTransform for images as a decoder hands them over: uint8 [h, w, 3] (HWC), any sizes, packed back to back
+ * into one buffer.  One table entry per image; the same table is read by the host checks (`table`, host memory) and by the kernels
+ * (`table_dev`, the caller's device copy of it).
+ *   ingest_u8          out fp32 [n, 3, pad_h, pad_w], every element written once (zeros outside [out_h, out_w]): the horizontal flip of
+ *                      detection/transforms.py:30-34 (a flipped image reads source column w - 1 - x), ToTensor's byte / 255 (a correctly
+ *                      rounded division), normalize, bilinear resize and batch_images with the arithmetic of mi355det_resize_bilinear
+ *                      (one blend function serves both), so the result equals, bit for bit, mi355det_resize_bilinear of the flipped float
+ *                      image.  A block owns tiles of MI355DET_INGEST_TILE_H x MI355DET_INGEST_TILE_W output pixels of one image and finds
+ *                      the image by a search of first_tile; image i owns the tiles [first_tile[i], first_tile[i] + mi355det_ingest_tiles).
+ *                      mean / stdv: device fp32 [3].  EINVAL for n <= 0, a null pointer, h, w, out_h, out_w <= 0, pad < out, an image
+ *                      that does not lie inside [0, packed_bytes) or a first_tile column that is not i * mi355det_ingest_tiles(pad_h,
+ *                      pad_w) (0 when the count does not fit).
+ *   flip_resize_boxes  all images' boxes in one launch: boxes [g, 4] xyxy concatenated, box_offsets int64 [n + 1] on the device (image i
+ *                      owns rows [box_offsets[i], box_offsets[i + 1])).  Where the image is flipped, x0' = w - x2 and x2' = w - x0 in
+ *                      float32 (transforms.py:37); then the ratio multiply of mi355det_resize_boxes with the same float32 ratios
+ *                      out / in.  g == 0 is a no-op. */
+#define MI355DET_INGEST_TILE_H 16
+#define MI355DET_INGEST_TILE_W 64
+typedef struct {
+  int64_t offset;     /* byte offset of the image's [h, w, 3] bytes in the packed buffer */
+  int32_t h, w;       /* source size */
+  int32_t out_h, out_w; /* resized size, <= the pad */
+  int32_t flip;       /* != 0: mirrored left to right */
+  int32_t first_tile; /* index of the image's first tile in the launch */
+} mi355det_ingest_image;
+int32_t mi355det_ingest_tiles(int32_t pad_h, int32_t pad_w);
+int mi355det_ingest_u8(const uint8_t* packed, int64_t packed_bytes, const mi355det_ingest_image* table,
+                       const mi355det_ingest_image* table_dev, int32_t n, const float* mean, const float* stdv, float* out, int32_t pad_h,
+                       int32_t pad_w, void* stream);
+int mi355det_flip_resize_boxes(const float* boxes, float* out, int64_t g, const int64_t* box_offsets,
+                               const mi355det_ingest_image* table_dev, int32_t n, void* stream);
+
 /* ---- output side: detections -> the numbers of the COCO json dicts (csrc/transform_kernels.hip) ----------
  * yolo/procedures/test_one_epoch.py:41-66 (scale = 1): boxes rows (x1,y1,x2,y2,...) with pitch box_ld in network pixels ->
  *   bbox_xywh [k,4] = (x1/inp_dim*W, y1/inp_dim*H, w, h) in the original image, area [k] = w*h, category_id [k] from the label column
@@ -743,6 +776,9 @@ int mi355det_mask_probs(const void* feat, int32_t feat_ld, const float* w_logits
                         int32_t num_classes, float* probs, void* stream);
 int mi355det_mask_resize_nearest(const uint8_t* in, int32_t planes, int32_t h, int32_t w, uint8_t* out, int32_t out_h, int32_t out_w,
                                  void* stream);
+/* mask_resize_nearest of masks.flip(-1) when flip != 0 (detection/transforms.py:38-39 ahead of the resize): source column w - 1 - x. */
+int mi355det_mask_flip_resize_nearest(const uint8_t* in, int32_t planes, int32_t h, int32_t w, uint8_t* out, int32_t out_h, int32_t out_w,
+                                      int32_t flip, void* stream);
 int mi355det_paste_masks(const float* masks, const float* boxes, int32_t num_masks, int32_t m, int32_t padding, int32_t im_h, int32_t im_w,
                          float* out, void* stream);
 

@@ -55,6 +55,14 @@ class MaskImages(C.Structure):
     _fields_ = [("masks", vp * MASK_MAX_IMAGES), ("h", i32 * MASK_MAX_IMAGES), ("w", i32 * MASK_MAX_IMAGES), ("n_images", i32)]
 
 
+INGEST_TILE_H, INGEST_TILE_W = 16, 64
+
+
+class IngestImage(C.Structure):
+    """mi355det_ingest_image: one uint8 [h, w, 3] image of a packed batch (mi355det_ingest_u8, mi355det_flip_resize_boxes)."""
+    _fields_ = [("offset", i64), ("h", i32), ("w", i32), ("out_h", i32), ("out_w", i32), ("flip", i32), ("first_tile", i32)]
+
+
 class PackItem(C.Structure):
     _fields_ = [("w", vp), ("w_fwd", vp), ("w_dgrad", vp), ("shape", ConvShape), ("cout_pad", i32), ("w_is_ohwi", i32)]
 
@@ -173,6 +181,9 @@ PROTOTYPES = {
     "mi355det_topk_ws": (C.c_int, [vp, i32, i64, i64, i32, C.c_float, vp, vp, vp, vp, sz, vp]),
     "mi355det_resize_bilinear": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp]),
     "mi355det_resize_boxes": (C.c_int, [vp, vp, i64, i32, i32, i32, i32, vp]),
+    "mi355det_ingest_tiles": (i32, [i32, i32]),
+    "mi355det_ingest_u8": (C.c_int, [vp, i64, vp, vp, i32, vp, vp, vp, i32, i32, vp]),
+    "mi355det_flip_resize_boxes": (C.c_int, [vp, vp, i64, vp, vp, i32, vp]),
     "mi355det_coco_rows": (C.c_int, [vp, i32, vp, vp, i32, i64, f32, f32, f32, i32, i32, vp, vp, vp, vp]),
     "mi355det_fastrcnn_loss_workspace": (sz, [i32]),
     "mi355det_fastrcnn_loss": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
@@ -182,6 +193,7 @@ PROTOTYPES = {
     "mi355det_mask_loss": (C.c_int, [vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "mi355det_mask_probs": (C.c_int, [vp, i32, vp, vp, vp, i32, i32, vp, vp]),
     "mi355det_mask_resize_nearest": (C.c_int, [vp, i32, i32, i32, vp, i32, i32, vp]),
+    "mi355det_mask_flip_resize_nearest": (C.c_int, [vp, i32, i32, i32, vp, i32, i32, i32, vp]),
     "mi355det_paste_masks": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp, vp]),
     "mi355det_mask_rle_workspace": (sz, [i32, i32]),
     "mi355det_mask_rle_count": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, sz, vp]),

@@ -5,7 +5,8 @@
 //                        defaults sampling_ratio = -1 (adaptive) and aligned = False, on the uint8 masks of every image in one launch.
 //   mask_loss            mask_fcn_logits (1x1, 256 -> K) restricted to the label channel + binary_cross_entropy_with_logits(mean), fused,
 //                        with every gradient the backward needs; mask_probs is its forward-only form (maskrcnn_inference).
-//   mask_resize_nearest  F.interpolate(mask[:, None].float(), ..., mode='nearest')[:, 0].byte() with torch's source-index rule.
+//   mask_resize_nearest  F.interpolate(mask[:, None].float(), ..., mode='nearest')[:, 0].byte() with torch's source-index rule; with the
+//                        flip flag, of masks.flip(-1) (detection/transforms.py:38-39) without the flipped copy.
 //   paste_masks          paste_masks_in_image (expand_masks, expand_boxes, per-box bilinear resize, clipped paste), each output pixel once.
 //
 // The branch's pooling, MultiScaleRoIAlign(['0'..'3'], 14, 2) into the conv layout (mi355det_mask_roi_pool), is the per-sample channels-last
@@ -174,14 +175,16 @@ __device__ __forceinline__ int nearest_src(int dst, int in, int out) {
   return min((int)floorf((float)dst * scale), in - 1);
 }
 
+// flip: the resize of masks.flip(-1) (RandomHorizontalFlip ahead of the transform), source column w - 1 - x
 __global__ __launch_bounds__(256) void mask_resize_nearest_kernel(const uint8_t* __restrict__ in, int planes, int h, int w,
-                                                                  uint8_t* __restrict__ out, int oh, int ow) {
+                                                                  uint8_t* __restrict__ out, int oh, int ow, int flip) {
   const long long total = (long long)planes * oh * ow;
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int x = (int)(i % ow);
     const int y = (int)((i / ow) % oh);
     const long long p = i / ((long long)ow * oh);
-    out[i] = in[(size_t)p * h * w + (size_t)nearest_src(y, h, oh) * w + nearest_src(x, w, ow)];
+    const int sx = nearest_src(x, w, ow);
+    out[i] = in[(size_t)p * h * w + (size_t)nearest_src(y, h, oh) * w + (flip ? w - 1 - sx : sx)];
   }
 }
 
@@ -253,13 +256,19 @@ int mi355det_mask_probs(const void* feat, int32_t feat_ld, const float* w_logits
   return check_launch("mask_probs");
 }
 
-int mi355det_mask_resize_nearest(const uint8_t* in, int32_t planes, int32_t h, int32_t w, uint8_t* out, int32_t out_h, int32_t out_w,
-                                 void* stream) {
+int mi355det_mask_flip_resize_nearest(const uint8_t* in, int32_t planes, int32_t h, int32_t w, uint8_t* out, int32_t out_h, int32_t out_w,
+                                      int32_t flip, void* stream) {
   if (planes < 0 || h <= 0 || w <= 0 || out_h <= 0 || out_w <= 0) return fail(MI355DET_EINVAL, "%s: bad arguments", "mask_resize_nearest");
   if (planes == 0) return MI355DET_OK;
+  if (!in || !out) return fail(MI355DET_EINVAL, "%s: null masks", "mask_resize_nearest");
   const long long total = (long long)planes * out_h * out_w;
-  hipLaunchKernelGGL(mask_resize_nearest_kernel, dim3(grid_for(total)), dim3(256), 0, S(stream), in, planes, h, w, out, out_h, out_w);
+  hipLaunchKernelGGL(mask_resize_nearest_kernel, dim3(grid_for(total)), dim3(256), 0, S(stream), in, planes, h, w, out, out_h, out_w, flip);
   return check_launch("mask_resize_nearest");
+}
+
+int mi355det_mask_resize_nearest(const uint8_t* in, int32_t planes, int32_t h, int32_t w, uint8_t* out, int32_t out_h, int32_t out_w,
+                                 void* stream) {
+  return mi355det_mask_flip_resize_nearest(in, planes, h, w, out, out_h, out_w, 0, stream);
 }
 
 int mi355det_paste_masks(const float* masks, const float* boxes, int32_t num_masks, int32_t m, int32_t padding, int32_t im_h, int32_t im_w,

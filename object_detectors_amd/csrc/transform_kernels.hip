@@ -1,17 +1,36 @@
 // Input-side transform of the detection step: GeneralizedRCNNTransform (torchvision_models/tvision/transform.py:88-226:
 // normalize -> bilinear resize (align_corners=False) -> zero-pad into the batch tensor), resize_boxes (:279-293) and the YOLO multi-scale
 // F.interpolate (yolo/procedures/train_one_epoch.py:64-69).  HBM-bound: every output element is written once, every input element read ~once
-// (the four taps of neighbouring outputs hit the same lines).
+// (the four taps of neighbouring outputs hit the same lines).  The uint8 route (mi355det_ingest_u8, mi355det_flip_resize_boxes) does the
+// same for a whole batch of decoded HWC images in one launch each, with the horizontal flip of detection/transforms.py:30-44 folded in.
 #include "common.h"
 
 using namespace mi355;
 
 namespace {
 
-// out[p][y][x] for planes p of one image (or of a same-size batch): bilinear sample of (in - mean[p % c]) / std[p % c], zero outside [oh, ow].
-// Index and weight arithmetic follow ATen's upsample_bilinear2d (area_pixel_compute_source_index, align_corners = false):
+// One axis of ATen's upsample_bilinear2d (area_pixel_compute_source_index, align_corners = false):
 //   src = max(scale * (dst + 0.5) - 0.5, 0), i0 = (int)src, i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1
+struct Taps {
+  int i0, i1;
+  float l0, l1;
+};
+__device__ __forceinline__ Taps bilinear_taps(float scale, int dst, int in) {
+  const float s = fmaxf(scale * ((float)dst + 0.5f) - 0.5f, 0.0f);
+  Taps t;
+  t.i0 = (int)s;
+  t.i1 = t.i0 + (t.i0 < in - 1 ? 1 : 0);
+  t.l1 = s - (float)t.i0;
+  t.l0 = 1.0f - t.l1;
+  return t;
+}
+// The four-tap blend, for the float route (resize_bilinear_kernel) and the uint8 route (ingest_u8_kernel) alike:
 //   val = h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11)
+__device__ __forceinline__ float bilinear_blend(float v00, float v01, float v10, float v11, const Taps& ty, const Taps& tx) {
+  return ty.l0 * (tx.l0 * v00 + tx.l1 * v01) + ty.l1 * (tx.l0 * v10 + tx.l1 * v11);
+}
+
+// out[p][y][x] for planes p of one image (or of a same-size batch): bilinear sample of (in - mean[p % c]) / std[p % c], zero outside [oh, ow].
 __global__ __launch_bounds__(256) void resize_bilinear_kernel(const float* __restrict__ in, int planes, int c, int h, int w, const float* __restrict__ mean,
                                                               const float* __restrict__ stdv, float* __restrict__ out, int oh, int ow, int ph, int pw,
                                                               float rh, float rw) {
@@ -22,12 +41,10 @@ __global__ __launch_bounds__(256) void resize_bilinear_kernel(const float* __res
     const int y = (int)(t % ph), p = (int)(t / ph);
     float v = 0.0f;
     if (y < oh && x < ow) {
-      const float sy = fmaxf(rh * ((float)y + 0.5f) - 0.5f, 0.0f), sx = fmaxf(rw * ((float)x + 0.5f) - 0.5f, 0.0f);
-      const int y0 = (int)sy, x0 = (int)sx;
-      const int y1 = y0 + (y0 < h - 1 ? 1 : 0), x1 = x0 + (x0 < w - 1 ? 1 : 0);
-      const float h1 = sy - (float)y0, h0 = 1.0f - h1, w1 = sx - (float)x0, w0 = 1.0f - w1;
+      const Taps ty = bilinear_taps(rh, y, h), tx = bilinear_taps(rw, x, w);
       const float* src = in + (size_t)p * h * w;
-      float v00 = src[(size_t)y0 * w + x0], v01 = src[(size_t)y0 * w + x1], v10 = src[(size_t)y1 * w + x0], v11 = src[(size_t)y1 * w + x1];
+      float v00 = src[(size_t)ty.i0 * w + tx.i0], v01 = src[(size_t)ty.i0 * w + tx.i1], v10 = src[(size_t)ty.i1 * w + tx.i0],
+            v11 = src[(size_t)ty.i1 * w + tx.i1];
       if (mean) {
         const float m = mean[p % c], s = stdv[p % c];
         v00 = (v00 - m) / s;
@@ -35,9 +52,67 @@ __global__ __launch_bounds__(256) void resize_bilinear_kernel(const float* __res
         v10 = (v10 - m) / s;
         v11 = (v11 - m) / s;
       }
-      v = h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11);
+      v = bilinear_blend(v00, v01, v10, v11, ty, tx);
     }
     out[i] = v;
+  }
+}
+
+// The same for a batch of uint8 HWC images of any sizes, packed back to back, in one launch (table: include/mi355det.h).  A block walks
+// tiles of TILE_H x TILE_W output pixels; a thread owns four neighbouring pixels of one row for all three channels, so each of its sixteen
+// taps is three neighbouring bytes and each plane's store is 16 bytes per lane (VEC: pw % 4 == 0 and out 16-byte aligned; else dwords).
+// The normalised value of a byte, ((float)b / 255.0f - mean) / std, has 256 values per channel: a block computes them once into LDS with
+// the two correctly rounded divisions of the float route and looks the taps up, instead of 24 divisions per pixel.  The bytes are plain
+// byte-indexed loads without an alignment assumption (rows are 3w bytes); the taps of neighbouring pixels share cache lines.
+constexpr int TILE_H = MI355DET_INGEST_TILE_H, TILE_W = MI355DET_INGEST_TILE_W;
+static_assert(TILE_H * (TILE_W / 4) == 256, "one thread per four pixels of a tile");
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void ingest_u8_kernel(const uint8_t* __restrict__ packed, const mi355det_ingest_image* __restrict__ table, int n,
+                                                        int tiles_x, int total_tiles, const float* __restrict__ mean,
+                                                        const float* __restrict__ stdv, float* __restrict__ out, int ph, int pw) {
+  __shared__ float lut[3][256];
+  for (int e = threadIdx.x; e < 3 * 256; e += 256) lut[e >> 8][e & 255] = ((float)(e & 255) / 255.0f - mean[e >> 8]) / stdv[e >> 8];
+  __syncthreads();
+  const int lx = (threadIdx.x % (TILE_W / 4)) * 4, ly = threadIdx.x / (TILE_W / 4);
+  const long long plane = (long long)ph * pw;
+  for (int tile = blockIdx.x; tile < total_tiles; tile += gridDim.x) {
+    int lo = 0, hi = n - 1;                                  // block-uniform: the last image whose first tile is <= tile
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (table[mid].first_tile <= tile) lo = mid; else hi = mid - 1;
+    }
+    const mi355det_ingest_image im = table[lo];
+    const int t = tile - im.first_tile;
+    const int y = (t / tiles_x) * TILE_H + ly, x = (t % tiles_x) * TILE_W + lx;
+    if (y >= ph || x >= pw) continue;
+    float v[3][4] = {};
+    if (y < im.out_h && x < im.out_w) {
+      const float rh = (float)im.h / (float)im.out_h, rw = (float)im.w / (float)im.out_w;
+      const Taps ty = bilinear_taps(rh, y, im.h);
+      const uint8_t* r0 = packed + im.offset + (long long)ty.i0 * im.w * 3;
+      const uint8_t* r1 = packed + im.offset + (long long)ty.i1 * im.w * 3;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (x + j >= im.out_w) continue;
+        const Taps tx = bilinear_taps(rw, x + j, im.w);
+        const int c0 = 3 * (im.flip ? im.w - 1 - tx.i0 : tx.i0), c1 = 3 * (im.flip ? im.w - 1 - tx.i1 : tx.i1);
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          v[c][j] = bilinear_blend(lut[c][r0[c0 + c]], lut[c][r0[c1 + c]], lut[c][r1[c0 + c]], lut[c][r1[c1 + c]], ty, tx);
+      }
+    }
+    float* o = out + ((long long)lo * 3 * ph + y) * pw + x;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if (VEC) {
+        *(float4*)(o + c * plane) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (x + j < pw) o[c * plane + j] = v[c][j];
+      }
+    }
   }
 }
 
@@ -45,6 +120,32 @@ __global__ void resize_boxes_kernel(const float* __restrict__ boxes, float* __re
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n * 4) return;
   out[i] = boxes[i] * ((i & 1) ? ratio_h : ratio_w);       // (xmin, ymin, xmax, ymax): x by the width ratio, y by the height ratio
+}
+
+// One thread per box of the whole batch: RandomHorizontalFlip's `boxes[:, [0, 2]] = width - boxes[:, [2, 0]]` where the image is flipped,
+// then resize_boxes_kernel's multiply with the float32 ratios out / in of the box's image.
+__global__ __launch_bounds__(256) void flip_resize_boxes_kernel(const float* __restrict__ boxes, float* __restrict__ out, long long g,
+                                                                const long long* __restrict__ box_offsets,
+                                                                const mi355det_ingest_image* __restrict__ table, int n) {
+  const long long b = blockIdx.x * 256ll + threadIdx.x;
+  if (b >= g) return;
+  int lo = 0, hi = n - 1;                                    // the last image whose first row is <= b (an image without boxes owns no row)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (box_offsets[mid] <= b) lo = mid; else hi = mid - 1;
+  }
+  const mi355det_ingest_image im = table[lo];
+  const float ratio_h = (float)im.out_h / (float)im.h, ratio_w = (float)im.out_w / (float)im.w;
+  float x0 = boxes[4 * b], x2 = boxes[4 * b + 2];
+  if (im.flip) {
+    const float w = (float)im.w, f0 = w - x2, f2 = w - x0;
+    x0 = f0;
+    x2 = f2;
+  }
+  out[4 * b] = x0 * ratio_w;
+  out[4 * b + 1] = boxes[4 * b + 1] * ratio_h;
+  out[4 * b + 2] = x2 * ratio_w;
+  out[4 * b + 3] = boxes[4 * b + 3] * ratio_h;
 }
 
 }  // namespace
@@ -69,6 +170,45 @@ int mi355det_resize_boxes(const float* boxes, float* out, int64_t n, int32_t ori
   const float rh = (float)new_h / (float)orig_h, rw = (float)new_w / (float)orig_w;
   hipLaunchKernelGGL(resize_boxes_kernel, dim3((int)((n * 4 + 255) / 256)), dim3(256), 0, S(stream), boxes, out, (long long)n, rh, rw);
   return check_launch("resize_boxes");
+}
+
+int32_t mi355det_ingest_tiles(int32_t pad_h, int32_t pad_w) {
+  if (pad_h <= 0 || pad_w <= 0) return 0;
+  const long long t = (long long)((pad_h + TILE_H - 1) / TILE_H) * ((pad_w + TILE_W - 1) / TILE_W);
+  return t > INT32_MAX ? 0 : (int32_t)t;
+}
+
+int mi355det_ingest_u8(const uint8_t* packed, int64_t packed_bytes, const mi355det_ingest_image* table, const mi355det_ingest_image* table_dev,
+                       int32_t n, const float* mean, const float* stdv, float* out, int32_t pad_h, int32_t pad_w, void* stream) {
+  if (n <= 0) return fail(MI355DET_EINVAL, "%s: need n > 0", "ingest_u8");
+  if (!packed || !table || !table_dev || !mean || !stdv || !out) return fail(MI355DET_EINVAL, "%s: null pointer", "ingest_u8");
+  const long long tiles = mi355det_ingest_tiles(pad_h, pad_w);
+  if (tiles <= 0 || tiles * n > INT32_MAX) return fail(MI355DET_EINVAL, "%s: bad pad, or too many tiles for one launch", "ingest_u8");
+  for (int i = 0; i < n; ++i) {
+    const mi355det_ingest_image& im = table[i];
+    if (im.h <= 0 || im.w <= 0 || im.out_h <= 0 || im.out_w <= 0) return fail(MI355DET_EINVAL, "%s: image %lld: sizes must be > 0", "ingest_u8", i);
+    if (pad_h < im.out_h || pad_w < im.out_w) return fail(MI355DET_EINVAL, "%s: image %lld: pad < out", "ingest_u8", i);
+    if (im.offset < 0 || im.offset > packed_bytes || (long long)im.h * im.w * 3 > packed_bytes - im.offset)
+      return fail(MI355DET_EINVAL, "%s: image %lld lies outside the %lld packed bytes", "ingest_u8", i, packed_bytes);
+    if (im.first_tile != i * tiles) return fail(MI355DET_EINVAL, "%s: image %lld: first_tile is not i * %lld", "ingest_u8", i, tiles);
+  }
+  const int total = (int)(tiles * n), grid = min(total, 2048), tiles_x = (pad_w + TILE_W - 1) / TILE_W;
+  if (pad_w % 4 == 0 && ((uintptr_t)out & 15) == 0)
+    hipLaunchKernelGGL(ingest_u8_kernel<true>, dim3(grid), dim3(256), 0, S(stream), packed, table_dev, n, tiles_x, total, mean, stdv, out, pad_h, pad_w);
+  else
+    hipLaunchKernelGGL(ingest_u8_kernel<false>, dim3(grid), dim3(256), 0, S(stream), packed, table_dev, n, tiles_x, total, mean, stdv, out, pad_h, pad_w);
+  return check_launch("ingest_u8");
+}
+
+int mi355det_flip_resize_boxes(const float* boxes, float* out, int64_t g, const int64_t* box_offsets, const mi355det_ingest_image* table_dev,
+                               int32_t n, void* stream) {
+  if (n <= 0 || g < 0) return fail(MI355DET_EINVAL, "%s: need n > 0 and g >= 0", "flip_resize_boxes");
+  if (!box_offsets || !table_dev) return fail(MI355DET_EINVAL, "%s: null table", "flip_resize_boxes");
+  if (g == 0) return MI355DET_OK;
+  if (!boxes || !out) return fail(MI355DET_EINVAL, "%s: null boxes", "flip_resize_boxes");
+  hipLaunchKernelGGL(flip_resize_boxes_kernel, dim3((int)((g + 255) / 256)), dim3(256), 0, S(stream), boxes, out, (long long)g,
+                     (const long long*)box_offsets, table_dev, n);
+  return check_launch("flip_resize_boxes");
 }
 
 }  // extern "C"

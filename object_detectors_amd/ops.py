@@ -860,14 +860,19 @@ def mask_probs(feat, w_logits, b_logits, labels):
     return probs
 
 
-def mask_resize_nearest(masks, size):
-    """F.interpolate(masks[:, None].float(), size, mode='nearest')[:, 0].byte() for uint8 [G, h, w] (transform.py:54-60)."""
+def mask_resize_nearest(masks, size, flip=False):
+    """F.interpolate(masks[:, None].float(), size, mode='nearest')[:, 0].byte() for uint8 [G, h, w] (transform.py:54-60); with `flip`, of
+    masks.flip(-1) (detection/transforms.py:38-39) without the flipped copy."""
     m = masks.to(torch.uint8).contiguous()
     if not m.is_cuda:
         raise ValueError("mask_resize_nearest needs CUDA/HIP tensors (no CPU fallback)")
     oh, ow = int(size[0]), int(size[1])
     out = torch.empty((m.shape[0], oh, ow), dtype=torch.uint8, device=m.device)
-    check(lib().mi355det_mask_resize_nearest(ptr(m), m.shape[0], m.shape[1], m.shape[2], ptr(out), oh, ow, stream_ptr()), "mask_resize_nearest")
+    if flip:
+        check(lib().mi355det_mask_flip_resize_nearest(ptr(m), m.shape[0], m.shape[1], m.shape[2], ptr(out), oh, ow, 1, stream_ptr()),
+              "mask_flip_resize_nearest")
+    else:
+        check(lib().mi355det_mask_resize_nearest(ptr(m), m.shape[0], m.shape[1], m.shape[2], ptr(out), oh, ow, stream_ptr()), "mask_resize_nearest")
     return out
 
 

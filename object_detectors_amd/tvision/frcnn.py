@@ -31,7 +31,7 @@ from .postprocess import (roi_heads_postprocess_detections, roi_heads_postproces
 from .roi_align import MultiScaleRoIAlign
 from .roi_heads import RoIHeadTargets, fastrcnn_loss, minibatch_tfidf
 from .rpn import RPNTargets
-from .transform import GeneralizedRCNNTransform
+from .transform import GeneralizedRCNNTransform, ImageList, ingested_sizes
 
 
 # Route switches, module attributes on purpose: the composed routes stay as the bit-exact references of tests/test_gpu_proposals.py and
@@ -180,7 +180,11 @@ class FasterRCNN(nn.Module):
         if self.training and targets is None:
             raise ValueError("In training mode, targets should be passed")          # generalized_rcnn.py:60-61
         original_image_sizes = None
-        if isinstance(images, (list, tuple)):
+        if isinstance(images, ImageList):              # from transform.ingest: transformed already, and so are the targets
+            original_image_sizes = ingested_sizes(images)
+            images, image_shapes = images.tensors, list(images.image_sizes)
+            self.engine.normalize = False
+        elif isinstance(images, (list, tuple)):
             original_image_sizes = [(int(i.shape[-2]), int(i.shape[-1])) for i in images]      # generalized_rcnn.py:72-76
             self.transform.train(self.training)
             image_list, targets = self.transform(images, targets)                              # generalized_rcnn.py:78

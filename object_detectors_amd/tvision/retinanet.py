@@ -15,7 +15,7 @@ from torch import nn
 
 from .engine import IMAGE_MEAN, IMAGE_STD, RetinaNetEngine
 from .postprocess import retinanet_postprocess_detections
-from .transform import GeneralizedRCNNTransform
+from .transform import GeneralizedRCNNTransform, ImageList, ingested_sizes
 
 
 class RetinaNet(nn.Module):
@@ -46,7 +46,11 @@ class RetinaNet(nn.Module):
                 if b.dim() != 2 or b.shape[-1] != 4:
                     raise ValueError("Expected target boxes to be a tensor of shape [N, 4], got {:}.".format(b.shape))   # retinanet.py:495-501
         original_image_sizes = None
-        if isinstance(images, (list, tuple)):
+        if isinstance(images, ImageList):              # from transform.ingest: transformed already, and so are the targets
+            original_image_sizes = ingested_sizes(images)
+            images, shapes = images.tensors, images.image_sizes
+            self.engine.normalize = False
+        elif isinstance(images, (list, tuple)):
             original_image_sizes = [(int(i.shape[-2]), int(i.shape[-1])) for i in images]                                # retinanet.py:505-509
             self.transform.train(self.training)
             image_list, targets = self.transform(images, targets)                                                        # retinanet.py:512

@@ -9,24 +9,41 @@ RetinaNet / Faster R-CNN step.
 
 Normalise + resize + pad run as ONE kernel per image (mi355det_resize_bilinear) that writes straight into the image's slot of the padded
 batch; the size arithmetic (float32 scale, floor of the double product) is host logic that follows the reference line by line so the
-output SIZES are identical."""
+output SIZES are identical.
+
+    image_list, targets = transform.ingest(images, targets, flips)      # images: list of uint8 [H,W,3] as a decoder hands them over
+
+is the second route: the horizontal flip of the training preset (tvision/presets.py), ToTensor's / 255, normalise, resize and pad of the
+WHOLE batch in one launch (mi355det_ingest_u8), all boxes in one more (mi355det_flip_resize_boxes); the same bits as `forward` on the
+flipped float images.  `plan_ingest` is its host-side size and layout planning."""
+import collections
+import ctypes
 import math
 
 import numpy as np
 import torch
 
-from .._lib import check, lib, ptr, stream_ptr
+from .._lib import INGEST_TILE_H, INGEST_TILE_W, IngestImage, check, lib, ptr, stream_ptr
 
 
 class ImageList:
-    """tvision/image_list.py:7-27."""
+    """tvision/image_list.py:7-27.  `original_image_sizes` [(H, W)] is set by `GeneralizedRCNNTransform.ingest`: a model given such a list
+    skips its transform and maps the detections back to these frames."""
 
-    def __init__(self, tensors, image_sizes):
+    def __init__(self, tensors, image_sizes, original_image_sizes=None):
         self.tensors = tensors
         self.image_sizes = image_sizes
+        self.original_image_sizes = original_image_sizes
 
     def to(self, device):
-        return ImageList(self.tensors.to(device), self.image_sizes)
+        return ImageList(self.tensors.to(device), self.image_sizes, self.original_image_sizes)
+
+
+def ingested_sizes(image_list):
+    """The original frames of an ImageList a model is called with in place of its images."""
+    if image_list.original_image_sizes is None:
+        raise ValueError("an ImageList given to a model must carry original_image_sizes (GeneralizedRCNNTransform.ingest sets them)")
+    return [(int(h), int(w)) for h, w in image_list.original_image_sizes]
 
 
 def resized_size(h, w, self_min_size, self_max_size):
@@ -63,6 +80,93 @@ def resize_boxes(boxes, original_size, new_size):
     return out
 
 
+def padded_size(sizes, size_divisible):
+    """batch_images (transform.py:215-226): the largest resized image, each side rounded up to a multiple of `size_divisible`."""
+    stride = float(size_divisible)
+    return (int(math.ceil(float(max(s[0] for s in sizes)) / stride) * stride),
+            int(math.ceil(float(max(s[1] for s in sizes)) / stride) * stride))
+
+
+IngestPlan = collections.namedtuple("IngestPlan", "sizes pad offsets nbytes first_tile tiles")
+
+
+def plan_ingest(shapes, min_size, max_size, size_divisible=32, fixed_size=None):
+    """Sizes and layout of one `ingest` call, on the host alone.  shapes: [(H, W)] of the uint8 images; min_size: the min side for all
+    images, or one per image (the training draws).
+        sizes       [(h, w)] of every resized image (`resized_size`, or `fixed_size`)
+        pad         (pad_h, pad_w) of the batch
+        offsets     byte offset of every image in the packed buffer (running sums of 3 * H * W), nbytes their total
+        first_tile  index of every image's first tile of the mi355det_ingest_u8 launch, tiles their total"""
+    n = len(shapes)
+    mins = list(min_size) if isinstance(min_size, (list, tuple)) else [min_size] * n
+    if len(mins) != n:
+        raise ValueError(f"plan_ingest: {len(mins)} min sizes for {n} images")
+    if fixed_size is not None:
+        sizes = [(int(fixed_size[1]), int(fixed_size[0]))] * n
+    else:
+        sizes = [resized_size(int(h), int(w), float(mn), float(max_size)) for (h, w), mn in zip(shapes, mins)]
+    ph, pw = padded_size(sizes, size_divisible)
+    per_image = -(-ph // INGEST_TILE_H) * -(-pw // INGEST_TILE_W)
+    offsets, total = [], 0
+    for h, w in shapes:
+        offsets.append(total)
+        total += 3 * int(h) * int(w)
+    return IngestPlan(sizes, (ph, pw), offsets, total, [i * per_image for i in range(n)], n * per_image)
+
+
+def _checked_ingest_arguments(images, targets, flips):
+    """The refusals of `ingest`, all on the host and ahead of any launch.  Returns the images as tensors, the targets as copied dicts (the
+    caller's dicts and tensors are not modified) and one bool per image."""
+    images = [torch.as_tensor(i) for i in images]
+    n = len(images)
+    if n == 0:
+        raise ValueError("ingest: images is empty")
+    for img in images:
+        if img.dtype != torch.uint8:
+            raise TypeError(f"ingest: expected uint8 images of shape [H, W, 3], but found type {img.dtype}")
+        if img.dim() != 3 or img.shape[-1] != 3 or img.shape[0] < 1 or img.shape[1] < 1:
+            raise ValueError("ingest: images is expected to be a list of uint8 tensors of shape [H, W, 3], got {}".format(tuple(img.shape)))
+    if any(img.device != images[0].device for img in images):
+        raise ValueError("ingest: the images are either all on the CPU or all on one device")
+    flips = [False] * n if flips is None else [bool(f) for f in flips]
+    if len(flips) != n:
+        raise ValueError(f"ingest: {len(flips)} flips for {n} images")
+    if targets is not None:
+        if len(targets) != n:
+            raise ValueError(f"ingest: {len(targets)} targets for {n} images")
+        targets = [dict(t) for t in targets]
+        for t, img in zip(targets, images):
+            if "keypoints" in t:
+                raise ValueError("ingest: targets with keypoints are not supported (there is no keypoint branch on this path)")
+            if "boxes" in t and (t["boxes"].dim() != 2 or t["boxes"].shape[-1] != 4):
+                raise ValueError("Expected target boxes to be a tensor of shape [N, 4], got {:}.".format(tuple(t["boxes"].shape)))
+            if "masks" in t and (t["masks"].dim() != 3 or tuple(t["masks"].shape[-2:]) != tuple(img.shape[:2])):
+                raise ValueError("ingest: masks of shape {} for an image of {}".format(tuple(t["masks"].shape), tuple(img.shape[:2])))
+    return images, targets, flips
+
+
+class _Staging:
+    """Pinned host buffers of `ingest` for one device: the packed pixels, and the image table followed by the box offsets.  An upload from
+    them is asynchronous, so `acquire` waits for the event recorded behind the previous call's copies before the buffers are written again."""
+
+    def __init__(self):
+        self.pixels = self.meta = self.event = None
+
+    def acquire(self, nbytes, nmeta):
+        if self.event is not None:
+            self.event.synchronize()
+        if self.pixels is None or self.pixels.numel() < nbytes:
+            self.pixels = torch.empty(max(nbytes, 1), dtype=torch.uint8, pin_memory=True)
+        if self.meta is None or self.meta.numel() < nmeta:
+            self.meta = torch.empty(nmeta, dtype=torch.uint8, pin_memory=True)
+        return self.pixels, self.meta
+
+    def release(self):
+        if self.event is None:
+            self.event = torch.cuda.Event()
+        self.event.record()
+
+
 class GeneralizedRCNNTransform(torch.nn.Module):
     def __init__(self, min_size, max_size, image_mean, image_std, size_divisible=32, fixed_size=None):
         super().__init__()
@@ -72,6 +176,7 @@ class GeneralizedRCNNTransform(torch.nn.Module):
         self.size_divisible = size_divisible
         self.fixed_size = fixed_size
         self._stats = {}
+        self._staging = {}
 
     def torch_choice(self, k):
         """transform.py:137-145 (same RNG draw as the reference)."""
@@ -99,9 +204,7 @@ class GeneralizedRCNNTransform(torch.nn.Module):
             else:
                 size = float(self.torch_choice(self.min_size)) if self.training else float(self.min_size[-1])
                 sizes.append(resized_size(h, w, size, float(self.max_size)))
-        stride = float(self.size_divisible)
-        ph = int(math.ceil(float(max(s[0] for s in sizes)) / stride) * stride)
-        pw = int(math.ceil(float(max(s[1] for s in sizes)) / stride) * stride)
+        ph, pw = padded_size(sizes, self.size_divisible)
         dev = images[0].device
         c = int(images[0].shape[0])
         mean, std = self._mean_std(dev)
@@ -116,6 +219,76 @@ class GeneralizedRCNNTransform(torch.nn.Module):
             if targets is not None and targets[i] is not None and "masks" in targets[i]:      # transform.py:54-60 (nearest, uint8)
                 targets[i]["masks"] = mask_resize_nearest(targets[i]["masks"], (oh, ow))
         return ImageList(batch, sizes), targets
+
+    def ingest(self, images, targets=None, flips=None, device=None):
+        """The route for images as a decoder hands them over: a list of uint8 [H, W, 3] tensors (or numpy arrays) of any sizes, all on the
+        CPU or all on one device, and one horizontal-flip flag per image (detection/transforms.py:30-44; `presets.DetectionPresetTrain.draw`).
+        Returns what `forward` returns for the flipped float images `img.permute(2, 0, 1).float().div(255)` and their flipped targets, bit
+        for bit, from one image launch (mi355det_ingest_u8) and one box launch (mi355det_flip_resize_boxes) per batch; the ImageList
+        carries `original_image_sizes`.  CPU images are packed into a pinned buffer and go up in one copy (to `device`, default the current
+        one).  Targets are copied: `boxes` and `masks` are transformed, other keys pass through, `keypoints` are refused."""
+        images, targets, flips = _checked_ingest_arguments(images, targets, flips)
+        n = len(images)
+        src_dev = images[0].device
+        shapes = [(int(img.shape[0]), int(img.shape[1])) for img in images]
+        if self.fixed_size is None and self.training:
+            mins = [float(self.torch_choice(self.min_size)) for _ in images]       # one draw per image, in order, as `forward`
+        else:
+            mins = float(self.min_size[-1])
+        plan = plan_ingest(shapes, mins, float(self.max_size), self.size_divisible, self.fixed_size)
+        if src_dev.type != "cpu":
+            dev = src_dev
+        else:
+            dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+
+        table = (IngestImage * n)()
+        for i, ((h, w), (oh, ow)) in enumerate(zip(shapes, plan.sizes)):
+            table[i] = IngestImage(plan.offsets[i], h, w, oh, ow, int(flips[i]), plan.first_tile[i])
+        with_boxes = [i for i in range(n) if targets is not None and "boxes" in targets[i]]
+        box_offsets = np.zeros(n + 1, dtype=np.int64)
+        for i in with_boxes:
+            box_offsets[i + 1] = targets[i]["boxes"].shape[0]
+        np.cumsum(box_offsets, out=box_offsets)
+        ntable = ctypes.sizeof(table)
+        nmeta = ntable + box_offsets.nbytes
+        with torch.cuda.device(dev):
+            stage = self._staging.setdefault(dev, _Staging())
+            pixels, meta = stage.acquire(plan.nbytes if src_dev.type == "cpu" else 0, nmeta)
+            meta[:ntable].copy_(torch.from_numpy(np.frombuffer(table, dtype=np.uint8)))
+            meta[ntable:nmeta].copy_(torch.from_numpy(box_offsets.view(np.uint8)))
+            if src_dev.type == "cpu":
+                for img, off, (h, w) in zip(images, plan.offsets, shapes):
+                    pixels[off:off + 3 * h * w].view(h, w, 3).copy_(img)
+                packed = torch.empty(plan.nbytes, dtype=torch.uint8, device=dev)
+                packed.copy_(pixels[:plan.nbytes], non_blocking=True)
+            else:
+                packed = torch.cat([img.reshape(-1) for img in images])
+            meta_dev = torch.empty(nmeta, dtype=torch.uint8, device=dev)
+            meta_dev.copy_(meta[:nmeta], non_blocking=True)
+            stage.release()
+            table_dev = ctypes.c_void_p(meta_dev.data_ptr())
+            mean, std = self._mean_std(dev)
+            ph, pw = plan.pad
+            batch = torch.empty((n, 3, ph, pw), dtype=torch.float32, device=dev)
+            L = lib()
+            check(L.mi355det_ingest_u8(ptr(packed), plan.nbytes, ctypes.cast(table, ctypes.c_void_p), table_dev, n, ptr(mean), ptr(std), ptr(batch),
+                                       ph, pw, stream_ptr()), "ingest_u8")
+            if with_boxes:
+                boxes = [targets[i]["boxes"].to(torch.float32) for i in with_boxes]
+                if any(b.device != boxes[0].device for b in boxes):
+                    boxes = [b.to(dev) for b in boxes]
+                boxes = torch.cat(boxes).to(dev).contiguous()
+                out = torch.empty_like(boxes)
+                check(L.mi355det_flip_resize_boxes(ptr(boxes), ptr(out), boxes.shape[0], ctypes.c_void_p(meta_dev.data_ptr() + ntable), table_dev, n,
+                                                   stream_ptr()), "flip_resize_boxes")
+                for i, b in zip(with_boxes, out.split([int(targets[i]["boxes"].shape[0]) for i in with_boxes])):
+                    targets[i]["boxes"] = b
+            if targets is not None:
+                from ..ops import mask_resize_nearest as _resize
+                for i, t in enumerate(targets):
+                    if "masks" in t:
+                        t["masks"] = _resize(t["masks"].to(dev), plan.sizes[i], flip=flips[i])
+        return ImageList(batch, plan.sizes, shapes), targets
 
     def postprocess(self, result, image_shapes, original_image_sizes, mask_format="dense"):
         """transform.py:228-247 (boxes, and masks when the result has them; no keypoint branch on this path).  mask_format "dense" is the
