@@ -924,6 +924,30 @@ int mi355det_coco_accumulate(int32_t num_cats, const int64_t* cat_dt_offsets, co
                              int32_t num_max_dets, const double* rec_thrs, int32_t num_recs, double* precision, double* recall, double* scores,
                              void* stream);
 
+/* ---- Model comparison (csrc/compare_kernels.hip): for two result sets over one ground truth, the best class-agnostic box overlap of every
+ * ground-truth instance and whether that detection carries the right label - the per-image body of the reference's
+ * notebooks/get_disagreement.py (torchvision box_iou, then max over the detections), for all images and both models in one launch.
+ * gt_offsets / dt_offsets_a / dt_offsets_b [num_images + 1] int64 ON THE DEVICE: image i owns the ground-truth slots gt_offsets[i]..
+ * gt_offsets[i + 1] and, per model, the detection slots dt_offsets[i]..dt_offsets[i + 1]; gt_offsets must run from 0 to num_gt (a slot no
+ * image owns is not written).  num_gt / num_dt_a / num_dt_b are the caller's host copies of the last offsets: they size the arrays, an
+ * image whose ground-truth range does not fit is skipped and one whose detection range does not fit (or holds more than 2^31 - 1
+ * detections: best_index is int32) counts as having no detections; nothing is read or written past them.  Boxes are float64 [*, 4] as
+ * [x, y, w, h] with finite entries, labels int64.  Outputs [2, num_gt], model a first: best_iou float64, best_index int32 (the detection's
+ * index within its image), correct uint8.  All floating point is float64 without contraction, the division is IEEE; no atomics, every
+ * output element has one writer, so the output is bit-identical from run to run.  No workspace; MI355DET_EINVAL for num_images < 0 and
+ * for missing offset tables with num_images > 0; no launch when there are no images or no ground truths.
+ *   per box          x2 = x + w, y2 = y + h first; area = (x2 - x) * (y2 - y) (not w * h: they differ in the last bit).
+ *   per pair         iw = max(min(dx2, gx2) - max(dx, gx), 0), ih likewise, inter = iw * ih, iou = inter / (da + ga - inter); a pair with
+ *                    zero union is 0 / 0 = NaN.
+ *   per ground truth the best detection as torch.max(iou, dim=0) picks it: NaN beats every number; among equal values, or among several
+ *                    NaNs, the lowest detection index wins.  correct = best_iou >= iou_threshold && gt_label == dt_label[best_index] (a NaN
+ *                    best is incorrect).  An image without detections of a model gives best_iou 0, best_index -1, correct 0 and reads
+ *                    no box and no label of that model. */
+int mi355det_box_disagreement(int64_t num_images, const int64_t* gt_offsets, int64_t num_gt, const double* gt_box, const int64_t* gt_label,
+                              const int64_t* dt_offsets_a, int64_t num_dt_a, const double* dt_box_a, const int64_t* dt_label_a,
+                              const int64_t* dt_offsets_b, int64_t num_dt_b, const double* dt_box_b, const int64_t* dt_label_b,
+                              double iou_threshold, double* best_iou, int32_t* best_index, uint8_t* correct, void* stream);
+
 /* layout / dtype converters at the module boundary */
 int mi355det_nhwc_to_nchw_f32(const void* x, int x_is_bf16, int32_t x_ld, int32_t n, int32_t c, int32_t h,
                               int32_t w, float* out, void* stream);

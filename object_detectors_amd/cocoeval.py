@@ -7,6 +7,7 @@ What pycocotools' COCOeval computes with a Python loop over images x categories 
     evaluate()      torch sorts group the detections (plumbing) -> coco_iou -> coco_match
     accumulate()    one stable sort per category -> coco_accumulate -> precision / recall / scores on the host
     summarize()     numpy on the small result arrays; prints pycocotools' twelve lines and sets .stats
+    summarize_per_category()    the same twelve numbers for every category on its own, read out of precision / recall (compare.py)
 
 Slot layout after evaluate(): detections and ground truths are each sorted category-major, image second (the order of `cat_ids`, `img_ids`);
 within a group the detections are in descending score order (stable, cut to 100) and the ground truths in annotation order.
@@ -29,6 +30,10 @@ REC_THRS = np.linspace(0, 1, 101)
 MAX_DETS = [1, 10, 100]
 AREA_RNG = [[0, 1e10], [0, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e10]]
 AREA_LABELS = ["all", "small", "medium", "large"]
+# the twelve statistics as (precision or recall, IoU threshold or all, area range, maxDets index), and the names the reference's notebooks use
+STAT_ROWS = [(1, None, 0, 2), (1, .5, 0, 2), (1, .75, 0, 2), (1, None, 1, 2), (1, None, 2, 2), (1, None, 3, 2),
+             (0, None, 0, 0), (0, None, 0, 1), (0, None, 0, 2), (0, None, 1, 2), (0, None, 2, 2), (0, None, 3, 2)]
+STAT_NAMES = ["AP", "AP50", "AP75", "APs", "APm", "APl", "AR1", "AR10", "AR100", "ARs", "ARm", "ARl"]
 
 
 def load_dataset(gt):
@@ -155,6 +160,20 @@ def group_offsets(keys, k):
     return c, torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(c, 0)])
 
 
+def image_indices(image_id, n, img_ids, img_index, dev, what):
+    """The image of n detections - one id for all, or a tensor [n] of ids - as int64 [n] positions in the sorted `img_ids` on the device
+    (`img_index`: id -> position); -1 for an image the ground truth does not know."""
+    if torch.is_tensor(image_id) and image_id.dim() > 0:
+        ids = image_id.to(dev).to(torch.int64).reshape(-1)
+        if ids.shape[0] != n:
+            raise ValueError(f"{what}: one image id per detection, or one for all")
+        table = torch.tensor(img_ids, dtype=torch.int64, device=dev)
+        i = torch.searchsorted(table, ids).clamp_(max=max(len(img_ids) - 1, 0))
+        return torch.where(table[i] == ids, i, torch.full_like(i, -1)) if len(img_ids) else torch.full_like(ids, -1)
+    i = img_index.get(image_id.item() if torch.is_tensor(image_id) else image_id, -1)
+    return torch.full((n,), i, dtype=torch.int64, device=dev)
+
+
 def category_order(cat_dt_offsets, dt_score):
     """Per category its detection slots in descending score order (stable over the image order the slots are in): coco_accumulate's `order`."""
     cat_of = torch.searchsorted(cat_dt_offsets, torch.arange(int(dt_score.shape[0]), device=dt_score.device), right=True) - 1
@@ -221,16 +240,7 @@ class COCOEval:
             if len(batch) != n:
                 raise ValueError("COCOEval.add: one mask per detection")
             self._masks.add_batch(batch)
-        if torch.is_tensor(image_id) and image_id.dim() > 0:
-            ids = image_id.to(dev).to(torch.int64).reshape(-1)
-            if ids.shape[0] != n:
-                raise ValueError("COCOEval.add: one image id per detection, or one for all")
-            table = torch.tensor(self.img_ids, dtype=torch.int64, device=dev)
-            i = torch.searchsorted(table, ids).clamp_(max=max(len(self.img_ids) - 1, 0))
-            self._img.append(torch.where(table[i] == ids, i, torch.full_like(i, -1)) if len(self.img_ids) else torch.full_like(ids, -1))
-        else:
-            i = self._img_index.get(image_id.item() if torch.is_tensor(image_id) else image_id, -1)
-            self._img.append(torch.full((n,), i, dtype=torch.int64, device=dev))
+        self._img.append(image_indices(image_id, n, self.img_ids, self._img_index, dev, "COCOEval.add"))
         self._cat.append(cat)
         self._score.append(score)
         self.num_added += n
@@ -344,10 +354,12 @@ class COCOEval:
         self.precision, self.recall, self.scores = p.cpu().numpy(), r.cpu().numpy(), s.cpu().numpy()
         return self
 
-    def _stat(self, ap, iou_thr=None, area=0, max_det=2):
+    def _stat(self, ap, iou_thr=None, area=0, max_det=2, cat=None):
         s = self.precision if ap else self.recall
         if iou_thr is not None:
             s = s[np.isclose(self.iou_thrs, iou_thr)]
+        if cat is not None:                                        # one category's slice: pycocotools with params.catIds = [that category]
+            s = s[:, :, cat:cat + 1] if ap else s[:, cat:cat + 1]
         s = s[:, :, :, area, max_det] if ap else s[:, :, area, max_det]
         s = s[s > -1]
         return np.float64(-1) if s.size == 0 else np.mean(s)
@@ -356,13 +368,23 @@ class COCOEval:
         """Prints pycocotools' twelve lines and sets .stats (float64 [12])."""
         if self.precision is None:
             raise RuntimeError("COCOEval.summarize: call accumulate() first")
-        rows = [(1, None, 0, 2), (1, .5, 0, 2), (1, .75, 0, 2), (1, None, 1, 2), (1, None, 2, 2), (1, None, 3, 2),
-                (0, None, 0, 0), (0, None, 0, 1), (0, None, 0, 2), (0, None, 1, 2), (0, None, 2, 2), (0, None, 3, 2)]
         stats = np.zeros(12, np.float64)
-        for n, (ap, thr, a, m) in enumerate(rows):
+        for n, (ap, thr, a, m) in enumerate(STAT_ROWS):
             stats[n] = self._stat(ap, thr, a, m)
             title, kind = ("Average Precision", "(AP)") if ap else ("Average Recall", "(AR)")
             span = f"{self.iou_thrs[0]:0.2f}:{self.iou_thrs[-1]:0.2f}" if thr is None else f"{thr:0.2f}"
             print(f" {title:<18} {kind} @[ IoU={span:<9} | area={AREA_LABELS[a]:>6s} | maxDets={self.max_dets[m]:>3d} ] = {stats[n]:0.3f}", file=file)
         self.stats = stats
         return stats
+
+    def summarize_per_category(self):
+        """The twelve statistics of every category on its own, float64 [K, 12]: row k is what summarize() would give with only cat_ids[k]
+        evaluated (pycocotools with params.catIds = [cat_ids[k]], which the reference's notebooks/get_map.py:54-60 runs once per category).
+        Read out of precision / recall by category: no new pass, nothing printed, .stats untouched."""
+        if self.precision is None:
+            raise RuntimeError("COCOEval.summarize_per_category: call accumulate() first")
+        out = np.zeros((len(self.cat_ids), 12), np.float64)
+        for k in range(len(self.cat_ids)):
+            for n, (ap, thr, a, m) in enumerate(STAT_ROWS):
+                out[k, n] = self._stat(ap, thr, a, m, cat=k)
+        return out

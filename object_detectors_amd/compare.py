@@ -1,0 +1,187 @@
+"""Model comparison on the device: which ground-truth instances two result sets get right (the 2 x 2 contingency table and McNemar's test of
+the reference's notebooks/get_disagreement.py) and the twelve COCO statistics per category (its notebooks/get_map.py), without pycocotools,
+torchvision or statsmodels.
+
+    d = Disagreement(gt)                      ground truth per image: EVERY annotation of the image in dataset order (any category, crowd or
+                                              not), as the notebook takes them
+    d.add(model, ...) / d.add_results(model, results)      model 0 is the notebook's baseline, model 1 its second experiment
+    d.run(iou_threshold, confidence)          torch filters and sorts (plumbing) -> mi355det_box_disagreement (csrc/compare_kernels.hip,
+                                              include/mi355det.h "Model comparison") -> four sums, one host read
+    d.report(alpha)                           the table, McNemar's test and the verdict line
+
+An instance is right for a model when the detection with the best class-agnostic box overlap reaches the threshold and carries the instance's
+label.  An image counts only if it has an annotation and both models keep a detection on it (the notebook's `except IndexError` path);
+every other image adds one to `missed`.
+
+Deviations from the notebooks, both deliberate: mcnemar(0, 0) returns (0.0, 1.0) where the bare formula divides by zero, and
+per_category_table returns the chosen metric columns where get_map.py:59-60 reads stats[position in the list]."""
+import math
+import sys
+
+import numpy as np
+import torch
+
+from . import ops
+from .cocoeval import STAT_NAMES, image_indices, load_dataset
+
+
+def mcnemar(yes_no, no_yes):
+    """McNemar's test as both notebooks call it (statsmodels mcnemar(table, exact=False, correction=True)) -> (statistic, pvalue):
+    statistic = (|b - c| - 1)^2 / (b + c), pvalue = the chi-square survival function at one degree of freedom = erfc(sqrt(statistic / 2)).
+    b + c == 0 (no discordant instance: nothing to test) returns (0.0, 1.0); the bare formula divides by zero there."""
+    b, c = int(yes_no), int(no_yes)
+    if b < 0 or c < 0:
+        raise ValueError("mcnemar: counts must not be negative")
+    if b + c == 0:
+        return 0.0, 1.0
+    statistic = (abs(b - c) - 1) ** 2 / (b + c)
+    return statistic, math.erfc(math.sqrt(statistic / 2))
+
+
+class Disagreement:
+    """get_disagreement.py on the device.  `gt`: see cocoeval.load_dataset.  `max_dets`: keep each model's `max_dets` best-scored detections
+    of an image, in descending score order (300 is what LVISResults applies); None keeps all, in input order."""
+
+    def __init__(self, gt, device=None, max_dets=None):
+        self.dataset = load_dataset(gt)
+        self.device = dev = torch.device("cuda:0" if device is None else device)
+        if max_dets is not None and int(max_dets) < 1:
+            raise ValueError("Disagreement: max_dets must be at least 1 (or None)")
+        self.max_dets = None if max_dets is None else int(max_dets)
+        self.img_ids = sorted(set(im["id"] for im in self.dataset["images"]))
+        self._img_index = {v: i for i, v in enumerate(self.img_ids)}
+        anns = [(j, a) for j, a in enumerate(self.dataset.get("annotations", [])) if a["image_id"] in self._img_index]
+        img = np.asarray([self._img_index[a["image_id"]] for _j, a in anns], np.int64)
+        order = np.argsort(img, kind="mergesort")                                # image-major, dataset order within an image
+        self.gt_index = np.asarray([anns[o][0] for o in order], np.int64)       # slot -> position in dataset["annotations"]
+        count = np.bincount(img, minlength=len(self.img_ids)).astype(np.int64)
+        self.gt_count = torch.from_numpy(count).to(dev)
+        self.gt_offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(count)]).astype(np.int64)).to(dev)
+        self.gt_box = torch.from_numpy(np.asarray([anns[o][1]["bbox"] for o in order], np.float64).reshape(-1, 4)).to(dev)
+        self.gt_label = torch.from_numpy(np.asarray([anns[o][1]["category_id"] for o in order], np.int64)).to(dev)
+        self.num_gt = int(self.gt_index.shape[0])
+        self.reset()
+
+    def reset(self):
+        """Forget the detections of both models (the ground truth stays)."""
+        self._det = [{"img": [], "cat": [], "score": [], "box": []} for _ in range(2)]
+        self.num_added = [0, 0]
+        self.result = None
+        self.best_iou = self.best_index = self.correct = self.dt_offsets = None
+
+    # ---- detections
+    def _side(self, model):
+        if isinstance(model, bool) or model not in (0, 1):
+            raise ValueError(f"Disagreement: model must be 0 or 1, not {model!r}")
+        return self._det[model]
+
+    def add(self, model, image_id, category_ids, scores, boxes):
+        """The detections of `model` (0 or 1) on one image (or, with image_id a tensor [n], on many): category_ids [n], scores [n], boxes [n, 4]
+        as [x, y, w, h].  Tensors stay on the device; float32 is widened exactly."""
+        side, dev = self._side(model), self.device
+        cat = torch.as_tensor(category_ids, device=dev).to(torch.int64).reshape(-1)
+        n = int(cat.shape[0])
+        score = torch.as_tensor(scores, device=dev).to(torch.float64).reshape(-1)
+        box = torch.as_tensor(boxes, device=dev).to(torch.float64).reshape(-1, 4)
+        if score.shape[0] != n or box.shape[0] != n:
+            raise ValueError("Disagreement.add: one score and one box per detection")
+        side["img"].append(image_indices(image_id, n, self.img_ids, self._img_index, dev, "Disagreement.add"))
+        side["cat"].append(cat)
+        side["score"].append(score)
+        side["box"].append(box)
+        self.num_added[model] += n
+
+    def add_results(self, model, results):
+        """COCO result dicts (`image_id`, `category_id`, `score`, `bbox`) of `model` (0 or 1), e.g. a loaded results json."""
+        side, dev = self._side(model), self.device
+        if not results:
+            return
+        side["img"].append(torch.tensor([self._img_index.get(r["image_id"], -1) for r in results], dtype=torch.int64, device=dev))
+        side["cat"].append(torch.tensor([r["category_id"] for r in results], dtype=torch.int64, device=dev))
+        side["score"].append(torch.tensor([r["score"] for r in results], dtype=torch.float64, device=dev))
+        side["box"].append(torch.tensor([r["bbox"] for r in results], dtype=torch.float64, device=dev).reshape(-1, 4))
+        self.num_added[model] += len(results)
+
+    def _kept(self, side, confidence):
+        """One model's detections as the kernel takes them: (offsets [I + 1], boxes, labels, per-image counts), image-major; within an image
+        in input order, or with max_dets in descending score order (stable) cut to max_dets."""
+        dev, I = self.device, len(self.img_ids)
+        cat_of = lambda xs, dt, shape: torch.cat(xs) if xs else torch.zeros(shape, dtype=dt, device=dev)
+        img, cat = cat_of(side["img"], torch.int64, (0,)), cat_of(side["cat"], torch.int64, (0,))
+        score, box = cat_of(side["score"], torch.float64, (0,)), cat_of(side["box"], torch.float64, (0, 4))
+        src = torch.nonzero((img >= 0) & (score > confidence)).reshape(-1)      # strict; a detection on an unknown image is dropped
+        key = img[src]
+        if self.max_dets is None:
+            perm = torch.sort(key, stable=True).indices
+            key = key[perm]
+        else:
+            o1 = torch.sort(-score[src], stable=True).indices
+            o2 = torch.sort(key[o1], stable=True).indices
+            perm = o1[o2]
+            key = key[perm]
+            _u, per = torch.unique_consecutive(key, return_counts=True)
+            rank = torch.arange(int(key.shape[0]), device=dev) - torch.repeat_interleave(torch.cumsum(per, 0) - per, per)
+            top = rank < self.max_dets
+            perm, key = perm[top], key[top]
+        index = src[perm]
+        count = torch.bincount(key, minlength=I) if I else torch.zeros(0, dtype=torch.int64, device=dev)
+        offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(count, 0)])
+        return offsets.contiguous(), box[index].contiguous(), cat[index].contiguous(), count, index
+
+    def _tally(self, count_a, count_b):
+        """[yes_yes, yes_no, no_yes, total, missed] on the device from `correct` and the two models' per-image detection counts."""
+        counted = (self.gt_count > 0) & (count_a > 0) & (count_b > 0)                        # per image
+        on = torch.repeat_interleave(counted, self.gt_count, output_size=self.num_gt)        # per ground truth
+        c0, c1 = self.correct[0].bool() & on, self.correct[1].bool() & on
+        return torch.stack([(c0 & c1).sum(), (c0 & ~c1).sum(), (~c0 & c1).sum(), on.sum(), len(self.img_ids) - counted.sum()])
+
+    def run(self, iou_threshold=0.5, confidence=0.0):
+        """-> {"yes_yes", "yes_no", "no_yes", "no_no", "total", "missed"} (ints) and "correct" (uint8 [2, G] on the device, slot order: gt_index).
+        yes_no: right for model 0 only; no_yes: right for model 1 only.  May be called again with other thresholds without re-adding.
+        Leaves best_iou / best_index / correct [2, G], dt_offsets and dt_index (per model: slot -> position in the order added) behind; the
+        rows of `correct` of an image that is not counted are still each model's own answer."""
+        a, b = self._kept(self._det[0], confidence), self._kept(self._det[1], confidence)
+        self.dt_offsets, self.dt_index = (a[0], b[0]), (a[4], b[4])
+        self.best_iou, self.best_index, self.correct = ops.box_disagreement(self.gt_offsets, self.gt_box, self.gt_label, a[:3], b[:3],
+                                                                            iou_threshold)
+        yes_yes, yes_no, no_yes, total, missed = (int(v) for v in self._tally(a[3], b[3]).cpu().tolist())        # the one host read
+        self.result = {"yes_yes": yes_yes, "yes_no": yes_no, "no_yes": no_yes, "no_no": total - yes_yes - yes_no - no_yes, "total": total,
+                       "missed": missed, "correct": self.correct, "iou_threshold": float(iou_threshold), "confidence": float(confidence)}
+        return self.result
+
+    def report(self, alpha=0.05, file=None):
+        """Prints the contingency table of the last run(), McNemar's test and the verdict line, as the notebook does; -> (statistic, pvalue)."""
+        if self.result is None:
+            raise RuntimeError("Disagreement.report: call run() first")
+        r, out = self.result, (sys.stdout if file is None else file)
+        rows = [[f"IoU@{r['iou_threshold']}", "Correct2", "Incorrect2"], ["Correct1", str(r["yes_yes"]), str(r["yes_no"])],
+                ["Incorrect1", str(r["no_yes"]), str(r["no_no"])]]
+        width = [max(len(row[c]) for row in rows) + 2 for c in range(3)]
+        rule = "+" + "+".join("-" * w for w in width) + "+"
+        print(rule, file=out)
+        for n, row in enumerate(rows):
+            print("|" + "|".join(cell.center(w) for cell, w in zip(row, width)) + "|", file=out)
+            if n == 0 or n == len(rows) - 1:
+                print(rule, file=out)
+        statistic, pvalue = mcnemar(r["yes_no"], r["no_yes"])
+        print("McNemar's test:", file=out)
+        print("statistic=%.4f, p-value=%.4f" % (statistic, pvalue), file=out)
+        print("Same proportions of errors (fail to reject H0)" if pvalue > alpha else "Different proportions of errors (reject H0)", file=out)
+        return statistic, pvalue
+
+
+def per_category_table(evaluators, metric_columns=(0,)):
+    """get_map.py's `results` dict for accumulated COCOEval objects {experiment name: COCOEval}: "columns" = the names of the chosen
+    statistics (indices into AP, AP50, AP75, APs, APm, APl, AR1, AR10, AR100, ARs, ARm, ARl) and, per experiment, {name of the statistic:
+    its value for every category, in the order of cat_ids}.  The chosen columns are returned; get_map.py:59-60 reads stats[position in the
+    list] instead, which is statistic 0 whatever was asked for."""
+    cols = [int(c) for c in metric_columns]
+    if any(c < 0 or c >= len(STAT_NAMES) for c in cols):
+        raise ValueError(f"per_category_table: metric_columns must index the {len(STAT_NAMES)} COCO statistics")
+    table = {"columns": [STAT_NAMES[c] for c in cols]}
+    for name, ev in evaluators.items():
+        if name == "columns":
+            raise ValueError("per_category_table: an experiment cannot be named 'columns'")
+        stats = ev.summarize_per_category()
+        table[name] = {STAT_NAMES[c]: [float(v) for v in stats[:, c]] for c in cols}
+    return table

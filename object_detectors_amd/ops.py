@@ -1182,3 +1182,33 @@ def coco_mask_iou(dt, gt, iscrowd):
     rle = {"dt": side(dt), "gt": side(gt), "dt_sizes": [dt.size if D else (0, 0)], "gt_sizes": [gt.size if G else (0, 0)]}
     boxes = lambda b: b.stats()[1].to(dev).to(torch.float64).contiguous()
     return coco_iou(*_one_group(D, G, dev), D * G, boxes(dt), boxes(gt), crowd, rle).reshape(D, G)
+
+
+# ---- model comparison (csrc/compare_kernels.hip; the front end on top of it is object_detectors_amd/compare.py)
+def box_disagreement(gt_offsets, gt_box, gt_label, dt_a, dt_b, iou_threshold):
+    """mi355det_box_disagreement: gt_offsets int64 [I + 1] (from 0 to G), gt_box float64 [G, 4] as [x, y, w, h], gt_label int64 [G]; dt_a / dt_b
+    = (dt_offsets int64 [I + 1], dt_box float64 [D, 4], dt_label int64 [D]) of the two models, everything on the device ->
+    best_iou float64 [2, G], best_index int32 [2, G] (within the image's detections; -1: the image has none), correct uint8 [2, G]."""
+    tensors = (gt_offsets, gt_box, gt_label) + tuple(dt_a) + tuple(dt_b)
+    if not all(torch.is_tensor(t) and t.is_cuda for t in tensors):
+        raise ValueError("box_disagreement needs CUDA/HIP tensors (no CPU fallback)")
+    dev = gt_box.device
+    i64c = lambda t: t.to(torch.int64).contiguous()
+    I = int(gt_offsets.shape[0]) - 1
+    gt_offsets, gt_box, gt_label = i64c(gt_offsets), _f64c(gt_box, dev).reshape(-1, 4), i64c(gt_label)
+    G = int(gt_box.shape[0])
+    if I < 0 or int(gt_label.shape[0]) != G:
+        raise ValueError("box_disagreement: gt_offsets must hold I + 1 entries and every ground truth one label")
+    sides = []
+    for off, box, label in (dt_a, dt_b):
+        off, box, label = i64c(off), _f64c(box, dev).reshape(-1, 4), i64c(label)
+        if int(off.shape[0]) != I + 1 or int(label.shape[0]) != int(box.shape[0]):
+            raise ValueError("box_disagreement: each model needs I + 1 offsets and one label per box")
+        sides.append((off, box, label))
+    best_iou = torch.empty((2, G), dtype=torch.float64, device=dev)
+    best_index = torch.empty((2, G), dtype=torch.int32, device=dev)
+    correct = torch.empty((2, G), dtype=torch.uint8, device=dev)
+    args = [a for off, box, label in sides for a in (ptr(off), int(box.shape[0]), ptr(box), ptr(label))]
+    check(lib().mi355det_box_disagreement(I, ptr(gt_offsets), G, ptr(gt_box), ptr(gt_label), *args, float(iou_threshold), ptr(best_iou),
+                                          ptr(best_index), ptr(correct), stream_ptr()), "box_disagreement")
+    return best_iou, best_index, correct
