@@ -924,6 +924,31 @@ int mi355det_coco_accumulate(int32_t num_cats, const int64_t* cat_dt_offsets, co
                              int32_t num_max_dets, const double* rec_thrs, int32_t num_recs, double* precision, double* recall, double* scores,
                              void* stream);
 
+/* ---- Bootstrap replicates (csrc/bootstrap_kernels.hip): coco_accumulate for num_replicates resampled data sets at once, reduced in place to
+ * one precision sum and one recall per cell.  The arguments of coco_accumulate without the scores (same layouts, same meaning; the match
+ * arrays are those of coco_match / lvis_match and are not touched), plus dt_image [num_dt] / gt_image [num_gt] int32 = each slot's image
+ * index and weights [num_images, num_replicates] int32 ON THE DEVICE, replicate-minor.
+ *   replicate b      the data set in which image i occurs weights[i][b] times, copies adjacent in image order.  Matching is per (image,
+ *                    category) group and does not change; only the accumulate pass does.
+ *   per (b, k, a, m, t)   npig = sum of weights[gt_image][b] over the category's non-ignored ground truths.  The kept detections (rank <
+ *                    max_dets[m]) of weight > 0 in `order`; tp and fp advance by the weight per slot; at the end of each slot rc = tp/npig
+ *                    and pr = tp/(fp + tp + 2^-52), the expressions of coco_accumulate; pr made non-increasing from the right; recall
+ *                    threshold r takes pr at the first slot with rc >= rec_thrs[r], 0 past the end.  The first kept slot owns threshold 0
+ *                    whatever its flags.  (This is the replicated data set exactly unless two kept detections of ONE group have equal
+ *                    scores and different flags: the replicated set interleaves their copies, this rule keeps each slot's copies adjacent.)
+ *   outputs          ap_sum, recall float64 [num_replicates, num_thrs, K, A, M].  ap_sum = the sum of the cell's num_recs precision values,
+ *                    added one by one in float64 in order of DESCENDING recall threshold (never count * value; an unreached threshold adds
+ *                    0.0); recall = total tp / npig, 0 without kept detections; both -1.0 where npig == 0.
+ * A slot whose image index lies outside [0, num_images) has weight 0 and no weight is read for it; a negative weight counts as 0.
+ * float64 without contraction, no atomics, one writer per element, 64-bit offsets: bit-identical from run to run and whatever the number of
+ * replicates per call.  No workspace.  MI355DET_EINVAL: a missing operand; num_cats, num_thrs, num_areas, num_max_dets, num_recs, num_images
+ * or num_replicates <= 0; num_dt or num_gt < 0; num_recs > 4096; num_max_dets > 8. */
+int mi355det_coco_bootstrap(int32_t num_cats, const int64_t* cat_dt_offsets, const int64_t* cat_gt_offsets, int64_t num_dt, int64_t num_gt,
+                            const int64_t* order, const int32_t* dt_rank, const int32_t* dt_match, const uint8_t* dt_ignore,
+                            const uint8_t* gt_ignore, int32_t num_thrs, int32_t num_areas, const int32_t* max_dets, int32_t num_max_dets,
+                            const double* rec_thrs, int32_t num_recs, const int32_t* dt_image, const int32_t* gt_image, const int32_t* weights,
+                            int32_t num_images, int32_t num_replicates, double* ap_sum, double* recall, void* stream);
+
 /* ---- Model comparison (csrc/compare_kernels.hip): for two result sets over one ground truth, the best class-agnostic box overlap of every
  * ground-truth instance and whether that detection carries the right label - the per-image body of the reference's
  * notebooks/get_disagreement.py (torchvision box_iou, then max over the detections), for all images and both models in one launch.

@@ -8,6 +8,8 @@ What pycocotools' COCOeval computes with a Python loop over images x categories 
     accumulate()    one stable sort per category -> coco_accumulate -> precision / recall / scores on the host
     summarize()     numpy on the small result arrays; prints pycocotools' twelve lines and sets .stats
     summarize_per_category()    the same twelve numbers for every category on its own, read out of precision / recall (compare.py)
+    bootstrap(weights)          after evaluate(): the twelve numbers of resampled data sets, all replicates in one accumulate walk with integer
+                                weights (csrc/bootstrap_kernels.hip); intervals and the paired test are compare.py
 
 Slot layout after evaluate(): detections and ground truths are each sorted category-major, image second (the order of `cat_ids`, `img_ids`);
 within a group the detections are in descending score order (stable, cut to 100) and the ground truths in annotation order.
@@ -182,6 +184,83 @@ def category_order(cat_dt_offsets, dt_score):
     return o1[o2].contiguous()
 
 
+# ---- bootstrap replicates (csrc/bootstrap_kernels.hip), shared with lviseval.py
+def check_weights(weights, num_images, what):
+    """Bootstrap weights, an integer numpy array or tensor [B, num_images] without negative entries -> an int32 tensor (on the device it
+    came from); anything else is a ValueError."""
+    if not torch.is_tensor(weights):
+        arr = np.asarray(weights)
+        if arr.dtype.kind not in "iu":
+            raise ValueError(f"{what}: the weights must be integers, not {arr.dtype}")
+        weights = torch.from_numpy(np.ascontiguousarray(arr.astype(np.int64) if arr.dtype.kind == "u" else arr))
+    if weights.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+        raise ValueError(f"{what}: the weights must be integers, not {weights.dtype}")
+    if weights.dim() != 2 or int(weights.shape[1]) != num_images:
+        raise ValueError(f"{what}: the weights must be [replicates, {num_images}] (one column per entry of img_ids), not {list(weights.shape)}")
+    if weights.numel() and (int(weights.min()) < 0 or int(weights.max()) > 2 ** 31 - 1):
+        raise ValueError(f"{what}: the weights must lie in 0 .. 2^31 - 1")
+    return weights.to(torch.int32)
+
+
+def bootstrap_cells(ev, weights, max_dets, cell_budget_bytes):
+    """The replicate cells of an evaluated COCOEval / LVISEval, a chunk of replicates at a time: yields (ap_sum, recall), float64
+    [chunk, T, K, A, M] on the device (mi355det_coco_bootstrap).  `weights`: int32 [B, images]; a chunk's two buffers stay within
+    `cell_budget_bytes` (one replicate at least).  A replicate's cells do not depend on the chunk it falls into."""
+    dev, I, K = ev.device, len(ev.img_ids), len(ev.cat_ids)
+    T, A, M = len(ev.iou_thrs), int(ev.area_rng.shape[0]), len(max_dets)
+    B = int(weights.shape[0])
+    chunk = max(1, int(cell_budget_bytes) // max(2 * 8 * T * K * A * M, 1))
+    if K == 0 or I == 0:                                          # nothing to evaluate: every cell is -1, no launch
+        for b0 in range(0, B, chunk):
+            none = torch.full((min(chunk, B - b0), T, K, A, M), -1.0, dtype=torch.float64, device=dev)
+            yield none, none.clone()
+        return
+    order = category_order(ev.cat_dt_offsets, ev.dt_score)
+    rec = torch.from_numpy(np.ascontiguousarray(ev.rec_thrs, np.float64)).to(dev)
+    for b0 in range(0, B, chunk):
+        w = weights[b0:b0 + chunk].to(dev).t().contiguous()                              # [images, chunk]: replicate-minor
+        yield ops.coco_bootstrap(ev.cat_dt_offsets, ev.cat_gt_offsets, order, ev.dt_rank, ev.dt_match, ev.dt_ignore, ev.gt_ignore, max_dets, rec,
+                                 ev.dt_image, ev.gt_image, w)
+
+
+def _row_sums(v):
+    """[B, n] -> [B], each row summed by halving (zero-padded to a power of two): elementwise additions only, so a row's sum has one fixed
+    order whatever the number of rows it is computed with - a replicate's statistics do not depend on the chunk it falls into."""
+    size = 1 << max(int(v.shape[1]) - 1, 0).bit_length()
+    v = torch.nn.functional.pad(v, (0, size - int(v.shape[1])))
+    while size > 1:
+        size >>= 1
+        v = v[:, :size] + v[:, size:]
+    return v[:, 0]
+
+
+def cell_mean(cells, per_cell):
+    """pycocotools' mean(s[s > -1]) of each replicate, regrouped: cells [B, ...] (-1: not valid) -> sum of the valid cells / (per_cell *
+    their number), -1 where none is valid; float64 [B] on the device.  `per_cell`: 101 for ap_sum (a cell is a sum of 101 values), 1 for
+    recall."""
+    v = cells.reshape(cells.shape[0], -1)
+    valid = v > -1
+    n = valid.sum(1)
+    total = _row_sums(torch.where(valid, v, torch.zeros_like(v)))
+    return torch.where(n > 0, total / (per_cell * n.clamp(min=1)).to(torch.float64), torch.full_like(total, -1.0))
+
+
+def run_bootstrap(ev, weights, max_dets, stat_rows, num_stats, cell_budget_bytes, return_cells, what):
+    """bootstrap() of both evaluators: `stat_rows(ap_sum, recall)` -> the `num_stats` statistics of a chunk as a list of [chunk] tensors."""
+    w = check_weights(weights, len(ev.img_ids), what)
+    if ev.iou is None:
+        raise RuntimeError(f"{what}: call evaluate() first")
+    none = torch.zeros((0, len(ev.iou_thrs), len(ev.cat_ids), int(ev.area_rng.shape[0]), len(max_dets)), dtype=torch.float64, device=ev.device)
+    stats, aps, rcs = [torch.zeros((0, num_stats), dtype=torch.float64, device=ev.device)], [none], [none]          # no replicate: empty results
+    for ap_sum, recall in bootstrap_cells(ev, w, max_dets, cell_budget_bytes):
+        stats.append(torch.stack(stat_rows(ap_sum, recall), 1))
+        if return_cells:
+            aps.append(ap_sum)
+            rcs.append(recall)
+    out = torch.cat(stats).cpu().numpy()
+    return (out, (torch.cat(aps), torch.cat(rcs))) if return_cells else out
+
+
 class COCOEval:
     """COCOeval for `bbox` or `segm` on the device.  `gt`: see load_dataset.  Detections come in through add() (one image, device tensors) or
     add_results() (COCO result dicts); evaluate(), accumulate() and summarize() then follow pycocotools' protocol."""
@@ -308,6 +387,7 @@ class COCOEval:
         self.dt_index = src[perm][top]
         key, self.dt_rank = key[top], rank[top].to(torch.int32)
         self.dt_score = score[self.dt_index].contiguous()
+        self.dt_image, self.gt_image = (key % max(I, 1)).to(torch.int32), (gt["key_dev"] % max(I, 1)).to(torch.int32)       # bootstrap() weighs by them
         num_dt = int(key.shape[0])
         # the groups: every (category, image) with a detection or a ground truth
         keys = torch.unique(torch.cat([key, gt["key_dev"]]))
@@ -353,6 +433,26 @@ class COCOEval:
                                       self.dt_ignore, self.gt_ignore, self.max_dets, rec)
         self.precision, self.recall, self.scores = p.cpu().numpy(), r.cpu().numpy(), s.cpu().numpy()
         return self
+
+    def bootstrap(self, weights, return_cells=False, cell_budget_bytes=1 << 30):
+        """The twelve statistics of resampled data sets, float64 numpy [B, 12] in STAT_ROWS order.  `weights`: integers [B, len(img_ids)]
+        (numpy or tensor, e.g. compare.bootstrap_weights); replicate b is the evaluation of the data set in which image i occurs
+        weights[b, i] times (include/mi355det.h, "Bootstrap replicates").  Needs evaluate() only; the match arrays are read, and .precision,
+        .recall and .stats stay as they are.  The replicates go through mi355det_coco_bootstrap in chunks whose two cell buffers stay within
+        `cell_budget_bytes`; a replicate's cells and statistics are the same bits whatever the chunking.
+        return_cells=True: -> (stats, (ap_sum, recall)), the cells float64 [B, 10, K, 4, 3] on the device: ap_sum = the sum of a cell's 101
+        precision values, so the AP of category k alone is a mean over ap_sum[:, :, k] / 101; -1 marks a cell without ground truth."""
+        R = len(self.rec_thrs)
+
+        def rows(ap_sum, recall):
+            out = []
+            for ap, thr, a, m in STAT_ROWS:
+                cells = ap_sum if ap else recall
+                if thr is not None:
+                    cells = cells[:, [int(j) for j in np.flatnonzero(np.isclose(self.iou_thrs, thr))]]
+                out.append(cell_mean(cells[:, :, :, a, m], R if ap else 1))
+            return out
+        return run_bootstrap(self, weights, self.max_dets, rows, len(STAT_ROWS), cell_budget_bytes, return_cells, "COCOEval.bootstrap")
 
     def _stat(self, ap, iou_thr=None, area=0, max_det=2, cat=None):
         s = self.precision if ap else self.recall

@@ -13,6 +13,9 @@ An instance is right for a model when the detection with the best class-agnostic
 label.  An image counts only if it has an annotation and both models keep a detection on it (the notebook's `except IndexError` path);
 every other image adds one to `missed`.
 
+Beyond the notebooks: bootstrap_weights / interval / paired_bootstrap turn the replicates of COCOEval.bootstrap and LVISEval.bootstrap
+(resampled images, all replicates in one kernel) into percentile intervals and a paired test on AP itself.
+
 Deviations from the notebooks, both deliberate: mcnemar(0, 0) returns (0.0, 1.0) where the bare formula divides by zero, and
 per_category_table returns the chosen metric columns where get_map.py:59-60 reads stats[position in the list]."""
 import math
@@ -168,6 +171,55 @@ class Disagreement:
         print("statistic=%.4f, p-value=%.4f" % (statistic, pvalue), file=out)
         print("Same proportions of errors (fail to reject H0)" if pvalue > alpha else "Different proportions of errors (reject H0)", file=out)
         return statistic, pvalue
+
+
+# ---- bootstrap over images: is a difference in AP more than noise?  (host code; the replicates are COCOEval.bootstrap / LVISEval.bootstrap)
+def bootstrap_weights(num_images, replicates, seed):
+    """`replicates` resamples of `num_images` images with replacement as counts: int32 [replicates, num_images], every row sums to
+    num_images.  The same seed gives the same array; two evaluators compared with paired_bootstrap must be given the same one."""
+    n, b = int(num_images), int(replicates)
+    if n < 1 or b < 0:
+        raise ValueError("bootstrap_weights: at least one image, and no negative number of replicates")
+    return np.random.default_rng(seed).multinomial(n, [1 / n] * n, size=b).astype(np.int32)
+
+
+def interval(values, level=0.95):
+    """The percentile interval of one statistic over its replicates (a replicate of value -1 has no valid cell and is dropped) ->
+    {"mean", "lo", "hi", "n_used"}: np.quantile at (1 - level) / 2 and 1 - (1 - level) / 2; NaN when no replicate is left."""
+    if not 0 < level < 1:
+        raise ValueError("interval: level must lie in (0, 1)")
+    v = np.asarray(values, np.float64).reshape(-1)
+    v = v[v != -1]
+    if v.size == 0:
+        return {"mean": float("nan"), "lo": float("nan"), "hi": float("nan"), "n_used": 0}
+    lo, hi = np.quantile(v, [(1 - level) / 2, 1 - (1 - level) / 2])
+    return {"mean": float(v.mean()), "lo": float(lo), "hi": float(hi), "n_used": int(v.size)}
+
+
+def paired_bootstrap(a, b, level=0.95):
+    """Two bootstrap() results [B, n] of two evaluators run with the SAME weights -> per column {"delta_mean", "lo", "hi", "n_used", "p"} as
+    arrays [n] (a [B] input is one column).  Pairs where either value is -1 are dropped; d = b - a; lo / hi as in interval();
+    p = min(1, 2 * min((#(d <= 0) + 1) / (n + 1), (#(d >= 0) + 1) / (n + 1))), the two-sided percentile test with the add-one correction.
+    No pair left: NaN for the mean and the bounds, p = 1."""
+    if not 0 < level < 1:
+        raise ValueError("paired_bootstrap: level must lie in (0, 1)")
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    if a.shape != b.shape or a.ndim not in (1, 2):
+        raise ValueError("paired_bootstrap: two arrays of the same shape [replicates] or [replicates, statistics]")
+    a, b = a.reshape(a.shape[0], -1), b.reshape(b.shape[0], -1)
+    cols = a.shape[1]
+    out = {"delta_mean": np.full(cols, np.nan), "lo": np.full(cols, np.nan), "hi": np.full(cols, np.nan), "n_used": np.zeros(cols, np.int64),
+           "p": np.ones(cols, np.float64)}
+    for c in range(cols):
+        keep = (a[:, c] != -1) & (b[:, c] != -1)
+        d = b[keep, c] - a[keep, c]
+        n = int(d.size)
+        if n == 0:
+            continue
+        out["delta_mean"][c], out["n_used"][c] = d.mean(), n
+        out["lo"][c], out["hi"][c] = np.quantile(d, [(1 - level) / 2, 1 - (1 - level) / 2])
+        out["p"][c] = min(1.0, 2 * min((int((d <= 0).sum()) + 1) / (n + 1), (int((d >= 0).sum()) + 1) / (n + 1)))
+    return out
 
 
 def per_category_table(evaluators, metric_columns=(0,)):

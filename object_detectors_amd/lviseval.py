@@ -10,6 +10,7 @@ rule (csrc/cocoeval_kernels.hip, `mi355det_lvis_match`: the COCO walk with a com
                     iscrowd, and an unmatched detection is ignored where its category is in the image's not_exhaustive_category_ids.
     accumulate()    coco_accumulate with one maxDets that cuts nothing -> precision [10, 101, K, 4], recall [10, K, 4] on the host
     summarize()     numpy: AP, AP50, AP75, APs, APm, APl, APr, APc, APf (categories by `frequency`), AR@300, ARs@300, ARm@300, ARl@300
+    bootstrap(w)    after evaluate(): the thirteen numbers of resampled data sets (cocoeval.py, csrc/bootstrap_kernels.hip)
 
 Slot layout after evaluate(): as in cocoeval.py (category-major, image second; `group_keys`, the three offset arrays, `dt_index`, `gt_index`,
 `iou`, `dt_match`, `dt_ignore`, `gt_match`, `gt_ignore`), with no per-group cut, plus `group_not_exhaustive` [groups] uint8.
@@ -23,7 +24,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .cocoeval import AREA_RNG, IOU_THRS, REC_THRS, category_order, group_offsets, load_dataset, sort_ground_truth
+from .cocoeval import AREA_RNG, IOU_THRS, REC_THRS, category_order, cell_mean, group_offsets, load_dataset, run_bootstrap, sort_ground_truth
 
 MAX_DETS = 300
 RESULT_KEYS = ("AP", "AP50", "AP75", "APs", "APm", "APl", "APr", "APc", "APf", "AR@300", "ARs@300", "ARm@300", "ARl@300")
@@ -168,6 +169,7 @@ class LVISEval:
         o3 = torch.sort(key, stable=True).indices
         self.dt_index, key = sel[o3], key[o3].contiguous()
         self.dt_score = score[self.dt_index].contiguous()
+        self.dt_image, self.gt_image = (key % max(I, 1)).to(torch.int32), (gt["key_dev"] % max(I, 1)).to(torch.int32)       # bootstrap() weighs by them
         num_dt = int(key.shape[0])
         self.dt_rank = torch.zeros(num_dt, dtype=torch.int32, device=dev)                   # no per-group cut: nothing ranks past NO_CUT
         keys = torch.unique(torch.cat([key, gt["key_dev"]]))
@@ -212,6 +214,20 @@ class LVISEval:
                                             self.dt_ignore, self.gt_ignore, [NO_CUT], rec)
         self.precision, self.recall = p[..., 0].cpu().numpy(), r[..., 0].cpu().numpy()
         return self
+
+    def bootstrap(self, weights, return_cells=False, cell_budget_bytes=1 << 30):
+        """The thirteen statistics of resampled data sets, float64 numpy [B, 13] in RESULT_KEYS order (APr / APc / APf over freq_groups):
+        COCOEval.bootstrap under the LVIS rules, with the single maxDets that cuts nothing.  Needs evaluate() only and leaves .precision,
+        .recall and .results as they are.  return_cells=True: -> (stats, (ap_sum, recall)), float64 [B, 10, K, 4, 1] on the device."""
+        R = len(self.rec_thrs)
+
+        def rows(ap_sum, recall):
+            ap = lambda cells: cell_mean(cells, R)
+            pick = lambda dim, idx: ap_sum.index_select(dim, torch.tensor([int(j) for j in idx], dtype=torch.int64, device=ap_sum.device))
+            at = lambda thr: pick(1, np.flatnonzero(np.isclose(self.iou_thrs, thr)))
+            return ([ap(ap_sum[:, :, :, 0]), ap(at(.5)[:, :, :, 0]), ap(at(.75)[:, :, :, 0])] + [ap(ap_sum[:, :, :, a]) for a in (1, 2, 3)] +
+                    [ap(pick(2, c)[:, :, :, 0]) for c in self.freq_groups] + [cell_mean(recall[:, :, :, a], 1) for a in (0, 1, 2, 3)])
+        return run_bootstrap(self, weights, [NO_CUT], rows, len(RESULT_KEYS), cell_budget_bytes, return_cells, "LVISEval.bootstrap")
 
     def _stat(self, ap, iou_thr=None, area=0, cats=None):
         s = self.precision if ap else self.recall

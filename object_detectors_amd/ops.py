@@ -1150,6 +1150,31 @@ def coco_accumulate(cat_dt_offsets, cat_gt_offsets, order, dt_rank, dt_score, dt
     return precision, recall, scores
 
 
+def coco_bootstrap(cat_dt_offsets, cat_gt_offsets, order, dt_rank, dt_match, dt_ignore, gt_ignore, max_dets, rec_thrs, dt_image, gt_image,
+                   weights):
+    """mi355det_coco_bootstrap: coco_accumulate's operands without the scores, dt_image [ND] / gt_image [NG] int32 (each slot's image index)
+    and weights int32 [num_images, B] (replicate-minor) -> ap_sum, recall float64 [B, T, K, A, M]."""
+    if not (torch.is_tensor(weights) and weights.is_cuda and rec_thrs.is_cuda):
+        raise ValueError("coco_bootstrap needs CUDA/HIP tensors (no CPU fallback)")
+    dev = weights.device
+    if weights.dtype != torch.int32 or weights.dim() != 2 or dt_image.dtype != torch.int32 or gt_image.dtype != torch.int32:
+        raise ValueError("coco_bootstrap: weights [num_images, B], dt_image and gt_image must be int32")
+    K = int(cat_dt_offsets.shape[0]) - 1
+    A, T, nd = (int(v) for v in dt_match.shape)
+    ngt, R, M = int(gt_ignore.shape[1]), int(rec_thrs.shape[0]), len(max_dets)
+    I, B = (int(v) for v in weights.shape)
+    if int(dt_image.shape[0]) != nd or int(gt_image.shape[0]) != ngt:
+        raise ValueError("coco_bootstrap: one image index per detection slot and per ground truth")
+    ap_sum = torch.full((B, T, K, A, M), -1.0, dtype=torch.float64, device=dev)
+    recall = torch.full((B, T, K, A, M), -1.0, dtype=torch.float64, device=dev)
+    md = (C.c_int32 * M)(*[int(m) for m in max_dets])
+    w = weights.contiguous()
+    check(lib().mi355det_coco_bootstrap(K, ptr(cat_dt_offsets), ptr(cat_gt_offsets), nd, ngt, ptr(order), ptr(dt_rank), ptr(dt_match),
+                                        ptr(dt_ignore), ptr(gt_ignore), T, A, md, M, ptr(rec_thrs), R, ptr(dt_image), ptr(gt_image), ptr(w),
+                                        I, B, ptr(ap_sum), ptr(recall), stream_ptr()), "coco_bootstrap")
+    return ap_sum, recall
+
+
 def _one_group(d, g, dev):
     off = lambda n: torch.tensor([0, n], dtype=torch.int64, device=dev)
     return off(d), off(g), off(d * g)

@@ -3,7 +3,9 @@
 2 x 2 table of ground-truth instances each gets right with McNemar's test (its notebooks/get_disagreement.py).
     python tools/compare_models.py --gt instances_val2017.json --results baseline.json other.json \\
         --iou_threshold 0.5 --confidence 0.0 --alpha 0.05 --metric_columns 0 1 --table per_category.json
-The first result file is the baseline (model 0, "Correct1" in the table).  No plots."""
+The first result file is the baseline (model 0, "Correct1" in the table).  No plots.
+--bootstrap B [--seed S] [--lvis] adds a last block: is the difference in AP more than noise?  Percentile intervals of AP, AP50
+and AP75 per model over B resamples of the images (all replicates in one kernel: COCOEval.bootstrap) and the paired difference with its p."""
 import argparse
 import json
 import os
@@ -25,6 +27,10 @@ def main(argv=None):
                     help="which of AP AP50 AP75 APs APm APl AR1 AR10 AR100 ARs ARm ARl (0..11) go into the per-category table")
     ap.add_argument("--table", default=None, help="write the per-category table to this json file")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--bootstrap", type=int, default=0, metavar="B",
+                    help="add a block with bootstrap intervals of AP / AP50 / AP75 per model and their paired difference over B resamples of the images")
+    ap.add_argument("--seed", type=int, default=0, help="seed of the resamples")
+    ap.add_argument("--lvis", action="store_true", help="the bootstrap block under the LVIS rules (an LVIS ground truth; adds APr / APc / APf)")
     args = ap.parse_args(argv)
 
     import torch
@@ -66,6 +72,32 @@ def main(argv=None):
     r = d.run(args.iou_threshold, args.confidence)
     print(f"== disagreement: {names}, {r['total']} instances on {len(d.img_ids) - r['missed']} images ({r['missed']} images not counted)")
     d.report(alpha=args.alpha)
+    if args.bootstrap:
+        bootstrap_block(args, dataset, results, names, evaluators, dev)
+
+
+def bootstrap_block(args, dataset, results, names, evaluators, dev):
+    """Percentile intervals of AP, AP50, AP75 (under --lvis also APr, APc, APf) per model over resampled images, and the paired difference:
+    both models see the same resamples."""
+    from object_detectors_amd import compare
+    if args.lvis:
+        from object_detectors_amd.lviseval import RESULT_KEYS, LVISEval
+        evs = [LVISEval(dataset, rows, device=dev).evaluate() for rows in results]
+        columns = [(RESULT_KEYS.index(k), k) for k in ("AP", "AP50", "AP75", "APr", "APc", "APf")]
+    else:
+        evs = [evaluators[n] for n in names]
+        columns = [(0, "AP"), (1, "AP50"), (2, "AP75")]
+    weights = compare.bootstrap_weights(len(evs[0].img_ids), args.bootstrap, args.seed)
+    a, b = (e.bootstrap(weights) for e in evs)
+    paired = compare.paired_bootstrap(a, b)
+    print(f"== bootstrap: {args.bootstrap} resamples of {len(evs[0].img_ids)} images, seed {args.seed}, 95% percentile intervals"
+          f"{' (LVIS rules)' if args.lvis else ''}")
+    for c, key in columns:
+        for name, v in zip(names, (a, b)):
+            i = compare.interval(v[:, c])
+            print(f"{key:>6s} {name:>24s} {i['mean']:8.4f} [{i['lo']:.4f}, {i['hi']:.4f}] ({i['n_used']} used)")
+        print(f"{key:>6s} {'difference':>24s} {paired['delta_mean'][c]:+8.4f} [{paired['lo'][c]:+.4f}, {paired['hi'][c]:+.4f}] "
+              f"p={paired['p'][c]:.4f} ({paired['n_used'][c]} used)")
 
 
 if __name__ == "__main__":
