@@ -949,6 +949,33 @@ int mi355det_coco_bootstrap(int32_t num_cats, const int64_t* cat_dt_offsets, con
                             const double* rec_thrs, int32_t num_recs, const int32_t* dt_image, const int32_t* gt_image, const int32_t* weights,
                             int32_t num_images, int32_t num_replicates, double* ap_sum, double* recall, void* stream);
 
+/* ---- Dataset statistics (csrc/dstats_kernels.hip): the per-class table that parameterises TF-IDF re-weighting, from the annotations - what
+ * the reference's yolo/utilities/get_idf.py and IDFTransformer's build branch (custom.py:176-247) compute image by image on the host.
+ *   category_frequencies   image_index, category_index int32 [n_annotations] ON THE DEVICE, one pair per annotation ->
+ *                    instance_freq[c] = the number of annotations of category c, img_freq[c] = the number of distinct images with at least
+ *                    one annotation of c; both int32 [n_categories].  Integer atomics only: exact, independent of the order of the
+ *                    annotations and of scheduling, bit-identical from run to run.  Distinct (image, category) pairs are found with a bitmap
+ *                    of n_images x ceil(n_categories / 32) 32-bit words = the workspace (category_frequencies_workspace bytes); the call
+ *                    zeroes the bitmap, both outputs and `errors` on the stream.  A pair whose image index lies outside [0, n_images) or
+ *                    whose category index lies outside [0, n_categories) is not counted and touches no memory; it adds 1 to errors[0]
+ *                    (int32 on the device), which the caller reads.  Up to category_frequencies_lds_categories() categories the two
+ *                    histograms are kept per workgroup in LDS and only non-zero bins reach memory; beyond, global atomics.
+ *   idf_table        img_freq, instance_freq int32 [n_rows] (the categories that occur: both > 0), n_images = D -> table float64
+ *                    [14, n_rows], rows in this order: smooth, raw, prob, normit, gombit, base2, base10, then the same seven `_obj`.
+ *                    With df = img_freq, p = df / D:  smooth = log((D + 1) / (df + 1)) + 1, raw = log(D / df), prob = log((D - df) / df),
+ *                    normit = -ndtri(p), gombit = -log(-log(1 - p)), base2 = -log2(p), base10 = -log10(p); the `_obj` rows with
+ *                    N = sum of instance_freq (summed in integers) for D and instance_freq for df.  ndtri = the inverse normal
+ *                    distribution function by Cephes' rational approximations (scipy.special.ndtri).  float64 without contraction, one
+ *                    writer per element.  p = 1 (a category in every image, or a single category) gives prob = normit = gombit = -inf
+ *                    as numpy does, never NaN.
+ * MI355DET_EINVAL: a missing operand; n_images, n_categories or n_rows <= 0; n_annotations < 0 or >= 2^31; a workspace that is too small. */
+size_t mi355det_category_frequencies_workspace(int32_t n_images, int32_t n_categories);
+int mi355det_category_frequencies_lds_categories(void);
+int mi355det_category_frequencies(const int32_t* image_index, const int32_t* category_index, int64_t n_annotations, int32_t n_images,
+                                  int32_t n_categories, int32_t* instance_freq, int32_t* img_freq, int32_t* errors, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+int mi355det_idf_table(const int32_t* img_freq, const int32_t* instance_freq, int32_t n_rows, int64_t n_images, double* table, void* stream);
+
 /* ---- Model comparison (csrc/compare_kernels.hip): for two result sets over one ground truth, the best class-agnostic box overlap of every
  * ground-truth instance and whether that detection carries the right label - the per-image body of the reference's
  * notebooks/get_disagreement.py (torchvision box_iou, then max over the detections), for all images and both models in one launch.

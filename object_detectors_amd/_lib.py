@@ -211,6 +211,10 @@ PROTOTYPES = {
     "mi355det_lvis_match": (C.c_int, [i64, vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
     "mi355det_coco_accumulate": (C.c_int, [i32, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp]),
     "mi355det_coco_bootstrap": (C.c_int, [i32, vp, vp, i64, i64, vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp]),
+    "mi355det_category_frequencies_workspace": (sz, [i32, i32]),
+    "mi355det_category_frequencies_lds_categories": (C.c_int, []),
+    "mi355det_category_frequencies": (C.c_int, [vp, vp, i64, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "mi355det_idf_table": (C.c_int, [vp, vp, i32, i64, vp, vp]),
     "mi355det_box_disagreement": (C.c_int, [i64, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, C.c_double, vp, vp, vp, vp]),
 }
 

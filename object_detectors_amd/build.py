@@ -30,6 +30,7 @@ SOURCES = [
     ("rle_kernels.hip", ["-ffp-contract=off"]),          # shares the paste pixel rule with mask_kernels.hip (csrc/mask_paste.h): no twin
     ("cocoeval_kernels.hip", ["-ffp-contract=off"]),     # float64 IoU / precision quotients, compared bit for bit: no twin
     ("bootstrap_kernels.hip", ["-ffp-contract=off"]),    # the float64 quotients of cocoeval_kernels.hip per replicate, bit for bit: no twin
+    ("dstats_kernels.hip", ["-ffp-contract=off"]),       # float64 idf columns in numpy's and Cephes' operation order: no twin
     ("poly_kernels.hip", ["-ffp-contract=off"]),        # float64 polygon walk, ys + s*t + .5 rounded twice as in C: no twin
     ("compare_kernels.hip", ["-ffp-contract=off"]),      # float64 box IoU and its arg-max, compared bit for bit: no twin
     ("resnet_kernels.hip", []),

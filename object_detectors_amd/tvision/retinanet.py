@@ -15,6 +15,7 @@ from torch import nn
 
 from .engine import IMAGE_MEAN, IMAGE_STD, RetinaNetEngine
 from .postprocess import retinanet_postprocess_detections
+from .roi_heads import minibatch_tfidf
 from .transform import GeneralizedRCNNTransform, ImageList, ingested_sizes
 
 
@@ -29,6 +30,11 @@ class RetinaNet(nn.Module):
         self.detections_per_img, self.topk_candidates = detections_per_img, topk_candidates
         self.tfidf = None if tfidf is None else tfidf["values"].to(self.engine.device).float()
         self.tfidf_post = self.tfidf
+        # retinanet.py:125-133: with 'mini_batch' the classification head replaces the row by the batch's own smoothed idf ('tfidf_norm'
+        # p-normalises it) in every training step; inference keeps the constructor's values (tfidf_post)
+        self.num_classes = num_classes
+        self.tfidf_mini_batch = bool(tfidf is not None and tfidf.get("mini_batch", False))
+        self.tfidf_norm = 0 if tfidf is None else tfidf.get("tfidf_norm", 0)
 
     def state_dict(self, *a, **k):
         return self.engine.reference_state_dict()
@@ -64,6 +70,8 @@ class RetinaNet(nn.Module):
                 b = t["boxes"]
                 if b.numel() and bool(((b[:, 2:] <= b[:, :2]).any())):
                     raise ValueError("All bounding boxes should have positive height and width.")                        # retinanet.py:515-525
+            if self.tfidf_mini_batch:
+                self.tfidf = minibatch_tfidf(targets, self.num_classes, self.tfidf_norm).to(self.engine.device).float().reshape(1, -1)
             losses = self.engine.train_step(images, targets, class_scale=self.tfidf)
             return {"classification": losses[0], "bbox_regression": losses[1]}
         out = self.engine.forward(images, training=False)
