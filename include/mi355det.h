@@ -976,6 +976,64 @@ int mi355det_category_frequencies(const int32_t* image_index, const int32_t* cat
                                   size_t workspace_bytes, void* stream);
 int mi355det_idf_table(const int32_t* img_freq, const int32_t* instance_freq, int32_t n_rows, int64_t n_images, double* table, void* stream);
 
+/* ---- Anchor k-means (csrc/kmeans_kernels.hip): the anchor list of a dataset from its annotations - what the reference's
+ * yolo/utilities/kmeans_anchors.py computes with pandas and scikit-learn (the first three anchors per scale of yolo/hydra/dataset/lvis.yaml) -
+ * and k-means on (w, h) under the 1 - IoU distance.  All arithmetic is float64 IEEE without contraction; no floating-point atomics.
+ *   features         per annotation of a listed image (kmeans_anchors.py:20-49), in this order: width = bbox[2] / W, height = bbox[3] / H,
+ *                    aspect = width / height, area = width * height, with W, H the image's integer sizes converted to float64.
+ *   selection, bands a box is kept iff aspect > 0.2 && aspect < 5 (strict; NaN and infinity from a zero height or size fall out by
+ *                    themselves).  Band 0 (small): area < 0.01; band 1 (medium): area > 0.01 && area < 0.1; band 2 (large): area > 0.1.  A
+ *                    kept box whose area is exactly 0.01 or 0.1 belongs to no band, as in the script; it and every dropped box have band -1.
+ *   distance         MI355DET_KMEANS_EUCLID: ((x0 - c0)^2 + (x1 - c1)^2) + ..., summed in feature order.  MI355DET_KMEANS_IOU (features = 2,
+ *                    x = (w, h)): 1 - i / (w * h + cw * ch - i) with i = min(w, cw) * min(h, ch).
+ *   Lloyd pass       for one problem (the points of one band, or all points) and one restart: every point goes to the centre with the
+ *                    smallest distance, ties to the lowest centre index.  After a pass every non-empty cluster's centre becomes
+ *                    sum / count; an EMPTY cluster keeps its centre (scikit-learn relocates it: a stated deviation).  Iteration stops after
+ *                    the first pass in which no label changed - the first pass always counts as changed - or after max_iter passes.  The
+ *                    result is the centres the last assignment was made against, that assignment's labels and counts, and the inertia =
+ *                    the sum of the minimal distances of that pass.  Restarts differ in their initial centres only; the caller picks the
+ *                    lowest inertia, ties to the lowest restart.
+ *   sums             a workgroup owns kmeans_limit(5) = 256 consecutive points.  Per (problem, restart, cluster) and feature it adds the
+ *                    points of that cluster, and per (problem, restart) the minimal distances of all the problem's points (the inertia),
+ *                    in ascending point order; the partials of workgroups l, l + 64, ... are added in ascending order by lane l of one
+ *                    wave, and the 64 lane sums are folded by a fixed xor butterfly (offsets 32, 16, ... 1).  So the order of every sum
+ *                    depends on n and the point's places alone, results are bit-identical from run to run, and two restarts that end in
+ *                    the same clustering with the clusters numbered differently have the same inertia bits (a tie, so the lower restart
+ *                    wins).  Counts and changed-label counts are integers (atomics).
+ * box_features       box_wh float64 [n_annotations, 2] = (bbox[2], bbox[3]), image_index int32 [n_annotations], image_size int32
+ *                    [n_images, 2] = (W, H) -> features float64 [n_annotations, 4], band int8 [n_annotations].  An image index outside
+ *                    [0, n_images) adds 1 to errors[0] (int32 on the device, zeroed by the call) and gives NaN features and band -1.
+ * kmeans_check       errors[0] = points with problem >= 0 that have a non-finite feature or, with the IoU distance, a non-positive one;
+ *                    errors[1] = points with problem >= problems.  int32 [2] on the device, zeroed by the call.
+ * kmeans_begin       resets a run: the previous labels (so that the first pass counts as changed), the done flags, status[0] and n_iter.
+ * kmeans_passes      enqueues n_passes Lloyd passes (two launches each, no host synchronisation) over x float64 [n, features] for all
+ *                    problems and restarts at once: problem int8 [n] gives each point's problem (NULL: all 0; < 0 or >= problems: the point
+ *                    takes part in nothing).  centers float64 [problems, restarts, k, features] in and out; per pass of an unfinished
+ *                    (problem, restart) the call writes sums [problems, restarts, k, features], counts int32 [problems, restarts, k],
+ *                    inertia float64 [problems, restarts], changed int32 [problems, restarts] and adds 1 to n_iter int32
+ *                    [problems, restarts].  A finished (problem, restart) is frozen; status[0] counts them, and passes enqueued after
+ *                    status[0] = problems * restarts return at once.  The caller reads status[0] every few passes.
+ * kmeans_assign      labels int32 [n] and the minimal distance float64 [n] against centers [problems, k, features] (k up to
+ *                    kmeans_limit(4)); a point that takes part in nothing gets label -1 and distance 0.
+ * kmeans_limit       0: problems <= 4, 1: restarts <= 16, 2: k <= 16, 3: features <= 4, 4: k of kmeans_assign <= 64, 5: points per workgroup.
+ * MI355DET_EINVAL: a missing operand; n <= 0 or >= 2^31; a size <= 0 or beyond its limit; the IoU distance with features != 2;
+ * max_iter or n_passes <= 0; a workspace smaller than kmeans_workspace (which is 0 for sizes it refuses). */
+#define MI355DET_KMEANS_EUCLID 0
+#define MI355DET_KMEANS_IOU 1
+int mi355det_kmeans_limit(int which);
+int mi355det_box_features(const double* box_wh, const int32_t* image_index, const int32_t* image_size, int64_t n_annotations, int32_t n_images,
+                          double* features, int8_t* band, int32_t* errors, void* stream);
+size_t mi355det_kmeans_workspace(int64_t n, int32_t problems, int32_t restarts, int32_t k, int32_t features);
+int mi355det_kmeans_check(const double* x, const int8_t* problem, int64_t n, int32_t problems, int32_t features, int32_t metric, int32_t* errors,
+                          void* stream);
+int mi355det_kmeans_begin(int64_t n, int32_t problems, int32_t restarts, int32_t k, int32_t features, int32_t* n_iter, int32_t* status,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int mi355det_kmeans_passes(const double* x, const int8_t* problem, int64_t n, int32_t problems, int32_t restarts, int32_t k, int32_t features,
+                           int32_t metric, int32_t max_iter, int32_t n_passes, double* centers, double* sums, int32_t* counts, double* inertia,
+                           int32_t* n_iter, int32_t* changed, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+int mi355det_kmeans_assign(const double* x, const int8_t* problem, int64_t n, int32_t problems, int32_t k, int32_t features, int32_t metric,
+                           const double* centers, int32_t* labels, double* distance, void* stream);
+
 /* ---- Model comparison (csrc/compare_kernels.hip): for two result sets over one ground truth, the best class-agnostic box overlap of every
  * ground-truth instance and whether that detection carries the right label - the per-image body of the reference's
  * notebooks/get_disagreement.py (torchvision box_iou, then max over the detections), for all images and both models in one launch.

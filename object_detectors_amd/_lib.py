@@ -215,6 +215,13 @@ PROTOTYPES = {
     "mi355det_category_frequencies_lds_categories": (C.c_int, []),
     "mi355det_category_frequencies": (C.c_int, [vp, vp, i64, i32, i32, vp, vp, vp, vp, sz, vp]),
     "mi355det_idf_table": (C.c_int, [vp, vp, i32, i64, vp, vp]),
+    "mi355det_kmeans_limit": (C.c_int, [C.c_int]),
+    "mi355det_box_features": (C.c_int, [vp, vp, vp, i64, i32, vp, vp, vp, vp]),
+    "mi355det_kmeans_workspace": (sz, [i64, i32, i32, i32, i32]),
+    "mi355det_kmeans_check": (C.c_int, [vp, vp, i64, i32, i32, i32, vp, vp]),
+    "mi355det_kmeans_begin": (C.c_int, [i64, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    "mi355det_kmeans_passes": (C.c_int, [vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "mi355det_kmeans_assign": (C.c_int, [vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp]),
     "mi355det_box_disagreement": (C.c_int, [i64, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, C.c_double, vp, vp, vp, vp]),
 }
 

@@ -31,6 +31,7 @@ SOURCES = [
     ("cocoeval_kernels.hip", ["-ffp-contract=off"]),     # float64 IoU / precision quotients, compared bit for bit: no twin
     ("bootstrap_kernels.hip", ["-ffp-contract=off"]),    # the float64 quotients of cocoeval_kernels.hip per replicate, bit for bit: no twin
     ("dstats_kernels.hip", ["-ffp-contract=off"]),       # float64 idf columns in numpy's and Cephes' operation order: no twin
+    ("kmeans_kernels.hip", ["-ffp-contract=off"]),       # float64 distances, centre quotients and fixed-order sums, bit for bit: no twin
     ("poly_kernels.hip", ["-ffp-contract=off"]),        # float64 polygon walk, ys + s*t + .5 rounded twice as in C: no twin
     ("compare_kernels.hip", ["-ffp-contract=off"]),      # float64 box IoU and its arg-max, compared bit for bit: no twin
     ("resnet_kernels.hip", []),

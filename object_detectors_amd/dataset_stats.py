@@ -73,6 +73,27 @@ def idf_columns(img_freq, instance_freq, n_images):
     return table
 
 
+def load_dataset(dataset):
+    """An annotation dict, or the path of its JSON -> the dict."""
+    if isinstance(dataset, (str, os.PathLike)):
+        with open(dataset) as f:
+            dataset = json.load(f)
+    return dataset
+
+
+def listed_annotations(dataset):
+    """The walk-the-images rule shared by dataset_arrays and anchors.box_arrays: (img_ids, keep, pos) with img_ids the sorted distinct ids of
+    `images`, keep a bool mask over `annotations` (False for an annotation whose image_id `images` does not list) and pos the index into
+    img_ids of every kept annotation."""
+    img_ids = np.unique(np.asarray([im["id"] for im in dataset.get("images") or []], dtype=np.int64))
+    ann_img = np.asarray([a["image_id"] for a in dataset.get("annotations") or []], dtype=np.int64)
+    if img_ids.size and ann_img.size:
+        pos = np.minimum(np.searchsorted(img_ids, ann_img), img_ids.size - 1)
+        keep = img_ids[pos] == ann_img
+        return img_ids, keep, pos[keep]
+    return img_ids, np.zeros(ann_img.size, bool), np.zeros(0, np.int64)
+
+
 def dataset_arrays(dataset, dset_name="coco"):
     """A COCO or LVIS annotation dict (or the path of its JSON) -> {'image_index', 'category_index': int32 numpy [A], 'n_images',
     'n_categories', 'names': {category id: name}} by the rules of the reference's loop (custom.py:178-201):
@@ -81,9 +102,7 @@ def dataset_arrays(dataset, dset_name="coco"):
       n_images       every distinct id in `images`, annotated or not;
       annotations    of an image id that `images` does not list are dropped (the reference walks the images, not the annotations).
     ValueError if no annotation is left."""
-    if isinstance(dataset, (str, os.PathLike)):
-        with open(dataset) as f:
-            dataset = json.load(f)
+    dataset = load_dataset(dataset)
     if dset_name not in ("coco", "lvis"):
         raise ValueError("dset_name must be 'coco' or 'lvis'")
     cats = dataset.get("categories") or []
@@ -91,16 +110,8 @@ def dataset_arrays(dataset, dset_name="coco"):
         raise ValueError("dataset_arrays: the dataset lists no categories")
     cat_ids = [int(c["id"]) for c in cats]
     n_categories = (cat_ids[-1] if dset_name == "coco" else max(cat_ids)) + 1
-    img_ids = np.unique(np.asarray([im["id"] for im in dataset.get("images") or []], dtype=np.int64))
-    anns = dataset.get("annotations") or []
-    ann_img = np.asarray([a["image_id"] for a in anns], dtype=np.int64)
-    ann_cat = np.asarray([a["category_id"] for a in anns], dtype=np.int64)
-    if img_ids.size and ann_img.size:
-        pos = np.minimum(np.searchsorted(img_ids, ann_img), img_ids.size - 1)
-        keep = img_ids[pos] == ann_img
-        pos, ann_cat = pos[keep], ann_cat[keep]
-    else:
-        pos = ann_cat = np.zeros(0, np.int64)
+    img_ids, keep, pos = listed_annotations(dataset)
+    ann_cat = np.asarray([a["category_id"] for a in dataset.get("annotations") or []], dtype=np.int64)[keep]
     if pos.size == 0:
         raise ValueError("dataset_arrays: no annotation of a listed image, nothing to count")
     if ann_cat.min() < 0 or ann_cat.max() >= n_categories:
