@@ -1058,6 +1058,63 @@ int mi355det_box_disagreement(int64_t num_images, const int64_t* gt_offsets, int
                               const int64_t* dt_offsets_b, int64_t num_dt_b, const double* dt_box_b, const int64_t* dt_label_b,
                               double iou_threshold, double* best_iou, int32_t* best_index, uint8_t* correct, void* stream);
 
+/* ---- Error breakdown (csrc/tide_kernels.hip): why an evaluated COCOEval / LVISEval (`bbox`) loses AP50, after TIDE (Bolya et al., ECCV
+ * 2020).  Every false positive is one of five kinds, the unexplained false negatives are a sixth, and each kind is priced by the AP50 gained
+ * when that kind alone is fixed; the pricing itself is mi355det_coco_accumulate on the flag arrays tide_fixes writes.
+ * Inputs.  fg = 0.5 must be one of the evaluator's IoU thresholds (index t), bg = 0.1; area range 0 (`all`); the detections are the
+ *   evaluator's kept slots.  A detection is a FALSE POSITIVE when dt_match[0, t, d] == 0 && dt_ignore[0, t, d] == 0.  A ground truth is
+ *   COUNTED when gt_ignore[0, g] == 0, FREE when counted and gt_match[0, t, g] == 0, USED when counted and matched.  A ground truth that is
+ *   not counted (COCO: crowds; LVIS: the ignore flags) takes no part anywhere below.
+ * Overlap.  The pair expression of mi355det_coco_iou in its non-crowd form, float64, no contraction, IEEE division: da = dw*dh, ga = gw*gh,
+ *   w = min(dx+dw, gx+gw) - max(dx, gx), h likewise; w <= 0 || h <= 0 gives 0, otherwise i = w*h and iou = i/(da + ga - i): for a pair of one
+ *   category the bits coco_iou wrote.
+ * Per false positive d of image i and category k.  Walk the counted ground truths of image i in ascending slot order: s, gs = the largest
+ *   overlap with one of category k and that ground truth; o, go = the same over every other category; strict > updates (the lowest slot wins
+ *   a tie); without a candidate the value is 0 and the partner -1.  The first test that holds names the kind:
+ *     1 Cls   o >= fg                 partner go        (tested second)
+ *     2 Loc   bg <= s < fg            partner gs        (tested first)
+ *     3 Both  everything else                           (tested last)
+ *     4 Dupe  s >= fg                                   (tested third)
+ *     5 Bkg   max(s, o) <= bg                           (tested fourth)
+ *   A detection that is not a false positive has kind 0, partner -1 and both overlaps 0.
+ * Miss.  A free ground truth that is the partner of no Loc and of no Cls detection, whatever the claims below decide.
+ * Fixes, each applied alone to the base state.  Loc: walk the image's Loc detections in claim order (descending score, then ascending
+ *   dt_index); one whose partner is free and not yet claimed in this walk claims it and becomes a true positive, every other Loc detection
+ *   is dropped.  Cls: the same walk over the Cls detections; a claimant becomes a true positive of the partner's category, the others are
+ *   dropped.  Both / Dupe / Bkg: those detections are dropped.  Miss: the missed ground truths stop being counted.  FP: every false
+ *   positive is dropped.  FN: every free ground truth stops being counted.
+ * Price.  dAP[kind] = AP50(fixed) - AP50(base), AP50 = the mean over the categories with a counted ground truth of the 101 precision values
+ *   at threshold t, area `all`, from coco_accumulate with dt_rank zero and one max_dets that cuts nothing.  The eight deltas do not add up
+ *   to 1 - AP50: each fix is priced alone.
+ * The image-major view (both entries).  img_dt_offsets / img_gt_offsets [num_images + 1] and img_dt_slots [num_dt] / img_gt_slots [num_gt],
+ *   int64 ON THE DEVICE: image i owns the entries offsets[i]..offsets[i + 1] of the slot lists; its detection slots stand in claim order, its
+ *   ground-truth slots ascending.  num_dt / num_gt are the caller's host copies of the last offsets and size every array: an image whose
+ *   ranges do not fit them is skipped, a slot outside them is passed over, nothing is read or written past them.  dt_cat / gt_cat int32 =
+ *   each slot's category index; dt_fp, gt_counted, gt_free uint8 = the flags above; boxes float64 [*, 4] as [x, y, w, h].
+ *   tide_classify    -> kind uint8 [num_dt], partner int64 [num_dt] (a ground-truth slot or -1), best_same / best_other float64 [num_dt] (s, o),
+ *                    missed uint8 [num_gt].
+ *   tide_fixes       dt_match int32 [num_dt] / dt_ignore uint8 [num_dt] = the evaluator's rows [0, t].  -> fix_dt_match int32 / fix_dt_ignore
+ *                    uint8 [8, 1, num_dt] and fix_gt_ignore uint8 [8, num_gt], the fix in the place of the area range, rows base, Loc,
+ *                    Both, Dupe, Bkg, Miss, FP, FN: a dropped detection has dt_ignore 1, a new true positive dt_match 1 and dt_ignore 0,
+ *                    an uncounted ground truth gt_ignore 1.  The Cls fix moves detections between categories, so it comes per slot:
+ *                    cls_cat int32 (the partner's category for a claimant, else dt_cat), cls_match int32, cls_ignore uint8 [num_dt]; the
+ *                    caller sorts the slots by cls_cat and calls coco_accumulate once more.
+ * One wavefront per image; all floating point is float64 without contraction; no atomics, every output element has one writer (tide_classify
+ * clears a partner's `missed` byte from every lane that names it: the same value), so the output is bit-identical from run to run and the
+ * winner of a claim depends on the claim order alone.  No workspace.  Both entries return MI355DET_EINVAL before any launch for a negative
+ * size and for a missing operand of a side that has slots, tide_classify also for thresholds outside (0, 1] or fg <= bg (tide_fixes takes no
+ * threshold); neither launches when there are no images or no slots at all. */
+int mi355det_tide_classify(int64_t num_images, const int64_t* img_dt_offsets, const int64_t* img_dt_slots, int64_t num_dt,
+                           const int64_t* img_gt_offsets, const int64_t* img_gt_slots, int64_t num_gt, const double* dt_boxes,
+                           const int32_t* dt_cat, const uint8_t* dt_fp, const double* gt_boxes, const int32_t* gt_cat, const uint8_t* gt_counted,
+                           const uint8_t* gt_free, double fg, double bg, uint8_t* kind, int64_t* partner, double* best_same, double* best_other,
+                           uint8_t* missed, void* stream);
+int mi355det_tide_fixes(int64_t num_images, const int64_t* img_dt_offsets, const int64_t* img_dt_slots, int64_t num_dt,
+                        const int64_t* img_gt_offsets, const int64_t* img_gt_slots, int64_t num_gt, const int32_t* dt_match,
+                        const uint8_t* dt_ignore, const int32_t* dt_cat, const int32_t* gt_cat, const uint8_t* gt_counted, const uint8_t* gt_free,
+                        const uint8_t* kind, const int64_t* partner, const uint8_t* missed, int32_t* fix_dt_match, uint8_t* fix_dt_ignore,
+                        uint8_t* fix_gt_ignore, int32_t* cls_cat, int32_t* cls_match, uint8_t* cls_ignore, void* stream);
+
 /* layout / dtype converters at the module boundary */
 int mi355det_nhwc_to_nchw_f32(const void* x, int x_is_bf16, int32_t x_ld, int32_t n, int32_t c, int32_t h,
                               int32_t w, float* out, void* stream);

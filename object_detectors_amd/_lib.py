@@ -223,6 +223,8 @@ PROTOTYPES = {
     "mi355det_kmeans_passes": (C.c_int, [vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "mi355det_kmeans_assign": (C.c_int, [vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp]),
     "mi355det_box_disagreement": (C.c_int, [i64, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, C.c_double, vp, vp, vp, vp]),
+    "mi355det_tide_classify": (C.c_int, [i64, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]),
+    "mi355det_tide_fixes": (C.c_int, [i64, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
 }
 
 def _f16_twins():

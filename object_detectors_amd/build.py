@@ -34,6 +34,7 @@ SOURCES = [
     ("kmeans_kernels.hip", ["-ffp-contract=off"]),       # float64 distances, centre quotients and fixed-order sums, bit for bit: no twin
     ("poly_kernels.hip", ["-ffp-contract=off"]),        # float64 polygon walk, ys + s*t + .5 rounded twice as in C: no twin
     ("compare_kernels.hip", ["-ffp-contract=off"]),      # float64 box IoU and its arg-max, compared bit for bit: no twin
+    ("tide_kernels.hip", ["-ffp-contract=off"]),         # the float64 overlap of cocoeval_kernels.hip across categories, bit for bit: no twin
     ("resnet_kernels.hip", []),
     ("conv_kernels.hip", []),
     ("igemm8_kernels.hip", []),

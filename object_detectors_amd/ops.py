@@ -1237,3 +1237,66 @@ def box_disagreement(gt_offsets, gt_box, gt_label, dt_a, dt_b, iou_threshold):
     check(lib().mi355det_box_disagreement(I, ptr(gt_offsets), G, ptr(gt_box), ptr(gt_label), *args, float(iou_threshold), ptr(best_iou),
                                           ptr(best_index), ptr(correct), stream_ptr()), "box_disagreement")
     return best_iou, best_index, correct
+
+
+# ---- error breakdown (csrc/tide_kernels.hip; the front end on top of these is object_detectors_amd/tide.py)
+def _tide_view(view, what):
+    """(img_dt_offsets, img_dt_slots, img_gt_offsets, img_gt_slots), int64 on the device -> their pointers with the three sizes in place."""
+    dt_off, dt_slots, gt_off, gt_slots = view
+    for t in view:
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()):
+            raise ValueError(f"{what} needs the image view as contiguous int64 CUDA/HIP tensors (no CPU fallback)")
+    I = int(dt_off.shape[0]) - 1
+    if I < 0 or int(gt_off.shape[0]) != I + 1:
+        raise ValueError(f"{what}: both offset tables must hold I + 1 entries")
+    return I, (I, ptr(dt_off), ptr(dt_slots), int(dt_slots.shape[0]), ptr(gt_off), ptr(gt_slots), int(gt_slots.shape[0]))
+
+
+def _tide_typed(what, n, **tensors):
+    """Each named (tensor, dtype) must be a contiguous device tensor of that dtype with n leading entries."""
+    for name, (t, dtype) in tensors.items():
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and int(t.shape[0]) == n):
+            raise ValueError(f"{what}: {name} must be a contiguous {dtype} CUDA/HIP tensor with {n} entries")
+
+
+def tide_classify(view, dt_boxes, dt_cat, dt_fp, gt_boxes, gt_cat, gt_counted, gt_free, fg=0.5, bg=0.1):
+    """mi355det_tide_classify.  `view` = (img_dt_offsets [I + 1], img_dt_slots [ND], img_gt_offsets [I + 1], img_gt_slots [NG]) int64;
+    boxes float64 [*, 4] as [x, y, w, h], dt_cat / gt_cat int32, dt_fp / gt_counted / gt_free uint8, all on the device ->
+    kind uint8 [ND], partner int64 [ND], best_same / best_other float64 [ND], missed uint8 [NG]."""
+    what = "tide_classify"
+    _I, head = _tide_view(view, what)
+    nd, ng, dev = head[3], head[6], view[0].device
+    _tide_typed(what, nd, dt_boxes=(dt_boxes, torch.float64), dt_cat=(dt_cat, torch.int32), dt_fp=(dt_fp, torch.uint8))
+    _tide_typed(what, ng, gt_boxes=(gt_boxes, torch.float64), gt_cat=(gt_cat, torch.int32), gt_counted=(gt_counted, torch.uint8),
+                gt_free=(gt_free, torch.uint8))
+    kind = torch.zeros(nd, dtype=torch.uint8, device=dev)
+    partner = torch.full((nd,), -1, dtype=torch.int64, device=dev)
+    best_same = torch.zeros(nd, dtype=torch.float64, device=dev)
+    best_other = torch.zeros(nd, dtype=torch.float64, device=dev)
+    missed = torch.zeros(ng, dtype=torch.uint8, device=dev)
+    check(lib().mi355det_tide_classify(*head, ptr(dt_boxes), ptr(dt_cat), ptr(dt_fp), ptr(gt_boxes), ptr(gt_cat), ptr(gt_counted), ptr(gt_free),
+                                       float(fg), float(bg), ptr(kind), ptr(partner), ptr(best_same), ptr(best_other), ptr(missed),
+                                       stream_ptr()), what)
+    return kind, partner, best_same, best_other, missed
+
+
+def tide_fixes(view, dt_match, dt_ignore, dt_cat, gt_cat, gt_counted, gt_free, kind, partner, missed):
+    """mi355det_tide_fixes.  `view` as in tide_classify; dt_match int32 [ND] / dt_ignore uint8 [ND] = the evaluator's rows at the analysis
+    threshold, area `all`; kind / partner / missed from tide_classify -> fix_dt_match int32 [8, 1, ND], fix_dt_ignore uint8 [8, 1, ND],
+    fix_gt_ignore uint8 [8, NG] (rows base, Loc, Both, Dupe, Bkg, Miss, FP, FN) and cls_cat int32, cls_match int32, cls_ignore uint8 [ND]."""
+    what = "tide_fixes"
+    _I, head = _tide_view(view, what)
+    nd, ng, dev = head[3], head[6], view[0].device
+    _tide_typed(what, nd, dt_match=(dt_match, torch.int32), dt_ignore=(dt_ignore, torch.uint8), dt_cat=(dt_cat, torch.int32),
+                kind=(kind, torch.uint8), partner=(partner, torch.int64))
+    _tide_typed(what, ng, gt_cat=(gt_cat, torch.int32), gt_counted=(gt_counted, torch.uint8), gt_free=(gt_free, torch.uint8),
+                missed=(missed, torch.uint8))
+    # a slot no image owns keeps the base state
+    fix_dt_match = dt_match.reshape(1, 1, nd).repeat(8, 1, 1)
+    fix_dt_ignore = dt_ignore.reshape(1, 1, nd).repeat(8, 1, 1)
+    fix_gt_ignore = (gt_counted == 0).to(torch.uint8).reshape(1, ng).repeat(8, 1)
+    cls_cat, cls_match, cls_ignore = dt_cat.clone(), dt_match.clone(), dt_ignore.clone()
+    check(lib().mi355det_tide_fixes(*head, ptr(dt_match), ptr(dt_ignore), ptr(dt_cat), ptr(gt_cat), ptr(gt_counted), ptr(gt_free), ptr(kind),
+                                    ptr(partner), ptr(missed), ptr(fix_dt_match), ptr(fix_dt_ignore), ptr(fix_gt_ignore), ptr(cls_cat),
+                                    ptr(cls_match), ptr(cls_ignore), stream_ptr()), what)
+    return fix_dt_match, fix_dt_ignore, fix_gt_ignore, cls_cat, cls_match, cls_ignore

@@ -16,6 +16,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+SIZES = dict(images=5000, categories=80, ground_truths=36000, detections=100)             # the defaults below; tools/bench_tide.py uses them too
+
 
 def device_ms(fn, reps, warmup):
     for _ in range(warmup):
@@ -68,10 +70,10 @@ def synth(images, cats, gts, dets, seed):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--images", type=int, default=5000)
-    ap.add_argument("--categories", type=int, default=80)
-    ap.add_argument("--ground-truths", type=int, default=36000)
-    ap.add_argument("--detections", type=int, default=100, help="per image")
+    ap.add_argument("--images", type=int, default=SIZES["images"])
+    ap.add_argument("--categories", type=int, default=SIZES["categories"])
+    ap.add_argument("--ground-truths", type=int, default=SIZES["ground_truths"])
+    ap.add_argument("--detections", type=int, default=SIZES["detections"], help="per image")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--oracle-images", type=int, default=100, help="images of the subset the numpy test oracle is timed on (0: skip)")

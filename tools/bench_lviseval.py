@@ -19,6 +19,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from tools.bench_cocoeval import device_ms, wall_ms  # noqa: E402
 
+SIZES = dict(images=19809, categories=1203, ground_truths=244707, detections=300)        # the defaults below; tools/bench_tide.py uses them too
+
 
 def synth(images, cats, gts, dets, seed):
     """-> LVIS dataset dict, and the detections as arrays (image id, category id, score, box)."""
@@ -61,10 +63,10 @@ def synth(images, cats, gts, dets, seed):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--images", type=int, default=19809)
-    ap.add_argument("--categories", type=int, default=1203)
-    ap.add_argument("--ground-truths", type=int, default=244707)
-    ap.add_argument("--detections", type=int, default=300, help="per image")
+    ap.add_argument("--images", type=int, default=SIZES["images"])
+    ap.add_argument("--categories", type=int, default=SIZES["categories"])
+    ap.add_argument("--ground-truths", type=int, default=SIZES["ground_truths"])
+    ap.add_argument("--detections", type=int, default=SIZES["detections"], help="per image")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--oracle-images", type=int, default=50, help="images of the subset the numpy test oracle is timed on (0: skip)")
