@@ -25,7 +25,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .cocoeval import STAT_NAMES, image_indices, load_dataset
+from .cocoeval import STAT_NAMES
+from .evalcore import DetectionStore, load_dataset, rank_in_run, score_then_key_order
 
 
 def mcnemar(yes_no, no_yes):
@@ -42,7 +43,7 @@ def mcnemar(yes_no, no_yes):
 
 
 class Disagreement:
-    """get_disagreement.py on the device.  `gt`: see cocoeval.load_dataset.  `max_dets`: keep each model's `max_dets` best-scored detections
+    """get_disagreement.py on the device.  `gt`: see evalcore.load_dataset.  `max_dets`: keep each model's `max_dets` best-scored detections
     of an image, in descending score order (300 is what LVISResults applies); None keeps all, in input order."""
 
     def __init__(self, gt, device=None, max_dets=None):
@@ -67,10 +68,11 @@ class Disagreement:
 
     def reset(self):
         """Forget the detections of both models (the ground truth stays)."""
-        self._det = [{"img": [], "cat": [], "score": [], "box": []} for _ in range(2)]
-        self.num_added = [0, 0]
+        self._det = [DetectionStore(self.device, self.img_ids, self._img_index) for _ in range(2)]
         self.result = None
         self.best_iou = self.best_index = self.correct = self.dt_offsets = None
+
+    num_added = property(lambda self: [side.num_added for side in self._det])
 
     # ---- detections
     def _side(self, model):
@@ -81,50 +83,26 @@ class Disagreement:
     def add(self, model, image_id, category_ids, scores, boxes):
         """The detections of `model` (0 or 1) on one image (or, with image_id a tensor [n], on many): category_ids [n], scores [n], boxes [n, 4]
         as [x, y, w, h].  Tensors stay on the device; float32 is widened exactly."""
-        side, dev = self._side(model), self.device
-        cat = torch.as_tensor(category_ids, device=dev).to(torch.int64).reshape(-1)
-        n = int(cat.shape[0])
-        score = torch.as_tensor(scores, device=dev).to(torch.float64).reshape(-1)
-        box = torch.as_tensor(boxes, device=dev).to(torch.float64).reshape(-1, 4)
-        if score.shape[0] != n or box.shape[0] != n:
-            raise ValueError("Disagreement.add: one score and one box per detection")
-        side["img"].append(image_indices(image_id, n, self.img_ids, self._img_index, dev, "Disagreement.add"))
-        side["cat"].append(cat)
-        side["score"].append(score)
-        side["box"].append(box)
-        self.num_added[model] += n
+        self._side(model).add("Disagreement.add", image_id, category_ids, scores, boxes)
 
     def add_results(self, model, results):
         """COCO result dicts (`image_id`, `category_id`, `score`, `bbox`) of `model` (0 or 1), e.g. a loaded results json."""
-        side, dev = self._side(model), self.device
-        if not results:
-            return
-        side["img"].append(torch.tensor([self._img_index.get(r["image_id"], -1) for r in results], dtype=torch.int64, device=dev))
-        side["cat"].append(torch.tensor([r["category_id"] for r in results], dtype=torch.int64, device=dev))
-        side["score"].append(torch.tensor([r["score"] for r in results], dtype=torch.float64, device=dev))
-        side["box"].append(torch.tensor([r["bbox"] for r in results], dtype=torch.float64, device=dev).reshape(-1, 4))
-        self.num_added[model] += len(results)
+        self._side(model).add_results(results)
 
     def _kept(self, side, confidence):
-        """One model's detections as the kernel takes them: (offsets [I + 1], boxes, labels, per-image counts), image-major; within an image
-        in input order, or with max_dets in descending score order (stable) cut to max_dets."""
+        """One model's detections (its DetectionStore) as the kernel takes them: (offsets [I + 1], boxes, labels, per-image counts),
+        image-major; within an image in input order, or with max_dets in descending score order (stable) cut to max_dets."""
         dev, I = self.device, len(self.img_ids)
-        cat_of = lambda xs, dt, shape: torch.cat(xs) if xs else torch.zeros(shape, dtype=dt, device=dev)
-        img, cat = cat_of(side["img"], torch.int64, (0,)), cat_of(side["cat"], torch.int64, (0,))
-        score, box = cat_of(side["score"], torch.float64, (0,)), cat_of(side["box"], torch.float64, (0, 4))
+        img, cat, score, box = side.tensors()
         src = torch.nonzero((img >= 0) & (score > confidence)).reshape(-1)      # strict; a detection on an unknown image is dropped
         key = img[src]
         if self.max_dets is None:
             perm = torch.sort(key, stable=True).indices
             key = key[perm]
         else:
-            o1 = torch.sort(-score[src], stable=True).indices
-            o2 = torch.sort(key[o1], stable=True).indices
-            perm = o1[o2]
+            perm = score_then_key_order(score[src], key)
             key = key[perm]
-            _u, per = torch.unique_consecutive(key, return_counts=True)
-            rank = torch.arange(int(key.shape[0]), device=dev) - torch.repeat_interleave(torch.cumsum(per, 0) - per, per)
-            top = rank < self.max_dets
+            top = rank_in_run(key) < self.max_dets
             perm, key = perm[top], key[top]
         index = src[perm]
         count = torch.bincount(key, minlength=I) if I else torch.zeros(0, dtype=torch.int64, device=dev)

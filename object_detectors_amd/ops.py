@@ -1094,42 +1094,38 @@ def coco_iou(dt_offsets, gt_offsets, iou_offsets, iou_size, dt_boxes, gt_boxes, 
     return out
 
 
-def coco_match(dt_offsets, gt_offsets, iou_offsets, iou, dt_area, gt_area, gt_crowd, iou_thrs, area_rngs):
-    """mi355det_coco_match -> dt_match int32 [A, T, ND], dt_ignore uint8 [A, T, ND], gt_match int32 [A, T, NG], gt_ignore uint8 [A, NG]."""
+def _match(entry, what, dt_offsets, gt_offsets, iou_offsets, iou, dt_area, gt_area, flags, iou_thrs, area_rngs):
+    """The match entries: `flags` = the uint8 operands between gt_area and iou_thrs (gt_crowd; for LVIS gt_flag, group_not_exhaustive)."""
     dev = iou.device
-    if not iou.is_cuda:
-        raise ValueError("coco_match needs CUDA/HIP tensors (no CPU fallback)")
     ng, nd, ngt = int(dt_offsets.shape[0]) - 1, int(dt_area.shape[0]), int(gt_area.shape[0])
     T, A = int(iou_thrs.shape[0]), int(area_rngs.shape[0])
     dt_match = torch.zeros((A, T, nd), dtype=torch.int32, device=dev)
     dt_ignore = torch.zeros((A, T, nd), dtype=torch.uint8, device=dev)
     gt_match = torch.zeros((A, T, ngt), dtype=torch.int32, device=dev)
     gt_ignore = torch.zeros((A, ngt), dtype=torch.uint8, device=dev)
-    check(lib().mi355det_coco_match(ng, ptr(dt_offsets), ptr(gt_offsets), ptr(iou_offsets), nd, ngt, int(iou.shape[0]), ptr(iou), ptr(dt_area),
-                                    ptr(gt_area), ptr(gt_crowd), ptr(iou_thrs), T, ptr(area_rngs), A, ptr(dt_match), ptr(dt_ignore),
-                                    ptr(gt_match), ptr(gt_ignore), stream_ptr()), "coco_match")
+    check(entry(ng, ptr(dt_offsets), ptr(gt_offsets), ptr(iou_offsets), nd, ngt, int(iou.shape[0]), ptr(iou), ptr(dt_area), ptr(gt_area),
+                *[ptr(f) for f in flags], ptr(iou_thrs), T, ptr(area_rngs), A, ptr(dt_match), ptr(dt_ignore), ptr(gt_match), ptr(gt_ignore),
+                stream_ptr()), what)
     return dt_match, dt_ignore, gt_match, gt_ignore
+
+
+def coco_match(dt_offsets, gt_offsets, iou_offsets, iou, dt_area, gt_area, gt_crowd, iou_thrs, area_rngs):
+    """mi355det_coco_match -> dt_match int32 [A, T, ND], dt_ignore uint8 [A, T, ND], gt_match int32 [A, T, NG], gt_ignore uint8 [A, NG]."""
+    if not iou.is_cuda:
+        raise ValueError("coco_match needs CUDA/HIP tensors (no CPU fallback)")
+    return _match(lib().mi355det_coco_match, "coco_match", dt_offsets, gt_offsets, iou_offsets, iou, dt_area, gt_area, [gt_crowd], iou_thrs,
+                  area_rngs)
 
 
 def lvis_match(dt_offsets, gt_offsets, iou_offsets, iou, dt_area, gt_area, gt_flag, group_not_exhaustive, iou_thrs, area_rngs):
     """mi355det_lvis_match (the match under LVISEval's rules: gt_flag uint8 [NG] = the annotations' ignore flags, group_not_exhaustive uint8
     [groups]) -> the four arrays of coco_match, same layouts."""
-    dev = iou.device
     if not (iou.is_cuda and group_not_exhaustive.is_cuda):
         raise ValueError("lvis_match needs CUDA/HIP tensors (no CPU fallback)")
-    ng, nd, ngt = int(dt_offsets.shape[0]) - 1, int(dt_area.shape[0]), int(gt_area.shape[0])
-    if group_not_exhaustive.dtype != torch.uint8 or int(group_not_exhaustive.shape[0]) != ng:
+    if group_not_exhaustive.dtype != torch.uint8 or int(group_not_exhaustive.shape[0]) != int(dt_offsets.shape[0]) - 1:
         raise ValueError("lvis_match: group_not_exhaustive must be uint8, one flag per group")
-    nel = group_not_exhaustive.contiguous()
-    T, A = int(iou_thrs.shape[0]), int(area_rngs.shape[0])
-    dt_match = torch.zeros((A, T, nd), dtype=torch.int32, device=dev)
-    dt_ignore = torch.zeros((A, T, nd), dtype=torch.uint8, device=dev)
-    gt_match = torch.zeros((A, T, ngt), dtype=torch.int32, device=dev)
-    gt_ignore = torch.zeros((A, ngt), dtype=torch.uint8, device=dev)
-    check(lib().mi355det_lvis_match(ng, ptr(dt_offsets), ptr(gt_offsets), ptr(iou_offsets), nd, ngt, int(iou.shape[0]), ptr(iou), ptr(dt_area),
-                                    ptr(gt_area), ptr(gt_flag), ptr(nel), ptr(iou_thrs), T, ptr(area_rngs), A,
-                                    ptr(dt_match), ptr(dt_ignore), ptr(gt_match), ptr(gt_ignore), stream_ptr()), "lvis_match")
-    return dt_match, dt_ignore, gt_match, gt_ignore
+    return _match(lib().mi355det_lvis_match, "lvis_match", dt_offsets, gt_offsets, iou_offsets, iou, dt_area, gt_area,
+                  [gt_flag, group_not_exhaustive.contiguous()], iou_thrs, area_rngs)
 
 
 def coco_accumulate(cat_dt_offsets, cat_gt_offsets, order, dt_rank, dt_score, dt_match, dt_ignore, gt_ignore, max_dets, rec_thrs):

@@ -5,7 +5,7 @@ detection of a ground truth that is taken) or Bkg - the ground truths no Loc or 
 the AP50 gained when that kind alone is fixed.  The rules are spelled out in include/mi355det.h, "Error breakdown"; they are close to tidecv's
 order of tests, not a port of it.
 
-    ErrorBreakdown(ev)      ev: a COCOEval or LVISEval after evaluate(); it is only read
+    ErrorBreakdown(ev)      ev: a COCOEval or LVISEval after evaluate(); only its public slot attributes (evalcore.py) are read
     .run(fg=0.5, bg=0.1)    torch sorts build the image-major view of the category-major slots (plumbing) -> tide_classify -> tide_fixes ->
                             coco_accumulate twice (seven fixes as eight "area ranges", then the Cls fix with its detections moved) -> dict
     .report(file=None)      the table
@@ -18,19 +18,16 @@ import numpy as np
 import torch
 
 from . import ops
-from .cocoeval import category_order
+from .evalcore import NO_CUT, category_order, masked_mean, zero_rank
 
 KINDS = ("Cls", "Loc", "Both", "Dupe", "Bkg", "Miss")            # kind codes 1..5 on the detections; Miss lives on the ground truths
 FIXES = KINDS + ("FP", "FN")
-NO_CUT = 2 ** 31 - 1                                             # the single "maxDets" of the accumulate passes: every rank passes
 _ROW_OF_FIX = {"Loc": 1, "Both": 2, "Dupe": 3, "Bkg": 4, "Miss": 5, "FP": 6, "FN": 7}     # rows of tide_fixes' arrays; row 0 is the base state
 
 
 def _ap(p, cats=None):
     """precision [R, K] of one state -> the mean of the valid cells the way the evaluators' summarize() takes it (-1: no category counts)."""
-    s = p if cats is None else p[:, np.asarray(cats, np.int64)]
-    s = s[s > -1]
-    return np.float64(-1) if s.size == 0 else np.mean(s)
+    return masked_mean(p if cats is None else p[:, np.asarray(cats, np.int64)])
 
 
 def _delta(fixed, base):
@@ -48,7 +45,6 @@ class ErrorBreakdown:
         if getattr(ev, "iou", None) is None:
             raise RuntimeError("ErrorBreakdown: call evaluate() on the evaluator first")
         self.ev = ev
-        self.is_lvis = hasattr(ev, "freq_groups")
         self.kind = self.partner = self.best_same = self.best_other = self.missed = self.result = None
 
     def _view(self):
@@ -71,7 +67,7 @@ class ErrorBreakdown:
         nd, ng = int(ev.num_dt), int(ev.num_gt)
         slot_cat = lambda off, n: (torch.searchsorted(off, torch.arange(n, device=dev), right=True) - 1).to(torch.int32)
         f = {"view": self._view(), "dt_cat": slot_cat(ev.cat_dt_offsets, nd), "gt_cat": slot_cat(ev.cat_gt_offsets, ng),
-             "dt_match": ev.dt_match[0, t].contiguous(), "dt_ignore": ev.dt_ignore[0, t].contiguous(), "gt_box": ev._ground_truth()["box"]}
+             "dt_match": ev.dt_match[0, t].contiguous(), "dt_ignore": ev.dt_ignore[0, t].contiguous(), "gt_box": ev.gt_boxes}
         f["dt_fp"] = ((f["dt_match"] == 0) & (f["dt_ignore"] == 0)).to(torch.uint8)
         counted = ev.gt_ignore[0] == 0
         f["gt_free"] = (counted & (ev.gt_match[0, t] == 0)).to(torch.uint8)
@@ -89,9 +85,8 @@ class ErrorBreakdown:
     def _price_in_place(self, rec):
         """The base state and the seven in-place fixes in one accumulate call, the fix in the place of the area range -> [R, K, 8] on the device."""
         ev = self.ev
-        rank = torch.zeros(int(ev.num_dt), dtype=torch.int32, device=ev.device)
-        rows, _r, _s = ops.coco_accumulate(ev.cat_dt_offsets, ev.cat_gt_offsets, category_order(ev.cat_dt_offsets, ev.dt_score), rank,
-                                           ev.dt_score, self.fix_dt_match, self.fix_dt_ignore, self.fix_gt_ignore, [NO_CUT], rec)
+        rows, _r, _s = ops.coco_accumulate(ev.cat_dt_offsets, ev.cat_gt_offsets, category_order(ev.cat_dt_offsets, ev.dt_score),
+                                           zero_rank(int(ev.num_dt), ev.device), ev.dt_score, self.fix_dt_match, self.fix_dt_ignore, self.fix_gt_ignore, [NO_CUT], rec)
         return rows[0, :, :, :, 0]
 
     def _price_cls(self, f, rec):
@@ -101,8 +96,7 @@ class ErrorBreakdown:
         perm = claim[torch.sort(self.cls_cat[claim], stable=True).indices].contiguous()
         cat_off = torch.searchsorted(self.cls_cat[perm].to(torch.int64).contiguous(), torch.arange(K + 1, device=dev)).contiguous()
         score = ev.dt_score[perm].contiguous()
-        rank = torch.zeros(nd, dtype=torch.int32, device=dev)
-        cls, _r, _s = ops.coco_accumulate(cat_off, ev.cat_gt_offsets, category_order(cat_off, score), rank, score,
+        cls, _r, _s = ops.coco_accumulate(cat_off, ev.cat_gt_offsets, category_order(cat_off, score), zero_rank(nd, dev), score,
                                           self.cls_match[perm].reshape(1, 1, nd).contiguous(), self.cls_ignore[perm].reshape(1, 1, nd).contiguous(),
                                           self.fix_gt_ignore[:1].contiguous(), [NO_CUT], rec)
         return cls[0, :, :, 0, 0]
@@ -143,7 +137,7 @@ class ErrorBreakdown:
                "dap": np.asarray([_delta(a, total[0]) for a in total[1:]], np.float64),
                "ap_per_category": ap,
                "dap_per_category": np.where(off, np.nan, ap[:, 1:] - ap[:, :1]).reshape(K, 8)}
-        if self.is_lvis:
+        if ev.kind == "lvis":
             groups = [[_ap(p[:, :, j], cats) if len(cats) else np.float64(-1) for j in range(9)] for cats in ev.freq_groups]
             res["dap_per_frequency"] = np.asarray([[_delta(g[j], g[0]) for j in range(1, 9)] for g in groups], np.float64)
         self.result = res

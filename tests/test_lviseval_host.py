@@ -80,7 +80,7 @@ def test_key_tables_of_the_federated_rules():
     e = LVISEval(DATASET, device="cpu")
     gt = e._ground_truth()
     assert gt["key"].tolist() == [1, 1, 2] and gt["index"].tolist() == [0, 2, 1]          # category 1 in image 7 twice, category 2 in image 4
-    assert gt["flag"].tolist() == [0, 0, 1] and gt["no_crowd"].tolist() == [0, 0, 0]
+    assert gt["flag"].tolist() == [0, 0, 1] and gt["crowd"].tolist() == [0, 0, 0]
     assert gt["filter_keys"].tolist() == [1, 2, 3]                                        # the two positive keys and (category 2, image 7) negative
     assert gt["nel_keys"].tolist() == [1]
 

@@ -37,13 +37,13 @@ def once_ms(fn):
 
 def evaluator(kind, size, dev):
     from object_detectors_amd.cocoeval import COCOEval
-    from object_detectors_amd.lviseval import NO_CUT, LVISEval
+    from object_detectors_amd.lviseval import LVISEval
     synth = bench_cocoeval.synth if kind == "coco" else bench_lviseval.synth
     dataset, (d_img, d_cat, d_score, d_box) = synth(size["images"], size["categories"], size["ground_truths"], size["detections"], 0)
     e = COCOEval(dataset, "bbox", device=dev) if kind == "coco" else LVISEval(dataset, device=dev)
     e.add(torch.from_numpy(d_img).to(dev), torch.from_numpy(d_cat).to(dev), torch.from_numpy(d_score).to(dev), boxes=torch.from_numpy(d_box).to(dev))
     e.evaluate().accumulate()
-    return e, (list(e.max_dets) if kind == "coco" else [NO_CUT])
+    return e, list(e.cuts)
 
 
 def bench(kind, size, replicates, rounds, dev):

@@ -2,8 +2,9 @@
 """COCO evaluation on the device at COCO-val size: 5000 images, 80 categories, about 36 000 ground truths, 100 detections per image,
 synthetic boxes (most detections are jittered ground truths, the rest random), `bbox`.
     python tools/bench_cocoeval.py --reps 100 --warmup 5 --out profiles/r13_cocoeval.md
-evaluate() and accumulate() are timed with HIP events after a warm-up and, because both end in a host read, with the wall clock around
-synchronised calls as well; the kernels alone are timed on the grouped arrays evaluate() leaves behind.  For context the numpy
+evaluate(), its two halves (the front end and IoU + match) and accumulate() are timed with HIP events after a warm-up and, because they end
+in a host read, with the wall clock around synchronised calls as well; the kernels alone are timed on the grouped arrays evaluate() leaves
+behind.  For context the numpy
 restatement of the rules that the tests compare against (tests/cocoeval_oracle.py - the test oracle, not pycocotools) is timed on a
 subset of the images.  Prints the markdown table and, with --out, writes it."""
 import argparse
@@ -87,19 +88,22 @@ def main():
     e.add(torch.from_numpy(d_img).to(dev), torch.from_numpy(d_cat).to(dev), torch.from_numpy(d_score).to(dev), boxes=torch.from_numpy(d_box).to(dev))
     t_eval_dev = device_ms(e.evaluate, args.reps, args.warmup)
     t_eval = wall_ms(e.evaluate, args.reps, 0)
+    t_front_dev = device_ms(e._group, args.reps, args.warmup)
+    t_front = wall_ms(e._group, args.reps, 0)
+    iou_size = e._group()
+    t_im_dev = device_ms(lambda: e._match(iou_size), args.reps, args.warmup)
+    t_im = wall_ms(lambda: e._match(iou_size), args.reps, 0)
     t_acc_dev = device_ms(e.accumulate, args.reps, args.warmup)
     t_acc = wall_ms(e.accumulate, args.reps, 0)
     e.summarize()
     # the kernels alone, on what evaluate() left
-    gt = e._ground_truth()
     thr = torch.from_numpy(np.ascontiguousarray(e.iou_thrs)).to(dev)
     rng = torch.from_numpy(np.ascontiguousarray(e.area_rng)).to(dev)
     rec = torch.from_numpy(np.ascontiguousarray(e.rec_thrs)).to(dev)
-    iou_size = int(e.iou.shape[0])
-    t_iou = device_ms(lambda: ops.coco_iou(e.dt_offsets, e.gt_offsets, e.iou_offsets, iou_size, e.dt_boxes, gt["box"], gt["crowd_dev"]),
+    t_iou = device_ms(lambda: ops.coco_iou(e.dt_offsets, e.gt_offsets, e.iou_offsets, iou_size, e.dt_boxes, e.gt_boxes, e.gt_crowd),
                       args.reps, args.warmup)
-    t_match = device_ms(lambda: ops.coco_match(e.dt_offsets, e.gt_offsets, e.iou_offsets, e.iou, e.dt_area, gt["area_dev"], gt["crowd_dev"], thr,
-                                               rng), args.reps, args.warmup)
+    t_match = device_ms(lambda: ops.coco_match(e.dt_offsets, e.gt_offsets, e.iou_offsets, e.iou, e.dt_area, e.gt_area, e.gt_flag, thr, rng),
+                        args.reps, args.warmup)
     t_accum = device_ms(lambda: ops.coco_accumulate(e.cat_dt_offsets, e.cat_gt_offsets, e.order, e.dt_rank, e.dt_score, e.dt_match, e.dt_ignore,
                                                     e.gt_ignore, e.max_dets, rec), args.reps, args.warmup)
     lines = [
@@ -113,6 +117,8 @@ def main():
         "| section | device ms | wall ms |",
         "|---|---:|---:|",
         f"| **COCOEval.evaluate()** (grouping sorts, mi355det_coco_iou, mi355det_coco_match, one host read) | **{t_eval_dev:.3f}** | {t_eval:.3f} |",
+        f"| front end (cut to 100 per group, grouping: torch sorts and searches, one host read) | {t_front_dev:.3f} | {t_front:.3f} |",
+        f"| IoU + match (mi355det_coco_iou, mi355det_coco_match, output allocation) | {t_im_dev:.3f} | {t_im:.3f} |",
         f"| **COCOEval.accumulate()** (per-category sort, mi355det_coco_accumulate, results to the host) | **{t_acc_dev:.3f}** | {t_acc:.3f} |",
         f"| mi355det_coco_iou alone (output allocation included) | {t_iou:.3f} | |",
         f"| mi355det_coco_match alone (output allocation and zeroing included) | {t_match:.3f} | |",
