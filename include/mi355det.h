@@ -814,6 +814,44 @@ int mi355det_mask_rle_emit(const float* dense, const float* masks, const float* 
 int64_t mi355det_rle_to_string(const int32_t* counts, int64_t n, char* out, int64_t cap);
 int64_t mi355det_rle_from_string(const char* s, int32_t* counts, int64_t cap);
 
+/* ---- Run lengths from counts strings (csrc/rle_string_kernels.hip): mi355det_rle_from_string for the n masks of a results file at once,
+ * with the checks, the area and the tight box that the evaluators need of every mask.  bytes: all strings back to back, no separators,
+ * num_bytes in all, ON THE DEVICE.  str_offsets int64 [n + 1]: mask k owns bytes[str_offsets[k]:str_offsets[k + 1]]; the same table is
+ * read by the host checks (`str_offsets`, host memory) and by the kernels (`str_offsets_dev`, the caller's device copy of it).  sizes int32
+ * [n, 2] = [h, w] per mask on the device.  The rules (rleFrString, then the mask store's checks, then rleArea / rleToBbox):
+ *   character  c = byte - 48 must lie in 0..63; its low five bits are payload, low group first; bit 0x20: the token goes on.
+ *   token      at most 7 characters; bit 0x10 of its last character sign-extends it; the string must end with a finished token.
+ *   counts     count m = token m, plus count m - 2 when m > 2: counts 0, 1 and 2 are raw, then two interleaved running sums, one over the
+ *              odd indices from 1 and one over the even indices from 2.  Every count must fit int32 and be >= 0, and the counts must add
+ *              up to h*w; 1 <= h, w and h*w < 2^31.
+ *   area       the sum of the odd-indexed counts.  bbox [xmin, ymin, xmax - xmin + 1, ymax - ymin + 1] over the non-empty runs of ones
+ *              (pixels in column-major order i = x*h + y); a run that goes on into the next column spans y = 0..h-1; zeros for an empty
+ *              mask.
+ * A kernel reads only inside str_offsets_dev[k]:str_offsets_dev[k + 1], whatever the bytes are: a token cut off at the end of its string
+ * is a status, and a range that does not lie in [0, num_bytes] (or holds more than 2^28 characters) is skipped with a status.  Malformed
+ * input sets the mask's status bits (MI355DET_RLESTR_*, 0 = a valid mask) and nothing else.
+ *   rle_strings_count  decodes and checks every mask: status uint8 [n], run_offsets int64 [n + 1] (as mi355det_mask_rle_count gives them:
+ *                      run_offsets[k] = index of mask k's first count; a skipped mask has none) and num_bad int64 [1] = the number of masks
+ *                      with a status, all on the device; a caller that places num_bad behind run_offsets reads both with one copy.
+ *                      EINVAL before any launch for n < 0, a null table, or host str_offsets that do not rise from 0 to num_bytes.
+ *   rle_strings_emit   decodes again and writes counts int32 [run_offsets[n]], area int64 [n] and bbox int32 [n, 4] (nullable).  total_runs
+ *                      is the caller's host copy of run_offsets[n]; capacity < total_runs is an error and no count is written at an index
+ *                      >= capacity or outside the mask's own slots.  What a mask with a status gets is unspecified.
+ * Integers only, no atomics, one writer per element: the output is bit-identical from run to run.  No workspace. */
+#define MI355DET_RLESTR_RANGE 1     /* the byte range does not fit the buffer: skipped */
+#define MI355DET_RLESTR_SIZE 2      /* h, w < 1 or h*w >= 2^31: skipped */
+#define MI355DET_RLESTR_ALPHABET 4  /* a character outside the alphabet */
+#define MI355DET_RLESTR_LONG 8      /* a token of more than 7 characters */
+#define MI355DET_RLESTR_OPEN 16     /* the string ends inside a token */
+#define MI355DET_RLESTR_INT32 32    /* a count that does not fit int32 */
+#define MI355DET_RLESTR_NEGATIVE 64 /* a negative count */
+#define MI355DET_RLESTR_SUM 128     /* the counts do not add up to h*w */
+int mi355det_rle_strings_count(const uint8_t* bytes, int64_t num_bytes, const int64_t* str_offsets, const int64_t* str_offsets_dev,
+                               const int32_t* sizes, int64_t n, int64_t* run_offsets, uint8_t* status, int64_t* num_bad, void* stream);
+int mi355det_rle_strings_emit(const uint8_t* bytes, int64_t num_bytes, const int64_t* str_offsets_dev, const int32_t* sizes, int64_t n,
+                              const int64_t* run_offsets, int64_t total_runs, int32_t* counts, int64_t capacity, int64_t* area,
+                              int32_t* bbox, void* stream);
+
 /* ---- Polygon ground truth as COCO run-length encodings (csrc/poly_kernels.hip; torchvision_models/detection/coco_utils.py:33-47
  * convert_coco_poly_to_mask = pycocotools frPyObjects + decode + any over the parts).  One polygon is k >= 3 points xy (float64, x then y);
  * its annotation's image is h x w.  The rules of pycocotools rleFrPoly, then rleMerge as a union:

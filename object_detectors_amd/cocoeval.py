@@ -14,15 +14,19 @@ What pycocotools' COCOeval computes with a Python loop over images x categories 
 The slot layout evaluate() leaves behind, the detection lists and the accumulate and bootstrap passes are evalcore.py (GroupedEval); here are
 COCO's cut (each group's detections in descending score order, stable, cut to 100), its match rule, the `segm` side and the summary.  The
 LVIS rules (federated annotations, APr / APc / APf) are lviseval.py: another front end and match rule on the same base.
-Out of scope: keypoints / OKS.  Polygon ground truth is converted first: COCOEval(polygons.dataset_to_rle(dataset), "segm")."""
+Out of scope: keypoints / OKS.  Polygon ground truth is converted first: COCOEval(polygons.dataset_to_rle(dataset), "segm").
+
+The masks of a `segm` evaluation live in a _MaskStore (also lviseval.LVISSegmEval's).  On a GPU a list of result dicts whose `counts` are
+all strings - a results file - is decoded, checked and measured by csrc/rle_string_kernels.hip in one call (add_strings); every other form
+is read on the host as before."""
 import numpy as np
 import torch
 
 from . import ops
 from .evalcore import (REC_THRS, GroupedEval, bootstrap_cells, category_order, cell_mean, check_weights, group_offsets,  # noqa: F401 (re-exported)
-                       image_indices, load_dataset, lookup, masked_mean, rank_in_run, score_then_key_order, sort_ground_truth)
+                       image_indices, load_dataset, lookup, masked_mean, rank_in_run, rle_operands, score_then_key_order, sort_ground_truth)
 from .polygons import is_polygon_segmentation
-from .rle import RLEBatch, counts_stats, string_to_counts
+from .rle import RLEBatch, counts_stats, pack_strings, string_to_counts
 
 MAX_DETS = [1, 10, 100]
 AREA_LABELS = ["all", "small", "medium", "large"]
@@ -54,23 +58,70 @@ def _segmentation_counts(seg, bitmaps):
     raise ValueError(f"COCOEval: unsupported segmentation of type {type(seg).__name__}")
 
 
+def _counts_strings(segs):
+    """(sizes int32 [n, 2], the `counts` strings) where every segmentation is a dict whose counts are a str / bytes of a form the string
+    kernels take (ASCII; 1 <= h, w and h*w < 2^31), else None: the host route reads - or refuses - everything else."""
+    if not segs or not all(isinstance(s, dict) and isinstance(s.get("counts"), (str, bytes)) for s in segs):
+        return None
+    try:
+        sizes = np.asarray([s["size"] for s in segs])
+    except (KeyError, ValueError):
+        return None
+    if sizes.ndim != 2 or sizes.shape[1] != 2 or sizes.dtype.kind not in "iu":
+        return None
+    sizes = sizes.astype(np.int64)
+    if (sizes < 1).any() or (sizes[:, 0] * sizes[:, 1] >= (1 << 31)).any() or (sizes >= (1 << 31)).any():
+        return None
+    strings = [s["counts"] for s in segs]
+    if not all(c.isascii() for c in strings if isinstance(c, str)):
+        return None
+    return sizes.astype(np.int32), strings
+
+
 class _MaskStore:
     """Run lengths of many masks in the concatenated counts / offsets form of RLEBatch, with each mask's size, area and tight box."""
 
     def __init__(self, dev):
-        self.dev = dev
-        self.counts, self.lens, self.area, self.bbox, self.sizes = [], [], [], [], []
+        self.dev = torch.device(dev)
+        self.counts, self.lens, self.area, self.bbox, self.sizes = [], [], [], [], []       # one entry per addition: tensors / host arrays
+
+    def add_arrays(self, counts, lens, area, bbox, sizes):
+        """Masks that are run lengths already: counts int32, area int64 [n], bbox int32 [n, 4] as tensors; lens [n], sizes [n, 2] on the
+        host.  Every other way in ends here."""
+        self.counts.append(counts.to(self.dev).to(torch.int32))
+        self.lens.append(np.asarray(lens, np.int64).reshape(-1))
+        self.area.append(area.to(self.dev))
+        self.bbox.append(bbox.to(self.dev))
+        self.sizes.append(np.asarray(sizes, np.int32).reshape(-1, 2))
+
+    def extend(self, other):
+        """The masks of another store of the same device, behind this one's."""
+        for name in ("counts", "lens", "area", "bbox", "sizes"):
+            getattr(self, name).extend(getattr(other, name))
+
+    def add_strings(self, sizes, strings):
+        """Masks given as `counts` strings, decoded, checked and measured by the string kernels (ops.rle_strings) in one call.  A refused
+        mask goes through the host route once more, which raises what it raises for that string."""
+        packed, offsets = pack_strings(strings)
+        counts, runs, area, bbox, status = ops.rle_strings(packed, offsets, sizes, self.dev)
+        if status is not None:
+            bad = np.flatnonzero(status)
+            parse = bad[(status[bad] & ops.RLESTR_PARSE) != 0]    # the host route decodes every string before it sums the first
+            j = int(parse[0] if parse.size else bad[0])
+            _MaskStore("cpu").add_segmentations([{"size": [int(sizes[j][0]), int(sizes[j][1])], "counts": strings[j]}])
+            raise RuntimeError(f"COCOEval: the string kernels refuse mask {j} (status {int(status[j])}) and the host codec does not")
+        self.add_arrays(counts, np.diff(runs), area, bbox, sizes)
 
     def add_batch(self, b):
         area, bbox = b.stats()
-        self.counts.append(b.counts.to(self.dev).to(torch.int32))
-        self.lens.extend(b.offsets[k + 1] - b.offsets[k] for k in range(len(b)))
-        self.area.append(area.to(self.dev))
-        self.bbox.append(bbox.to(self.dev))
-        self.sizes.extend([b.size] * len(b))
+        self.add_arrays(b.counts, np.diff(np.asarray(b.offsets, np.int64)), area, bbox, [b.size] * len(b))
 
     def add_segmentations(self, segs):
-        """Segmentations in any accepted form, in order.  Bitmaps go through ops.mask_rle_dense, one call per shape."""
+        """Segmentations in any accepted form, in order.  On a GPU, a list of nothing but `counts` strings goes through the string kernels
+        (add_strings); everything else is read here on the host, bitmaps through ops.mask_rle_dense, one call per shape."""
+        strings = _counts_strings(segs) if self.dev.type == "cuda" else None
+        if strings is not None:
+            return self.add_strings(*strings)
         bitmaps, parsed = [], []
         for s in segs:
             parsed.append(_segmentation_counts(s, bitmaps))
@@ -101,28 +152,17 @@ class _MaskStore:
                 sub_off.append(sub_off[-1] + len(counts[j]))
             sub = np.concatenate([counts[j] for j in idx])
             area[idx], bbox[idx] = counts_stats(sub, sub_off, size[0])
-        self.counts.append(torch.from_numpy(np.ascontiguousarray(flat, np.int32)).to(self.dev))
-        self.lens.extend(len(c) for c in counts)
-        self.area.append(torch.from_numpy(area).to(self.dev))
-        self.bbox.append(torch.from_numpy(bbox).to(self.dev))
-        self.sizes.extend(size for size, _c in parsed)
+        self.add_arrays(torch.from_numpy(np.ascontiguousarray(flat, np.int32)), [len(c) for c in counts], torch.from_numpy(area),
+                        torch.from_numpy(bbox), [size for size, _c in parsed])
 
     def tensors(self):
         """counts int32, runs int64 [n + 1], area float64 [n], tight boxes float64 [n, 4] on the device; sizes int32 [n, 2] on the host."""
         cat = lambda xs, dt, shape: torch.cat(xs) if xs else torch.zeros(shape, dtype=dt, device=self.dev)
-        runs = torch.from_numpy(np.concatenate([[0], np.cumsum(np.asarray(self.lens, np.int64))]).astype(np.int64)).to(self.dev)
+        lens = np.concatenate(self.lens) if self.lens else np.zeros(0, np.int64)
+        runs = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)).to(self.dev)
         return (cat(self.counts, torch.int32, (0,)).contiguous(), runs, cat(self.area, torch.int64, (0,)).to(torch.float64),
-                cat(self.bbox, torch.int32, (0, 4)).to(torch.float64).contiguous(), np.asarray(self.sizes, np.int32).reshape(-1, 2))
-
-
-def _image_sizes(sizes, img, num_images, what):
-    """Per-image [h, w] of one side's masks ([0, 0]: none); masks of one image must agree."""
-    out = np.zeros((num_images, 2), np.int32)
-    for s, i in zip(sizes, img):
-        if out[i].any() and (out[i] != s).any():
-            raise ValueError(f"COCOEval: the {what} masks of one image differ in size")
-        out[i] = s
-    return out
+                cat(self.bbox, torch.int32, (0, 4)).to(torch.float64).contiguous(),
+                np.concatenate(self.sizes) if self.sizes else np.zeros((0, 2), np.int32))
 
 
 class COCOEval(GroupedEval):
@@ -186,14 +226,9 @@ class COCOEval(GroupedEval):
             self._rle = None
             return self._layout(key, dt_index, score, box, rank=rank)
         gt = self._ground_truth()
-        counts, runs, area, box, sizes = self._masks.tensors()
-        iou_size = self._layout(key, dt_index, score, box, area, rank)
-        host_keys = self.group_keys.cpu().numpy() % max(I, 1)     # the groups' image indices
-        dt_img = _image_sizes(sizes[src.cpu().numpy()], img[src].cpu().numpy(), I, "detection")
-        gt_img = _image_sizes(gt["sizes"], gt["key"] % max(I, 1), I, "ground-truth")
-        has = lambda off: (off[1:] > off[:-1]).cpu().numpy()[:, None]
-        self._rle = {"dt": (counts, runs, self.dt_index.contiguous()), "gt": (gt["counts"], gt["runs"], None),
-                     "dt_sizes": dt_img[host_keys] * has(self.dt_offsets), "gt_sizes": gt_img[host_keys] * has(self.gt_offsets)}
+        masks = self._masks.tensors()
+        iou_size = self._layout(key, dt_index, score, masks[3], masks[2], rank)
+        self._rle = rle_operands(self, masks, gt, src, img)
         return iou_size
 
     def _match(self, iou_size):

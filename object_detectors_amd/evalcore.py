@@ -108,6 +108,31 @@ def masked_mean(s):
     return np.float64(-1) if s.size == 0 else np.mean(s)
 
 
+# ---- the run-length operands of coco_iou (`segm`)
+def image_sizes(sizes, img, num_images, what, name):
+    """Per-image [h, w] of one side's masks ([0, 0]: none): sizes [n, 2] and image indices [n] on the host; masks of one image must agree."""
+    out = np.zeros((num_images, 2), np.int32)
+    sizes, img = np.asarray(sizes, np.int32).reshape(-1, 2), np.asarray(img, np.int64).reshape(-1)
+    out[img] = sizes                                           # one of an image's sizes; it is every mask's unless they differ
+    if (out[img] != sizes).any():
+        raise ValueError(f"{name}: the {what} masks of one image differ in size")
+    return out
+
+
+def rle_operands(ev, masks, gt, src, img):
+    """coco_iou's run-length mode for an evaluator whose _layout() has run: `masks` = the detections' (counts, runs, area, box, sizes) as
+    the mask store gives them, `gt` the ground truth with counts / runs / sizes, `src` the positions (device int64) of the detections
+    that count for the per-image sizes and `img` every detection's image index -> the `rle` dict of ops.coco_iou."""
+    I = len(ev.img_ids)
+    counts, runs, _area, _box, sizes = masks
+    host_keys = ev.group_keys.cpu().numpy() % max(I, 1)       # the groups' image indices
+    dt_img = image_sizes(sizes[src.cpu().numpy()], img[src].cpu().numpy(), I, "detection", ev.name)
+    gt_img = image_sizes(gt["sizes"], gt["key"] % max(I, 1), I, "ground-truth", ev.name)
+    has = lambda off: (off[1:] > off[:-1]).cpu().numpy()[:, None]
+    return {"dt": (counts, runs, ev.dt_index.contiguous()), "gt": (gt["counts"], gt["runs"], None),
+            "dt_sizes": dt_img[host_keys] * has(ev.dt_offsets), "gt_sizes": gt_img[host_keys] * has(ev.gt_offsets)}
+
+
 # ---- bootstrap replicates (csrc/bootstrap_kernels.hip)
 def check_weights(weights, num_images, what):
     """Bootstrap weights, an integer numpy array or tensor [B, num_images] without negative entries -> an int32 tensor (on the device it

@@ -15,7 +15,10 @@ walk with a compile-time switch):
 
 After evaluate() there is no per-group cut (`dt_rank` is zero), and `group_not_exhaustive` [groups] uint8 joins the slot layout.
 
-`bbox` only: LVIS segmentations are polygons; polygons.dataset_to_rle converts them, and wiring that in is a later change."""
+LVISEval is `bbox`; `segm` (lvis-api's `LVISEval(gt, results, 'segm')`) is LVISSegmEval below: the same cut, filter, match, accumulate and
+statistics over masks.  What differs, as in lvis-api: a result's area is its mask's set pixels and its box the mask's tight box
+(LVISResults), the IoU is maskUtils.iou of the run lengths with an all-zero iscrowd, and the ground truth's polygons become run lengths
+once (polygons.segmentations_to_rle = frPyObjects + merge); its area stays the annotation's `area` field."""
 import json
 import sys
 from collections import OrderedDict
@@ -24,7 +27,11 @@ import numpy as np
 import torch
 
 from . import ops
-from .evalcore import NO_CUT, GroupedEval, cell_mean, lookup, masked_mean, member, rank_in_run, score_then_key_order
+from .cocoeval import _MaskStore
+from .evalcore import (NO_CUT, GroupedEval, cell_mean, image_indices, lookup, masked_mean, member, rank_in_run, rle_operands,
+                       score_then_key_order)
+from .polygons import is_polygon_segmentation, segmentations_to_rle
+from .rle import RLEBatch
 
 MAX_DETS = 300
 RESULT_KEYS = ("AP", "AP50", "AP75", "APs", "APm", "APl", "APr", "APc", "APf", "AR@300", "ARs@300", "ARm@300", "ARl@300")
@@ -38,9 +45,11 @@ class LVISEval(GroupedEval):
 
     def __init__(self, lvis_gt, lvis_dt=None, iou_type="bbox", device=None):
         if iou_type != "bbox":
-            raise NotImplementedError(f"LVISEval: iou_type {iou_type!r}: only bbox is evaluated here (LVIS segmentations are polygons, and the "
-                                      "polygon-to-mask conversion is out of scope: DESIGN.md)")
-        super().__init__(lvis_gt, iou_type, device, MAX_DETS)
+            raise NotImplementedError(f"LVISEval: iou_type {iou_type!r}: only bbox is evaluated here (for segm: LVISSegmEval(lvis_gt, lvis_dt))")
+        self._setup(lvis_gt, lvis_dt, iou_type, device)
+
+    def _setup(self, lvis_gt, lvis_dt, iou_type, device):
+        GroupedEval.__init__(self, lvis_gt, iou_type, device, MAX_DETS)
         for im in self.dataset["images"]:
             for field in ("neg_category_ids", "not_exhaustive_category_ids"):
                 if field not in im:
@@ -51,12 +60,16 @@ class LVISEval(GroupedEval):
         freq = {c["id"]: c["frequency"] for c in self.dataset["categories"]}
         self.freq_groups = [[k for k, c in enumerate(self.cat_ids) if freq[c] == f] for f in ("r", "c", "f")]
         if lvis_dt is not None:
-            if isinstance(lvis_dt, (str, bytes)) or hasattr(lvis_dt, "__fspath__"):
-                with open(lvis_dt) as f:
-                    lvis_dt = json.load(f)
-            if not isinstance(lvis_dt, (list, tuple)):
-                raise ValueError("LVISEval: the detections must be a results json path or a list of result dicts")
-            self.add_results(lvis_dt)
+            self._add_given(lvis_dt)
+
+    def _add_given(self, lvis_dt):
+        """The constructor's detections: a results json path or a list of result dicts."""
+        if isinstance(lvis_dt, (str, bytes)) or hasattr(lvis_dt, "__fspath__"):
+            with open(lvis_dt) as f:
+                lvis_dt = json.load(f)
+        if not isinstance(lvis_dt, (list, tuple)):
+            raise ValueError("LVISEval: the detections must be a results json path or a list of result dicts")
+        self.add_results(lvis_dt)
 
     def reset(self):
         super().reset()
@@ -77,6 +90,10 @@ class LVISEval(GroupedEval):
         """The front end: cut, filter, group."""
         I, gt = len(self.img_ids), self._ground_truth()
         img, cat_id, score, box = self._dets.tensors()
+        masks = self._mask_tensors()                               # None for bbox; for segm a detection's box and area are its mask's
+        area = None
+        if masks is not None:
+            box, area = masks[3], masks[2]
         # the cut: descending score (stable), then by image (stable): each image's detections of all categories in score order; rank < 300
         src = torch.nonzero(img >= 0).reshape(-1)
         sel = src[score_then_key_order(score[src], img[src])]
@@ -88,14 +105,20 @@ class LVISEval(GroupedEval):
         sel, key = sel[keep], key[keep]
         # group: a stable sort by key keeps each group's detections in score order
         o = torch.sort(key, stable=True).indices
-        iou_size = self._layout(key[o].contiguous(), sel[o], score, box)
+        iou_size = self._layout(key[o].contiguous(), sel[o], score, box, area)
         self.group_not_exhaustive = member(gt["nel_keys"], self.group_keys).to(torch.uint8).contiguous()
+        self._rle = None if masks is None else rle_operands(self, masks, gt, src, img)
         return iou_size
+
+    def _mask_tensors(self):
+        """The detections' masks as _MaskStore.tensors() gives them; None where the evaluator works on boxes."""
+        return None
 
     def _match(self, iou_size):
         """coco_iou with an all-zero crowd array (never the ignore flags), then lvis_match."""
         thr, rng, _rec = self._params()
-        self.iou = ops.coco_iou(self.dt_offsets, self.gt_offsets, self.iou_offsets, iou_size, self.dt_boxes, self.gt_boxes, self.gt_crowd)
+        self.iou = ops.coco_iou(self.dt_offsets, self.gt_offsets, self.iou_offsets, iou_size, self.dt_boxes, self.gt_boxes, self.gt_crowd,
+                                self._rle)
         self.dt_match, self.dt_ignore, self.gt_match, self.gt_ignore = ops.lvis_match(
             self.dt_offsets, self.gt_offsets, self.iou_offsets, self.iou, self.dt_area, self.gt_area, self.gt_flag, self.group_not_exhaustive,
             thr, rng)
@@ -158,3 +181,98 @@ class LVISEval(GroupedEval):
             title, kind = ("Average Precision", "(AP)") if key.startswith("AP") else ("Average Recall", "(AR)")
             iou, area, cats = rows.get(key, (span, "all", "all"))
             print(template.format(title, kind, iou, area, self.max_dets, cats, value), file=sys.stdout if file is None else file)
+
+
+class LVISSegmEval(LVISEval):
+    """LVISEval for `segm` on the device: lvis-api's `LVISEval(lvis_gt, lvis_dt, 'segm')`.  The ground truth's `segmentation`s are polygons
+    (LVIS's own form; converted once by polygons.segmentations_to_rle) or run lengths, and every image needs `height` and `width`.
+    Detections are masks: add(image_id, category_ids, scores, masks=RLEBatch or dense probabilities) or result dicts with `segmentation`
+    ({"size", "counts"}; on a GPU the counts strings of a whole list are decoded by csrc/rle_string_kernels.hip).  A detection's area is
+    its mask's set pixels and its box the mask's tight box, whatever `bbox` a result dict carries; a mask must have its image's size."""
+
+    def __init__(self, lvis_gt, lvis_dt=None, device=None):
+        self._setup(lvis_gt, lvis_dt, "segm", device)
+
+    def _setup(self, lvis_gt, lvis_dt, iou_type, device):
+        super()._setup(lvis_gt, None, iou_type, device)
+        for im in self.dataset["images"]:
+            if not all(isinstance(im.get(f), (int, np.integer)) and not isinstance(im.get(f), bool) and im[f] >= 1 for f in ("height", "width")):
+                raise ValueError(f"LVISSegmEval: image {im.get('id')} of the ground truth has no height and width")
+        self._image_hw = np.zeros((len(self.img_ids), 2), np.int64)
+        for im in self.dataset["images"]:
+            self._image_hw[self._img_index[im["id"]]] = (im["height"], im["width"])
+        if lvis_dt is not None:
+            self._add_given(lvis_dt)
+
+    def reset(self):
+        super().reset()
+        self._masks = _MaskStore(self.device)
+
+    def _check_sizes(self, img, sizes, what):
+        """Every mask of a known image (img: image indices, -1 = unknown) has that image's size."""
+        img, sizes = np.asarray(img, np.int64).reshape(-1), np.asarray(sizes, np.int64).reshape(-1, 2)
+        known = img >= 0
+        if not known.any():
+            return
+        wrong = np.flatnonzero(known & (sizes != self._image_hw[np.where(known, img, 0)]).any(1))
+        if wrong.size:
+            j = int(wrong[0])
+            h, w = self._image_hw[img[j]]
+            raise ValueError(f"LVISSegmEval: a {what} mask of image {self.img_ids[img[j]]} is {sizes[j][0]}x{sizes[j][1]}, the image {h}x{w}")
+
+    # ---- detections
+    def add(self, image_id, category_ids, scores, masks=None):
+        """GroupedEval.add with masks in place of boxes: an RLEBatch (MaskRCNN(mask_format="rle")) or dense [n, H, W] / [n, 1, H, W]
+        probabilities (`> 0.5` through ops.mask_rle_dense)."""
+        if masks is not None:                                      # without masks DetectionStore.add refuses below
+            if not isinstance(masks, RLEBatch):
+                masks = ops.mask_rle_dense(torch.as_tensor(masks, device=self.device).to(torch.float32), 0.5)
+            if torch.is_tensor(image_id) and image_id.dim() > 0:   # one id per detection: a host read of the ids
+                img = image_indices(image_id, len(masks), self.img_ids, self._img_index, self.device, "LVISSegmEval.add").cpu().numpy()
+            else:
+                img = [self._img_index.get(image_id.item() if torch.is_tensor(image_id) else image_id, -1)]
+            self._check_sizes(img, [masks.size] * len(img), "detection")
+        self._dets.add("LVISSegmEval.add", image_id, category_ids, scores, None, masks)
+        self._masks.add_batch(masks)
+
+    def add_results(self, results):
+        """LVIS result dicts (`image_id`, `category_id`, `score`, `segmentation`); a `bbox` is not read."""
+        if not results:
+            return
+        for r in results:
+            if "segmentation" not in r:
+                raise ValueError("LVISSegmEval: a result without `segmentation`")
+        store = _MaskStore(self.device)
+        store.add_segmentations([r["segmentation"] for r in results])
+        self._check_sizes([self._img_index.get(r["image_id"], -1) for r in results], store.tensors()[4], "detection")
+        self._masks.extend(store)
+        self._dets.add_results(results)
+
+    # ---- ground truth
+    def _build_ground_truth(self):
+        """The annotations' masks in slot order: polygons through polygons.segmentations_to_rle (one conversion), run lengths as they are."""
+        gt = super()._build_ground_truth()
+        anns = [self._anns[o][1] for o in gt["order"]]
+        for a in anns:
+            if "segmentation" not in a:
+                raise ValueError(f"LVISSegmEval: annotation {a.get('id')} of the ground truth has no segmentation")
+        segs = [a["segmentation"] for a in anns]
+        which = [j for j, s in enumerate(segs) if is_polygon_segmentation(s)]
+        store = _MaskStore(self.device)
+        if which:
+            hw = [tuple(int(v) for v in self._image_hw[self._img_index[anns[j]["image_id"]]]) for j in which]
+            r = segmentations_to_rle([segs[j] for j in which], hw, self.device)
+        if which and len(which) == len(segs):                      # LVIS's own form: the run lengths stay on the device
+            store.add_arrays(r.counts, np.diff(np.asarray(r.offsets, np.int64)), r.area, r.bbox, r.sizes)
+        else:
+            if which:                                              # mixed forms: the polygons join the others as count lists
+                host = np.ascontiguousarray(r.counts.detach().cpu().numpy(), dtype=np.int32)
+                for n, j in enumerate(which):
+                    segs[j] = {"size": [int(r.sizes[n][0]), int(r.sizes[n][1])], "counts": host[r.offsets[n]:r.offsets[n + 1]]}
+            store.add_segmentations(segs)
+        gt["counts"], gt["runs"], _area, gt["box"], gt["sizes"] = store.tensors()
+        self._check_sizes(gt["key"] % max(len(self.img_ids), 1), gt["sizes"], "ground-truth")
+        return gt
+
+    def _mask_tensors(self):
+        return self._masks.tensors()

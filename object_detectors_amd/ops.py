@@ -935,6 +935,88 @@ def mask_rle_paste(masks, boxes, img_shape, padding=1, threshold=0.5, capacity=N
     return _mask_rle(None, m, b, D, M, int(padding), H, W, float(threshold), m.device, capacity)
 
 
+# ---- run lengths from counts strings (csrc/rle_string_kernels.hip; the mask store on top of these is cocoeval._MaskStore)
+RLESTR_RANGE, RLESTR_SIZE, RLESTR_ALPHABET, RLESTR_LONG, RLESTR_OPEN, RLESTR_INT32, RLESTR_NEGATIVE, RLESTR_SUM = (1 << b for b in range(8))
+RLESTR_PARSE = RLESTR_ALPHABET | RLESTR_LONG | RLESTR_OPEN | RLESTR_INT32        # what mi355det_rle_from_string refuses
+
+
+def _rle_strings_operands(what, packed, str_offsets, str_offsets_dev, sizes):
+    import numpy as np
+    for t in (packed, str_offsets_dev, sizes):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError(f"{what} needs CUDA/HIP tensors (no CPU fallback)")
+    host = np.ascontiguousarray(str_offsets, dtype=np.int64).reshape(-1)
+    n = int(host.shape[0]) - 1
+    if packed.dtype != torch.uint8 or str_offsets_dev.dtype != torch.int64 or sizes.dtype != torch.int32:
+        raise ValueError(f"{what}: packed must be uint8, str_offsets_dev int64 and sizes int32")
+    if n < 0 or int(str_offsets_dev.numel()) != n + 1 or tuple(sizes.shape) != (n, 2):
+        raise ValueError(f"{what}: str_offsets [n + 1] on both sides and sizes [n, 2]")
+    return packed.contiguous(), host, str_offsets_dev.contiguous(), sizes.contiguous(), n
+
+
+def rle_strings_count(packed, str_offsets, str_offsets_dev, sizes):
+    """mi355det_rle_strings_count: packed uint8 [bytes] on the device, str_offsets int64 [n + 1] on the host and its device copy, sizes int32
+    [n, 2] on the device -> (table int64 [n + 2] on the device: the run offsets [n + 1], then the number of masks with a status; status uint8
+    [n] on the device).  One host read of `table` gives what sizes the counts and whether any mask was refused."""
+    packed, host, d_off, sizes, n = _rle_strings_operands("rle_strings_count", packed, str_offsets, str_offsets_dev, sizes)
+    table = torch.empty(n + 2, dtype=torch.int64, device=packed.device)
+    status = torch.empty(n, dtype=torch.uint8, device=packed.device)
+    check(lib().mi355det_rle_strings_count(ptr(packed), int(packed.numel()), host.ctypes.data_as(C.c_void_p), ptr(d_off), ptr(sizes), n,
+                                           ptr(table), ptr(status), C.c_void_p(table.data_ptr() + 8 * (n + 1)), stream_ptr()),
+          "rle_strings_count")
+    return table, status
+
+
+def rle_strings_emit(packed, str_offsets_dev, sizes, run_offsets, total_runs, capacity=None):
+    """mi355det_rle_strings_emit after rle_strings_count on the same operands: run_offsets int64 [n + 1] on the device, total_runs the
+    host's copy of its last entry -> (counts int32 [total_runs], area int64 [n], bbox int32 [n, 4]) on the device."""
+    for t in (packed, str_offsets_dev, sizes, run_offsets):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError("rle_strings_emit needs CUDA/HIP tensors (no CPU fallback)")
+    n, dev = int(sizes.shape[0]), packed.device
+    if run_offsets.dtype != torch.int64 or int(run_offsets.numel()) < n + 1 or int(str_offsets_dev.numel()) != n + 1:
+        raise ValueError("rle_strings_emit: run_offsets and str_offsets_dev must be int64 [n + 1]")
+    cap = int(total_runs) if capacity is None else int(capacity)
+    counts = torch.empty(max(cap, 0), dtype=torch.int32, device=dev)
+    area = torch.empty(n, dtype=torch.int64, device=dev)
+    bbox = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    check(lib().mi355det_rle_strings_emit(ptr(packed), int(packed.numel()), ptr(str_offsets_dev), ptr(sizes), n, ptr(run_offsets),
+                                          int(total_runs), ptr(counts), cap, ptr(area), ptr(bbox), stream_ptr()), "rle_strings_emit")
+    return counts, area, bbox
+
+
+def rle_strings(packed, str_offsets, sizes, device=None, mark=None):
+    """The masks of a results file from their `counts` strings (rle.pack_strings): packed uint8 [bytes], str_offsets int64 [n + 1] and
+    sizes [n, 2] = [h, w] as host arrays -> (counts int32, run offsets as a host int64 array [n + 1], area int64 [n], bbox int32 [n, 4],
+    status): everything else on the device; status is None when every mask is valid, else a host uint8 array [n] of RLESTR_* bits (the
+    other results are then of no use).  Two uploads (the bytes; the offsets and sizes as one table), count, ONE host read, emit.
+    `mark(name)` is called after the stages "upload", "count" and "emit" (tools/bench_lvissegm.py times them with it)."""
+    import numpy as np
+    dev = torch.device("cuda" if device is None else device)
+    if dev.type != "cuda":
+        raise ValueError("rle_strings needs a CUDA/HIP device (no CPU fallback)")
+    mark = mark or (lambda name: None)
+    host_off = np.ascontiguousarray(str_offsets, dtype=np.int64).reshape(-1)
+    n = int(host_off.shape[0]) - 1
+    sz = np.ascontiguousarray(sizes, dtype=np.int32).reshape(-1, 2)
+    if n < 0 or sz.shape[0] != n:
+        raise ValueError("rle_strings: str_offsets [n + 1] and sizes [n, 2]")
+    table = np.empty(2 * n + 1, np.int64)                  # the offsets, then the sizes: two int32 fill one int64 slot
+    table[:n + 1] = host_off
+    table[n + 1:].view(np.int32)[:] = sz.reshape(-1)
+    d_table = torch.from_numpy(table).to(dev)
+    d_bytes = torch.from_numpy(np.ascontiguousarray(packed, dtype=np.uint8).reshape(-1)).to(dev)
+    d_off, d_sz = d_table[:n + 1], d_table[n + 1:].view(torch.int32).view(n, 2)
+    mark("upload")
+    out, status = rle_strings_count(d_bytes, host_off, d_off, d_sz)
+    mark("count")
+    host = out.cpu().numpy()                               # the one host read: the offsets size the counts, the last entry tells of refusals
+    runs, bad = host[:n + 1], int(host[n + 1])
+    counts, area, bbox = rle_strings_emit(d_bytes, d_off, d_sz, out, int(runs[-1]))
+    mark("emit")
+    return counts, runs, area, bbox, (status.cpu().numpy() if bad else None)
+
+
 # ---- COCO polygons as run lengths, and run lengths as bitmaps (csrc/poly_kernels.hip; the readers on top are object_detectors_amd/polygons.py)
 POLY_MAX_COORD = float(1 << 24)
 

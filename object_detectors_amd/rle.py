@@ -41,6 +41,23 @@ def string_to_counts(s, cap=None):
     return out[:n].copy()
 
 
+def pack_strings(strings):
+    """The `counts` strings of many masks (str or bytes) as the operands of `ops.rle_strings`: one uint8 array with all strings back to
+    back and int64 offsets [n + 1].  A string ends at its first NUL, as it does for string_to_counts."""
+    strings = list(strings)
+    if all(isinstance(s, str) for s in strings):
+        raw = "".join(strings).encode("ascii")             # ASCII: a string's length is its number of bytes
+    else:
+        strings = [s.encode("ascii") if isinstance(s, str) else bytes(s) for s in strings]
+        raw = b"".join(strings)
+    if b"\0" in raw:
+        strings = [(s.encode("ascii") if isinstance(s, str) else s).split(b"\0", 1)[0] for s in strings]
+        raw = b"".join(strings)
+    offsets = np.zeros(len(strings) + 1, np.int64)
+    np.cumsum(np.fromiter(map(len, strings), np.int64, len(strings)), out=offsets[1:])
+    return np.frombuffer(bytearray(raw), np.uint8), offsets      # a writable copy: torch takes it without a warning
+
+
 def counts_stats(counts, offsets, h):
     """Set pixels (int64 [D]) and tight boxes [xmin, ymin, xmax - xmin + 1, ymax - ymin + 1] (int32 [D, 4], zeros for an empty mask) of
     run lengths over columns of height h: concatenated int32 counts, mask d owning counts[offsets[d]:offsets[d + 1]]."""
