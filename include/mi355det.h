@@ -852,6 +852,46 @@ int mi355det_rle_strings_emit(const uint8_t* bytes, int64_t num_bytes, const int
                               const int64_t* run_offsets, int64_t total_runs, int32_t* counts, int64_t capacity, int64_t* area,
                               int32_t* bbox, void* stream);
 
+/* ---- Mask boundaries as run lengths (csrc/boundary_kernels.hip): the masks that `iou_type="boundary"` of lvis-api and of the COCO
+ * boundary-IoU API (Cheng et al., "Boundary IoU", CVPR 2021) compare, made from the masks' run lengths without a bitmap on the host.  The rule:
+ *   dilation   d = int(round(ratio * sqrt(h*h + w*w))) in float64 with ties to even, ratio = 0.02 unless given, 1 where that is below 1.  The
+ *              caller works it out on the host (rle.boundary_dilation) and hands it in per mask.
+ *   erosion    eroded(x, y) = 1 iff the whole (2d+1) x (2d+1) window centred on (x, y) lies inside the image and every pixel of it is set:
+ *              copyMakeBorder(1 px of 0) + cv2.erode(3x3 ones, iterations = d) + crop.
+ *   boundary   mask & ~eroded: a subset of the mask, hence of the mask's tight box.
+ * Boundary IoU is maskUtils.iou (mi355det_coco_iou, run-length mode) on two boundaries with the same iscrowd flags, and the IoU a matcher
+ * sees is min(mask IoU, boundary IoU); both are the callers' business (ops.coco_boundary_iou, COCOEval / LVISSegmEval with "boundary").
+ * Operands: counts int32 [num_counts] and runs int64 [num_src + 1] as the run-length entries give them (mask s owns counts[runs[s]:
+ * runs[s + 1]], which must add up to its h*w; otherwise the result is unspecified, nothing outside the mask's own slots is read or written);
+ * index int64 [n] or null: output mask k is the boundary of source mask index[k] (null: of mask k, and num_src >= n); geom int32 [n, 7] =
+ * h, w, d, then the mask's tight box x, y, w, h (any box that holds every set pixel gives the same result; w or h of 0: the empty mask);
+ * slices int64 [n]: the byte offset of mask k's scratch slice in the workspace.  runs, index, geom and slices are read by the host checks
+ * (host memory) and by the kernels (`*_dev`, the caller's device copies), as str_offsets is in mi355det_rle_strings_count.
+ *   rle_boundary_plan   host only: checks every mask, lays the slices out in chunks of consecutive masks whose slices together stay within
+ *                       budget_bytes (a chunk holds one mask at least) and returns the number of chunks C; chunk_starts int64 [C + 1] (room
+ *                       for n + 1) and workspace_bytes [1] = the largest chunk.  A slice holds three bit planes of the box (64 rows a word)
+ *                       and the mask's scanned counts.
+ *   rle_boundary_count  masks first .. first + num - 1 (one chunk of the plan): num_runs int64 [n] on the device gets each mask's number of
+ *                       counts.  The caller's exclusive sum over all n is run_offsets [n + 1]; one host read of it sizes the counts.
+ *   rle_boundary_emit   the same chunk again: counts int32 at run_offsets[k], area int64 [n] and bbox int32 [n, 4] (nullable; pycocotools
+ *                       `area` / `toBbox` of the boundary).  total_runs is the host copy of run_offsets[n]; capacity < total_runs is an error
+ *                       and no count is written at an index >= capacity or outside the mask's own slots.
+ * Every entry refuses with EINVAL, before any launch: n < 0, a null table, h or w < 1 or h*w >= 2^31, d < 1, a box that leaves its image, an
+ * index that is no source mask, runs that leave the counts; EWORKSPACE: slices that overlap or leave the workspace.  Chunks of one plan may
+ * share one workspace on one stream.  Integers only, no atomics, one writer per element: the output is bit-identical from run to run and does
+ * not depend on the chunking. */
+int64_t mi355det_rle_boundary_plan(const int64_t* runs, int64_t num_src, int64_t num_counts, const int64_t* index, const int32_t* geom, int64_t n,
+                                   int64_t budget_bytes, int64_t* slices, int64_t* chunk_starts, int64_t* workspace_bytes);
+int mi355det_rle_boundary_count(const int32_t* counts, int64_t num_counts, const int64_t* runs, const int64_t* runs_dev, int64_t num_src,
+                                const int64_t* index, const int64_t* index_dev, const int32_t* geom, const int32_t* geom_dev,
+                                const int64_t* slices, const int64_t* slices_dev, int64_t n, int64_t first, int64_t num, int64_t* num_runs,
+                                void* workspace, size_t workspace_bytes, void* stream);
+int mi355det_rle_boundary_emit(const int32_t* counts, int64_t num_counts, const int64_t* runs, const int64_t* runs_dev, int64_t num_src,
+                               const int64_t* index, const int64_t* index_dev, const int32_t* geom, const int32_t* geom_dev,
+                               const int64_t* slices, const int64_t* slices_dev, int64_t n, int64_t first, int64_t num,
+                               const int64_t* run_offsets, int64_t total_runs, int32_t* out_counts, int64_t capacity, int64_t* area,
+                               int32_t* bbox, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Polygon ground truth as COCO run-length encodings (csrc/poly_kernels.hip; torchvision_models/detection/coco_utils.py:33-47
  * convert_coco_poly_to_mask = pycocotools frPyObjects + decode + any over the parts).  One polygon is k >= 3 points xy (float64, x then y);
  * its annotation's image is h x w.  The rules of pycocotools rleFrPoly, then rleMerge as a union:

@@ -202,6 +202,9 @@ PROTOTYPES = {
     "mi355det_rle_from_string": (i64, [C.c_char_p, vp, i64]),
     "mi355det_rle_strings_count": (C.c_int, [vp, i64, vp, vp, vp, i64, vp, vp, vp, vp]),
     "mi355det_rle_strings_emit": (C.c_int, [vp, i64, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp]),
+    "mi355det_rle_boundary_plan": (i64, [vp, i64, i64, vp, vp, i64, i64, vp, vp, vp]),
+    "mi355det_rle_boundary_count": (C.c_int, [vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, sz, vp]),
+    "mi355det_rle_boundary_emit": (C.c_int, [vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, i64, i64, vp, i64, vp, i64, vp, vp, vp, sz, vp]),
     "mi355det_poly_points_count": (C.c_int, [vp, vp, vp, vp, i32, i32, vp, vp]),
     "mi355det_poly_points_emit": (C.c_int, [vp, vp, vp, vp, i32, i32, vp, i64, vp, i64, vp]),
     "mi355det_poly_events": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, vp, i64, vp, vp]),

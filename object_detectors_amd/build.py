@@ -29,6 +29,7 @@ SOURCES = [
     ("mask_kernels.hip", ["-ffp-contract=off"]),
     ("rle_kernels.hip", ["-ffp-contract=off"]),          # shares the paste pixel rule with mask_kernels.hip (csrc/mask_paste.h): no twin
     ("rle_string_kernels.hip", []),                      # counts strings to run lengths: integers only, no twin
+    ("boundary_kernels.hip", []),                        # mask boundaries from run lengths: integers only, no twin
     ("cocoeval_kernels.hip", ["-ffp-contract=off"]),     # float64 IoU / precision quotients, compared bit for bit: no twin
     ("bootstrap_kernels.hip", ["-ffp-contract=off"]),    # the float64 quotients of cocoeval_kernels.hip per replicate, bit for bit: no twin
     ("dstats_kernels.hip", ["-ffp-contract=off"]),       # float64 idf columns in numpy's and Cephes' operation order: no twin

@@ -23,10 +23,10 @@ import numpy as np
 import torch
 
 from . import ops
-from .evalcore import (REC_THRS, GroupedEval, bootstrap_cells, category_order, cell_mean, check_weights, group_offsets,  # noqa: F401 (re-exported)
+from .evalcore import (MASK_TYPES, REC_THRS, GroupedEval, bootstrap_cells, category_order, cell_mean, check_weights, group_offsets,  # noqa: F401 (re-exported)
                        image_indices, load_dataset, lookup, masked_mean, rank_in_run, rle_operands, score_then_key_order, sort_ground_truth)
 from .polygons import is_polygon_segmentation
-from .rle import RLEBatch, counts_stats, pack_strings, string_to_counts
+from .rle import RLEBatch, boundary_dilation, boundary_dilations, counts_stats, pack_strings, string_to_counts
 
 MAX_DETS = [1, 10, 100]
 AREA_LABELS = ["all", "small", "medium", "large"]
@@ -155,6 +155,17 @@ class _MaskStore:
         self.add_arrays(torch.from_numpy(np.ascontiguousarray(flat, np.int32)), [len(c) for c in counts], torch.from_numpy(area),
                         torch.from_numpy(bbox), [size for size, _c in parsed])
 
+    def boundaries(self, dilation_ratio, budget_bytes=1 << 30):
+        """tensors() of the masks' boundaries (ops.rle_boundary, each mask eroded by rle.boundary_dilation of its own size): one conversion
+        of the whole store, one host read of the boxes and one of the run offsets."""
+        cat = lambda xs, dt, shape: torch.cat(xs) if xs else torch.zeros(shape, dtype=dt, device=self.dev)
+        lens = np.concatenate(self.lens) if self.lens else np.zeros(0, np.int64)
+        sizes = np.concatenate(self.sizes) if self.sizes else np.zeros((0, 2), np.int32)
+        counts, runs, area, bbox = ops.rle_boundary(cat(self.counts, torch.int32, (0,)).contiguous(), np.concatenate([[0], np.cumsum(lens)]),
+                                                    sizes, boundary_dilations(sizes, dilation_ratio), cat(self.bbox, torch.int32, (0, 4)),
+                                                    budget_bytes=budget_bytes)
+        return counts, torch.from_numpy(runs).to(self.dev), area.to(torch.float64), bbox.to(torch.float64).contiguous(), sizes
+
     def tensors(self):
         """counts int32, runs int64 [n + 1], area float64 [n], tight boxes float64 [n, 4] on the device; sizes int32 [n, 2] on the host."""
         cat = lambda xs, dt, shape: torch.cat(xs) if xs else torch.zeros(shape, dtype=dt, device=self.dev)
@@ -166,47 +177,53 @@ class _MaskStore:
 
 
 class COCOEval(GroupedEval):
-    """COCOeval for `bbox` or `segm` on the device.  `gt`: see load_dataset.  Detections come in through add() (one image, device tensors) or
+    """COCOeval for `bbox`, `segm` or `boundary` on the device.  `gt`: see load_dataset.  `boundary` (the COCO boundary-IoU API) takes
+    exactly the inputs of `segm` and matches on min(mask IoU, boundary IoU), the boundaries eroded by rle.boundary_dilation(h, w,
+    dilation_ratio); a detection's area and box stay its mask's.  Detections come in through add() (one image, device tensors) or
     add_results() (COCO result dicts); evaluate(), accumulate() and summarize() then follow pycocotools' protocol."""
     kind, flag_field, stat_names = "coco", "iscrowd", STAT_NAMES
     cuts = property(lambda self: self.max_dets)
 
-    def __init__(self, gt, iou_type="bbox", device=None):
-        if iou_type not in ("bbox", "segm"):
-            raise ValueError(f"COCOEval: iou_type {iou_type!r} is not supported (bbox, segm; keypoints / OKS are out of scope)")
+    def __init__(self, gt, iou_type="bbox", device=None, dilation_ratio=0.02):
+        if iou_type not in ("bbox",) + MASK_TYPES:
+            raise ValueError(f"COCOEval: iou_type {iou_type!r} is not supported (bbox, segm, boundary; keypoints / OKS are out of scope)")
+        boundary_dilation(1, 1, dilation_ratio)                        # refuses a ratio <= 0
+        self.dilation_ratio = float(dilation_ratio)
         super().__init__(gt, iou_type, device, list(MAX_DETS))
-        if iou_type == "segm":
+        if self.on_masks:
             for _j, a in self._anns:
                 if is_polygon_segmentation(a.get("segmentation")):
                     _segmentation_counts(a["segmentation"], [])            # raises NotImplementedError
 
     def reset(self):
         super().reset()
-        self._masks = _MaskStore(self.device) if self.iou_type == "segm" else None
+        self._masks = _MaskStore(self.device) if self.on_masks else None
         self.scores = self.stats = None
 
     # ---- detections
     def add(self, image_id, category_ids, scores, boxes=None, masks=None):
         """GroupedEval.add with, for `segm`, masks in place of boxes: an RLEBatch (MaskRCNN(mask_format="rle")) or dense [n, H, W] /
         [n, 1, H, W] probabilities (`> 0.5` through ops.mask_rle_dense)."""
-        if self.iou_type == "segm" and masks is not None and not isinstance(masks, RLEBatch):
+        if self.on_masks and masks is not None and not isinstance(masks, RLEBatch):
             masks = ops.mask_rle_dense(torch.as_tensor(masks, device=self.device).to(torch.float32), 0.5)
         self._dets.add("COCOEval.add", image_id, category_ids, scores, boxes, masks)
-        if self.iou_type == "segm":
+        if self.on_masks:
             self._masks.add_batch(masks)
 
     def add_results(self, results):
         """COCO result dicts (`image_id`, `category_id`, `score` and `bbox` or `segmentation`), e.g. the rows of to_coco_results."""
-        if results and self.iou_type == "segm":
+        if results and self.on_masks:
             self._masks.add_segmentations([r["segmentation"] for r in results])
         super().add_results(results)
 
     def _build_ground_truth(self):
         gt = super()._build_ground_truth()
-        if self.iou_type == "segm":
+        if self.on_masks:
             store = _MaskStore(self.device)
             store.add_segmentations([self._anns[o][1]["segmentation"] for o in gt["order"]])
             gt["counts"], gt["runs"], _area, gt["box"], gt["sizes"] = store.tensors()
+            if self.iou_type == "boundary":
+                gt["boundary"] = store.boundaries(self.dilation_ratio)
         return gt
 
     def _group(self):
@@ -228,13 +245,13 @@ class COCOEval(GroupedEval):
         gt = self._ground_truth()
         masks = self._masks.tensors()
         iou_size = self._layout(key, dt_index, score, masks[3], masks[2], rank)
-        self._rle = rle_operands(self, masks, gt, src, img)
+        self._set_rle(masks, gt, src, img)
         return iou_size
 
     def _match(self, iou_size):
         """coco_iou (crowd pairs take the crowd union), then coco_match with iscrowd as the flag."""
         thr, rng, _rec = self._params()
-        self.iou = ops.coco_iou(self.dt_offsets, self.gt_offsets, self.iou_offsets, iou_size, self.dt_boxes, self.gt_boxes, self.gt_crowd, self._rle)
+        self.iou = self._iou(iou_size)
         self.dt_match, self.dt_ignore, self.gt_match, self.gt_ignore = ops.coco_match(
             self.dt_offsets, self.gt_offsets, self.iou_offsets, self.iou, self.dt_area, self.gt_area, self.gt_flag, thr, rng)
 

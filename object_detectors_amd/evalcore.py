@@ -22,6 +22,7 @@ from . import ops
 IOU_THRS = np.linspace(.5, .95, 10)
 REC_THRS = np.linspace(0, 1, 101)
 AREA_RNG = [[0, 1e10], [0, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e10]]
+MASK_TYPES = ("segm", "boundary")     # the evaluations over masks; "boundary" matches on min(mask IoU, boundary IoU)
 NO_CUT = 2 ** 31 - 1                      # as the single "maxDets" of an accumulate pass: every rank passes
 
 
@@ -295,10 +296,11 @@ class GroupedEval:
 
     def reset(self):
         """Forget the detections (the ground truth stays)."""
-        self._dets = DetectionStore(self.device, self.img_ids, self._img_index, self.iou_type == "bbox", self.iou_type == "segm")
+        self._dets = DetectionStore(self.device, self.img_ids, self._img_index, self.iou_type == "bbox", self.on_masks)
         self.precision = self.recall = self.iou = None
 
     num_added = property(lambda self: self._dets.num_added)
+    on_masks = property(lambda self: self.iou_type in MASK_TYPES)
 
     # ---- detections
     def add(self, image_id, category_ids, scores, boxes=None):
@@ -362,6 +364,27 @@ class GroupedEval:
         self.gt_boxes, self.gt_area, self.gt_flag, self.gt_crowd = gt["box"], gt["area_dev"], gt["flag_dev"], gt["crowd_dev"]
         self.num_dt, self.num_gt, self.num_groups = num_dt, int(gt["key"].shape[0]), int(keys.shape[0])
         return iou_size
+
+    def _set_rle(self, masks, gt, src, img):
+        """After _layout(), for an evaluation over masks: coco_iou's run-length operands (rle_operands) and, for `boundary`, the same
+        operands over the boundaries of the same slots with the boundaries' tight boxes.  The detections' boundaries are made here, once
+        per evaluate(); the ground truth's were made with the ground truth."""
+        self._rle, self._boundary = rle_operands(self, masks, gt, src, img), None
+        if self.iou_type == "boundary":
+            counts, runs, _area, box, _sizes = self._masks.boundaries(self.dilation_ratio)
+            g = gt["boundary"]
+            self._boundary = {"rle": dict(self._rle, dt=(counts, runs, self.dt_index.contiguous()), gt=(g[0], g[1], None)),
+                              "dt_boxes": box[self.dt_index].contiguous(), "gt_boxes": g[3]}
+
+    def _iou(self, iou_size):
+        """The ragged IoU buffer: coco_iou on boxes or masks; for `boundary` the element-wise minimum (float64) of the mask IoU and the
+        IoU of the boundaries, both with the same crowd flags."""
+        iou = ops.coco_iou(self.dt_offsets, self.gt_offsets, self.iou_offsets, iou_size, self.dt_boxes, self.gt_boxes, self.gt_crowd, self._rle)
+        if self.iou_type == "boundary":
+            b = self._boundary
+            iou = torch.minimum(iou, ops.coco_iou(self.dt_offsets, self.gt_offsets, self.iou_offsets, iou_size, b["dt_boxes"], b["gt_boxes"],
+                                                  self.gt_crowd, b["rle"]))
+        return iou
 
     def evaluate(self):
         """Group, IoU, match: leaves the slot layout and the match arrays of the module docstring on the device."""

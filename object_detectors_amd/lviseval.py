@@ -28,10 +28,9 @@ import torch
 
 from . import ops
 from .cocoeval import _MaskStore
-from .evalcore import (NO_CUT, GroupedEval, cell_mean, image_indices, lookup, masked_mean, member, rank_in_run, rle_operands,
-                       score_then_key_order)
+from .evalcore import (MASK_TYPES, NO_CUT, GroupedEval, cell_mean, image_indices, lookup, masked_mean, member, rank_in_run, score_then_key_order)
 from .polygons import is_polygon_segmentation, segmentations_to_rle
-from .rle import RLEBatch
+from .rle import RLEBatch, boundary_dilation
 
 MAX_DETS = 300
 RESULT_KEYS = ("AP", "AP50", "AP75", "APs", "APm", "APl", "APr", "APc", "APf", "AR@300", "ARs@300", "ARm@300", "ARl@300")
@@ -45,7 +44,7 @@ class LVISEval(GroupedEval):
 
     def __init__(self, lvis_gt, lvis_dt=None, iou_type="bbox", device=None):
         if iou_type != "bbox":
-            raise NotImplementedError(f"LVISEval: iou_type {iou_type!r}: only bbox is evaluated here (for segm: LVISSegmEval(lvis_gt, lvis_dt))")
+            raise NotImplementedError(f"LVISEval: iou_type {iou_type!r}: only bbox is evaluated here (for segm and boundary: LVISSegmEval(lvis_gt, lvis_dt, iou_type=...))")
         self._setup(lvis_gt, lvis_dt, iou_type, device)
 
     def _setup(self, lvis_gt, lvis_dt, iou_type, device):
@@ -107,7 +106,10 @@ class LVISEval(GroupedEval):
         o = torch.sort(key, stable=True).indices
         iou_size = self._layout(key[o].contiguous(), sel[o], score, box, area)
         self.group_not_exhaustive = member(gt["nel_keys"], self.group_keys).to(torch.uint8).contiguous()
-        self._rle = None if masks is None else rle_operands(self, masks, gt, src, img)
+        if masks is None:
+            self._rle = None
+        else:
+            self._set_rle(masks, gt, src, img)
         return iou_size
 
     def _mask_tensors(self):
@@ -117,8 +119,7 @@ class LVISEval(GroupedEval):
     def _match(self, iou_size):
         """coco_iou with an all-zero crowd array (never the ignore flags), then lvis_match."""
         thr, rng, _rec = self._params()
-        self.iou = ops.coco_iou(self.dt_offsets, self.gt_offsets, self.iou_offsets, iou_size, self.dt_boxes, self.gt_boxes, self.gt_crowd,
-                                self._rle)
+        self.iou = self._iou(iou_size)
         self.dt_match, self.dt_ignore, self.gt_match, self.gt_ignore = ops.lvis_match(
             self.dt_offsets, self.gt_offsets, self.iou_offsets, self.iou, self.dt_area, self.gt_area, self.gt_flag, self.group_not_exhaustive,
             thr, rng)
@@ -188,10 +189,16 @@ class LVISSegmEval(LVISEval):
     (LVIS's own form; converted once by polygons.segmentations_to_rle) or run lengths, and every image needs `height` and `width`.
     Detections are masks: add(image_id, category_ids, scores, masks=RLEBatch or dense probabilities) or result dicts with `segmentation`
     ({"size", "counts"}; on a GPU the counts strings of a whole list are decoded by csrc/rle_string_kernels.hip).  A detection's area is
-    its mask's set pixels and its box the mask's tight box, whatever `bbox` a result dict carries; a mask must have its image's size."""
+    its mask's set pixels and its box the mask's tight box, whatever `bbox` a result dict carries; a mask must have its image's size.
+    iou_type="boundary" is lvis-api's `LVISEval(lvis_gt, lvis_dt, 'boundary')`, Boundary AP: the same inputs and rules, matched on
+    min(mask IoU, boundary IoU) with the boundaries eroded by rle.boundary_dilation(h, w, dilation_ratio)."""
 
-    def __init__(self, lvis_gt, lvis_dt=None, device=None):
-        self._setup(lvis_gt, lvis_dt, "segm", device)
+    def __init__(self, lvis_gt, lvis_dt=None, device=None, iou_type="segm", dilation_ratio=0.02):
+        if iou_type not in MASK_TYPES:
+            raise ValueError(f"LVISSegmEval: iou_type {iou_type!r} is not supported (segm, boundary; for bbox: LVISEval)")
+        boundary_dilation(1, 1, dilation_ratio)                    # refuses a ratio <= 0
+        self.dilation_ratio = float(dilation_ratio)
+        self._setup(lvis_gt, lvis_dt, iou_type, device)
 
     def _setup(self, lvis_gt, lvis_dt, iou_type, device):
         super()._setup(lvis_gt, None, iou_type, device)
@@ -271,6 +278,8 @@ class LVISSegmEval(LVISEval):
                     segs[j] = {"size": [int(r.sizes[n][0]), int(r.sizes[n][1])], "counts": host[r.offsets[n]:r.offsets[n + 1]]}
             store.add_segmentations(segs)
         gt["counts"], gt["runs"], _area, gt["box"], gt["sizes"] = store.tensors()
+        if self.iou_type == "boundary":
+            gt["boundary"] = store.boundaries(self.dilation_ratio)
         self._check_sizes(gt["key"] % max(len(self.img_ids), 1), gt["sizes"], "ground-truth")
         return gt
 

@@ -1017,6 +1017,102 @@ def rle_strings(packed, str_offsets, sizes, device=None, mark=None):
     return counts, runs, area, bbox, (status.cpu().numpy() if bad else None)
 
 
+# ---- mask boundaries as run lengths (csrc/boundary_kernels.hip; include/mi355det.h "Mask boundaries as run lengths")
+def _host_table(t, dtype, shape, what):
+    """An operand the host checks read: a host array as it is, a device tensor through one copy.  dtype int32: wider integers are clipped
+    into its range first (what is out of range stays out of range for the checks)."""
+    import numpy as np
+    a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+    if dtype == np.int32 and a.dtype != np.int32:
+        a = np.asarray(a, np.int64).clip(-2 ** 31, 2 ** 31 - 1)
+    a = np.ascontiguousarray(a, dtype=dtype)
+    try:
+        return a.reshape(shape)
+    except ValueError:
+        raise ValueError(f"rle_boundary: {what} must have shape {list(shape)}") from None
+
+
+class BoundaryPlan:
+    """The operands of mi355det_rle_boundary_count / _emit, checked and laid out by mi355det_rle_boundary_plan: the host tables, their device
+    copies, the chunks and one workspace for all of them.  count() -> run offsets int64 [n + 1] on the device; emit(run_offsets, total) ->
+    (counts, area, bbox).  ops.rle_boundary is plan, count, one host read, emit; tools/bench_boundary.py times the two passes apart."""
+
+    def __init__(self, counts, runs, sizes, dilation, boxes, index=None, budget_bytes=1 << 30):
+        import numpy as np
+        if not torch.is_tensor(counts) or not counts.is_cuda:
+            raise ValueError("rle_boundary needs CUDA/HIP tensors (no CPU fallback)")
+        for t in (runs, sizes, dilation, boxes, index):
+            if torch.is_tensor(t) and not t.is_cuda:
+                raise ValueError("rle_boundary needs CUDA/HIP tensors (no CPU fallback); tables for the host checks are numpy arrays or lists")
+        if counts.dtype != torch.int32:
+            raise ValueError("rle_boundary: counts must be int32")
+        self.dev, self.counts = counts.device, counts.contiguous()
+        h_runs = _host_table(runs, np.int64, (-1,), "runs")
+        num_src = int(h_runs.shape[0]) - 1
+        if num_src < 0:
+            raise ValueError("rle_boundary: runs must hold masks + 1 entries")
+        h_index = None if index is None else _host_table(index, np.int64, (-1,), "index")
+        self.n = n = num_src if h_index is None else int(h_index.shape[0])
+        geom = np.empty((n, 7), np.int32)
+        geom[:, 0:2] = _host_table(sizes, np.int32, (n, 2), "sizes")
+        dil = np.asarray(dilation.detach().cpu().numpy() if torch.is_tensor(dilation) else dilation)
+        if dil.dtype.kind not in "iu":
+            raise ValueError("rle_boundary: the dilation must be an integer (rle.boundary_dilation)")
+        dil = dil.astype(np.int64).clip(-1, 2 ** 31 - 1).reshape(-1)
+        if dil.size not in (1, n):
+            raise ValueError("rle_boundary: one dilation for all masks, or one per mask")
+        geom[:, 2] = dil if dil.size == n else dil[0]
+        geom[:, 3:7] = _host_table(boxes, np.int32, (n, 4), "boxes")
+        hp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        slices, starts, need = np.zeros(max(n, 1), np.int64), np.zeros(n + 1, np.int64), np.zeros(1, np.int64)
+        chunks = int(lib().mi355det_rle_boundary_plan(hp(h_runs), num_src, int(self.counts.numel()), hp(h_index), hp(geom), n, int(budget_bytes),
+                                                      hp(slices), hp(starts), hp(need)))
+        if chunks < 0:
+            check(chunks, "rle_boundary_plan")
+        self.chunks = [(int(starts[j]), int(starts[j + 1] - starts[j])) for j in range(chunks)]
+        up = lambda a: torch.from_numpy(a).to(self.dev)
+        d_runs = runs.to(torch.int64).contiguous().reshape(-1) if torch.is_tensor(runs) else up(h_runs)
+        d_index = None if h_index is None else (index.to(torch.int64).contiguous().reshape(-1) if torch.is_tensor(index) else up(h_index))
+        d_geom, d_slices = up(geom), up(slices)
+        self.nbytes = int(need[0])
+        self.ws = torch.empty(max(self.nbytes, 8), dtype=torch.uint8, device=self.dev)
+        self._keep = (h_runs, h_index, geom, slices, d_runs, d_index, d_geom, d_slices)
+        self._tables = (ptr(self.counts), int(self.counts.numel()), hp(h_runs), ptr(d_runs), num_src, hp(h_index), ptr(d_index), hp(geom),
+                        ptr(d_geom), hp(slices), ptr(d_slices), n)
+
+    def count(self):
+        i64 = dict(dtype=torch.int64, device=self.dev)
+        num_runs = torch.empty(self.n, **i64)
+        for first, num in self.chunks:
+            check(lib().mi355det_rle_boundary_count(*self._tables, first, num, ptr(num_runs), ptr(self.ws), self.nbytes, stream_ptr()),
+                  "rle_boundary_count")
+        return torch.cat([torch.zeros(1, **i64), torch.cumsum(num_runs, 0)])
+
+    def emit(self, run_offsets, total):
+        out = torch.empty(int(total), dtype=torch.int32, device=self.dev)
+        area = torch.empty(self.n, dtype=torch.int64, device=self.dev)
+        bbox = torch.empty((self.n, 4), dtype=torch.int32, device=self.dev)
+        for first, num in self.chunks:
+            check(lib().mi355det_rle_boundary_emit(*self._tables, first, num, ptr(run_offsets), int(total), ptr(out), int(total), ptr(area),
+                                                   ptr(bbox), ptr(self.ws), self.nbytes, stream_ptr()), "rle_boundary_emit")
+        return out, area, bbox
+
+
+def rle_boundary(counts, runs, sizes, dilation, boxes, index=None, budget_bytes=1 << 30):
+    """The boundaries `mask & ~eroded` of n masks as run lengths (mi355det_rle_boundary_*): counts int32 on the device and runs [masks + 1] as
+    the run-length ops give them, sizes [n, 2] = [h, w], dilation (an int for all, or [n]; rle.boundary_dilation), boxes [n, 4] = the masks'
+    tight boxes [x, y, w, h] and index [n] or None (output mask k is the boundary of mask index[k]) ->
+    (counts int32, run offsets as a host int64 array [n + 1], area int64 [n], bbox int32 [n, 4]); all but the offsets on the device.
+    runs, sizes, dilation, boxes and index are read on the host (they size the scratch and are checked there): host arrays cost nothing,
+    device tensors one copy each.  Then count -> ONE host read of the run offsets -> emit; both passes go over the masks in chunks whose
+    scratch stays within `budget_bytes` (one mask at least), and the result does not depend on the chunking."""
+    plan = BoundaryPlan(counts, runs, sizes, dilation, boxes, index, budget_bytes)
+    run_offsets = plan.count()
+    offsets = run_offsets.cpu().numpy()                    # the one host read: it sizes the counts
+    out, area, bbox = plan.emit(run_offsets, int(offsets[-1]))
+    return out, offsets, area, bbox
+
+
 # ---- COCO polygons as run lengths, and run lengths as bitmaps (csrc/poly_kernels.hip; the readers on top are object_detectors_amd/polygons.py)
 POLY_MAX_COORD = float(1 << 24)
 
@@ -1285,6 +1381,15 @@ def coco_mask_iou(dt, gt, iscrowd):
     rle = {"dt": side(dt), "gt": side(gt), "dt_sizes": [dt.size if D else (0, 0)], "gt_sizes": [gt.size if G else (0, 0)]}
     boxes = lambda b: b.stats()[1].to(dev).to(torch.float64).contiguous()
     return coco_iou(*_one_group(D, G, dev), D * G, boxes(dt), boxes(gt), crowd, rle).reshape(D, G)
+
+
+def coco_boundary_iou(dt, gt, iscrowd, dilation_ratio=0.02):
+    """The IoU that `iou_type="boundary"` matches on: min(mask IoU, boundary IoU), element by element, RLEBatch [D] against RLEBatch [G] of
+    the same [H, W] -> float64 [D, G].  The boundary IoU is coco_mask_iou on RLEBatch.boundary(dilation_ratio) of both sides with the same
+    iscrowd flags (a crowd ground truth divides by the detection's boundary area)."""
+    if not dt.counts.is_cuda or not gt.counts.is_cuda:
+        raise ValueError("coco_boundary_iou needs CUDA/HIP tensors (no CPU fallback)")
+    return torch.minimum(coco_mask_iou(dt, gt, iscrowd), coco_mask_iou(dt.boundary(dilation_ratio), gt.boundary(dilation_ratio), iscrowd))
 
 
 # ---- model comparison (csrc/compare_kernels.hip; the front end on top of it is object_detectors_amd/compare.py)

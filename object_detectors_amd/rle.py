@@ -80,6 +80,24 @@ def counts_stats(counts, offsets, h):
     return area, bbox
 
 
+def boundary_dilation(h, w, ratio=0.02):
+    """The erosion depth d of boundary IoU for an h x w image: int(round(ratio * sqrt(h^2 + w^2))) in float64, ties to even, at least 1
+    (the boundary-IoU API's mask_to_boundary).  Host only."""
+    ratio = float(ratio)
+    if not ratio > 0 or not np.isfinite(ratio):
+        raise ValueError(f"boundary_dilation: the dilation ratio must be positive, not {ratio}")
+    d = int(round(ratio * np.sqrt(int(h) ** 2 + int(w) ** 2)))
+    return 1 if d < 1 else d
+
+
+def boundary_dilations(sizes, ratio=0.02):
+    """boundary_dilation of every row of sizes [n, 2] = [h, w]: int32 numpy [n] (the same float64 expression, np.round = ties to even)."""
+    boundary_dilation(1, 1, ratio)                         # the ratio's check
+    s = np.asarray(sizes, np.int64).reshape(-1, 2)
+    d = np.round(float(ratio) * np.sqrt((s[:, 0] ** 2 + s[:, 1] ** 2).astype(np.float64)))
+    return np.maximum(d, 1).astype(np.int32)
+
+
 class RLEBatch:
     """The run-length encodings of the D masks of one image.
 
@@ -124,6 +142,18 @@ class RLEBatch:
         """[{"size": [H, W], "counts": str}] - the `segmentation` field of a COCO result, one per mask."""
         h, w = self.size
         return [{"size": [h, w], "counts": counts_to_string(self.counts_of(d))} for d in range(len(self))]
+
+    def boundary(self, dilation_ratio=0.02, budget_bytes=1 << 30):
+        """The masks' boundaries `mask & ~eroded` as another RLEBatch, made on the device (ops.rle_boundary; the rule: boundary_dilation
+        and include/mi355det.h, "Mask boundaries as run lengths").  Its area and bbox are the boundaries'."""
+        from . import ops
+        d = boundary_dilation(self.size[0], self.size[1], dilation_ratio)
+        if not self.counts.is_cuda:
+            raise ValueError("RLEBatch.boundary needs CUDA/HIP tensors (no CPU fallback)")
+        _area, bbox = self.stats()
+        counts, offsets, area, box = ops.rle_boundary(self.counts, np.asarray(self.offsets, np.int64), [self.size] * len(self), d, bbox,
+                                                      budget_bytes=budget_bytes)
+        return RLEBatch(self.size, counts, offsets, area, box)
 
     def decode(self):
         """The bitmaps back: uint8 [D, H, W] on the host."""

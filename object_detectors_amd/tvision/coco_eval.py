@@ -61,7 +61,7 @@ class CocoEvaluator:
         for t in iou_types:
             if t == "keypoints":
                 raise ValueError("CocoEvaluator: keypoints (OKS) evaluation is not supported")
-            if t not in ("bbox", "segm"):
+            if t not in ("bbox", "segm", "boundary"):
                 raise ValueError("Unknown iou type {}".format(t))
         self.coco_gt = load_dataset(coco_gt)
         self.iou_types = list(iou_types)
@@ -79,7 +79,7 @@ class CocoEvaluator:
             if image_id in self.predictions:
                 continue
             kept = {k: prediction[k].detach() for k in ("boxes", "scores", "labels") if k in prediction}
-            if "segm" in self.iou_types:
+            if "segm" in self.iou_types or "boundary" in self.iou_types:
                 masks = prediction["masks"]
                 kept["masks"] = masks if isinstance(masks, RLEBatch) else mask_rle_dense(masks, 0.5)
             self.predictions[image_id] = kept
@@ -126,7 +126,7 @@ class CocoEvaluator:
     def prepare(self, predictions, iou_type):
         if iou_type == "bbox":
             return prepare_for_coco_detection(predictions)
-        if iou_type == "segm":
+        if iou_type in ("segm", "boundary"):                   # boundary IoU reads the same masks
             return prepare_for_coco_segmentation(predictions)
         raise ValueError("Unknown iou type {}".format(iou_type))
 
