@@ -721,6 +721,63 @@ int mi355det_ingest_u8(const uint8_t* packed, int64_t packed_bytes, const mi355d
 int mi355det_flip_resize_boxes(const float* boxes, float* out, int64_t g, const int64_t* box_offsets,
                                const mi355det_ingest_image* table_dev, int32_t n, void* stream);
 
+/* ---- YOLO ingest (csrc/cubic_kernels.hip): decoded uint8 images through OpenCV's bicubic resize to the square batch -----------
+ * The YOLO twin of the uint8 ingest above: yolo/dsets/transformations.py:10-53 (ResizeToTensor = cv2.resize(img, (S, S), INTER_CUBIC),
+ * / 255, normalise, boxes to relative xcycwh) for a whole batch, one launch for the images and one for the boxes.
+ *
+ * The rule is OpenCV's 8-bit INTER_CUBIC path, restated from resize.cpp (the C path; a SIMD build of OpenCV may round the last bit
+ * differently).  Each output axis maps a source size `src` to a destination size `dst` on its own.  For an output index d:
+ *   scale    scale = 1.0 / (dst / (double)src)
+ *   position fx = (float)((d + 0.5) * scale - 0.5), the product in double
+ *   split    s = floor(fx), then fx -= s in float32
+ *   weights  float32, A = -0.75, every expression evaluated as written:
+ *              c0 = ((A*(fx+1) - 5A)*(fx+1) + 8A)*(fx+1) - 4A
+ *              c1 = ((A+2)*fx - (A+3))*fx*fx + 1
+ *              c2 = ((A+2)*(1-fx) - (A+3))*(1-fx)*(1-fx) + 1
+ *              c3 = 1 - c0 - c1 - c2, left to right
+ *   fixed    w_k = (short)rint(c_k * 2048): a float32 product, rounded half to even, saturated to int16; not renormalised
+ *   taps     source indices s-1 .. s+2, each clamped to [0, src-1]; no antialiasing, whatever the scale
+ *   pixel    per channel acc = sum_ky wy[ky] * (sum_kx wx[kx] * S[y_ky][x_kx]) in int32 (|acc| < 2^31 for every weight the rule can
+ *            give: the |w_k| of an axis sum to at most 2816 + 2, at fx = 0.5, and 2818 * 2818 * 255 < 2^31), integers, so any order
+ *            gives the same bits
+ *   byte     clamp((acc + (1 << 21)) >> 22, 0, 255), an arithmetic shift
+ *   grey     a [h, w] image is its channel three times (cv2.cvtColor(GRAY2RGB), transformations.py:30-34)
+ *   flip     a flipped image reads source column w - 1 - x (the project's own addition, as in the ingest above)
+ *   value    float32((float32(byte / 255.0 in float64) - mean_c) / std_c): 768 values, which the caller builds on the host with the
+ *            reference's own operations (transformations.py:36-41) and hands over as `lut`
+ * The (s, w0..w3) of an axis depend on (src, dst) alone.  The caller builds them on the host in the order above and uploads them (`taps`);
+ * the kernel does no float arithmetic at all, so nothing on the device has to round as the host does.
+ *   yolo_ingest_u8  out fp32 [n, 3, size, size], every element written once.  packed: the images' bytes back to back ([h, w, 3], or
+ *                   [h, w] where channels == 1); table / table_dev: one entry per image, host copy for the checks and device copy for
+ *                   the kernel; taps_dev: n_taps entries on the device, image i reads [xtab, xtab + size) for its columns and
+ *                   [ytab, ytab + size) for its rows; lut: device fp32 [3][256].  The kernel clamps every tap index itself, so no
+ *                   content of `taps_dev` can make it read outside an image.  EINVAL, before any launch, for n <= 0, a null pointer,
+ *                   size <= 0, h or w <= 0, channels other than 1 or 3, an image that does not lie inside [0, packed_bytes) or an
+ *                   xtab / ytab with [tab, tab + size) outside [0, n_taps).
+ *   yolo_targets    all images' boxes in one launch: boxes float64 [g, 4] (xmin, ymin, w, h) and area float64 [g] concatenated,
+ *                   box_offsets int64 [n + 1] on the device as for flip_resize_boxes.  In float64 (transformations.py:44-49,
+ *                   helper.convert2_rel_xcycwh): where the image is flipped xmin' = w - (xmin + bw) first; xc = xmin / w + (bw / w) / 2,
+ *                   yc = ymin / h + (bh / h) / 2, bw / w, bh / h, cast to float32 into bbox [g, 4]; rel_area [g] = area / (h * w) stays
+ *                   float64.  EINVAL for n <= 0, g < 0 or a null pointer; g == 0 is a no-op. */
+#define MI355DET_YOLO_TILE_H 16
+#define MI355DET_YOLO_TILE_W 64
+typedef struct {
+  int32_t s;     /* floor of the source position: the taps are s-1 .. s+2 */
+  int16_t w[4];  /* the weights in units of 1/2048 */
+} mi355det_cubic_tap;
+typedef struct {
+  int64_t offset;     /* byte offset of the image's bytes in the packed buffer */
+  int32_t h, w;       /* source size */
+  int32_t channels;   /* 3: [h, w, 3]; 1: [h, w], grey */
+  int32_t flip;       /* != 0: mirrored left to right */
+  int32_t xtab, ytab; /* index of the image's first column / row entry in the tap buffer */
+} mi355det_yolo_image;
+int mi355det_yolo_ingest_u8(const uint8_t* packed, int64_t packed_bytes, const mi355det_yolo_image* table,
+                            const mi355det_yolo_image* table_dev, int32_t n, const mi355det_cubic_tap* taps_dev, int64_t n_taps,
+                            const float* lut, float* out, int32_t size, void* stream);
+int mi355det_yolo_targets(const double* boxes, const double* area, int64_t g, const int64_t* box_offsets,
+                          const mi355det_yolo_image* table_dev, int32_t n, float* bbox, double* rel_area, void* stream);
+
 /* ---- output side: detections -> the numbers of the COCO json dicts (csrc/transform_kernels.hip) ----------
  * yolo/procedures/test_one_epoch.py:41-66 (scale = 1): boxes rows (x1,y1,x2,y2,...) with pitch box_ld in network pixels ->
  *   bbox_xywh [k,4] = (x1/inp_dim*W, y1/inp_dim*H, w, h) in the original image, area [k] = w*h, category_id [k] from the label column

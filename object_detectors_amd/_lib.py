@@ -63,6 +63,19 @@ class IngestImage(C.Structure):
     _fields_ = [("offset", i64), ("h", i32), ("w", i32), ("out_h", i32), ("out_w", i32), ("flip", i32), ("first_tile", i32)]
 
 
+YOLO_TILE_H, YOLO_TILE_W = 16, 64
+
+
+class CubicTap(C.Structure):
+    """mi355det_cubic_tap: one output index of one axis of the fixed-point bicubic resize (mi355det_yolo_ingest_u8)."""
+    _fields_ = [("s", i32), ("w", C.c_int16 * 4)]
+
+
+class YoloImage(C.Structure):
+    """mi355det_yolo_image: one uint8 [h, w, 3] or [h, w] image of a packed batch (mi355det_yolo_ingest_u8, mi355det_yolo_targets)."""
+    _fields_ = [("offset", i64), ("h", i32), ("w", i32), ("channels", i32), ("flip", i32), ("xtab", i32), ("ytab", i32)]
+
+
 class PackItem(C.Structure):
     _fields_ = [("w", vp), ("w_fwd", vp), ("w_dgrad", vp), ("shape", ConvShape), ("cout_pad", i32), ("w_is_ohwi", i32)]
 
@@ -184,6 +197,8 @@ PROTOTYPES = {
     "mi355det_ingest_tiles": (i32, [i32, i32]),
     "mi355det_ingest_u8": (C.c_int, [vp, i64, vp, vp, i32, vp, vp, vp, i32, i32, vp]),
     "mi355det_flip_resize_boxes": (C.c_int, [vp, vp, i64, vp, vp, i32, vp]),
+    "mi355det_yolo_ingest_u8": (C.c_int, [vp, i64, vp, vp, i32, vp, i64, vp, vp, i32, vp]),
+    "mi355det_yolo_targets": (C.c_int, [vp, vp, i64, vp, vp, i32, vp, vp, vp]),
     "mi355det_coco_rows": (C.c_int, [vp, i32, vp, vp, i32, i64, f32, f32, f32, i32, i32, vp, vp, vp, vp]),
     "mi355det_fastrcnn_loss_workspace": (sz, [i32]),
     "mi355det_fastrcnn_loss": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]),

@@ -26,6 +26,7 @@ SOURCES = [
     ("proposal_kernels.hip", ["-ffp-contract=off"]),
     ("frcnn_kernels.hip", ["-ffp-contract=off"]),
     ("transform_kernels.hip", ["-ffp-contract=off"]),
+    ("cubic_kernels.hip", ["-ffp-contract=off"]),        # YOLO ingest: integer bicubic, float64 box quotients rounded once each: no twin
     ("mask_kernels.hip", ["-ffp-contract=off"]),
     ("rle_kernels.hip", ["-ffp-contract=off"]),          # shares the paste pixel rule with mask_kernels.hip (csrc/mask_paste.h): no twin
     ("rle_string_kernels.hip", []),                      # counts strings to run lengths: integers only, no twin

@@ -876,6 +876,48 @@ def mask_resize_nearest(masks, size, flip=False):
     return out
 
 
+def _device_bytes(what, **tensors):
+    for name, (t, dtype) in tensors.items():
+        if not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous {dtype} CUDA/HIP tensor (no CPU fallback)")
+
+
+def yolo_ingest_u8(packed, table, table_dev, taps_dev, lut, size, out=None):
+    """mi355det_yolo_ingest_u8: OpenCV's 8-bit bicubic resize to size x size, / 255 and normalise of a packed batch of uint8 images in one
+    launch (the rule: include/mi355det.h).  packed: uint8 [bytes] on the device; table: a host (_lib.YoloImage * n) array, table_dev: its
+    bytes on the device (uint8); taps_dev: the (s, w0..w3) entries of both axes as bytes on the device (uint8, 12 each); lut: fp32 [3, 256]
+    on the device.  Returns fp32 [n, 3, size, size]."""
+    n, size = len(table), int(size)
+    _device_bytes("yolo_ingest_u8", packed=(packed, torch.uint8), table_dev=(table_dev, torch.uint8), taps_dev=(taps_dev, torch.uint8),
+                  lut=(lut, torch.float32))
+    if table_dev.numel() != C.sizeof(table) or taps_dev.numel() % C.sizeof(_lib.CubicTap) or lut.numel() != 768:
+        raise ValueError("yolo_ingest_u8: table_dev, taps_dev or lut has the wrong size")
+    if out is None:
+        out = torch.empty((n, 3, size, size), dtype=torch.float32, device=packed.device)
+    elif tuple(out.shape) != (n, 3, size, size):
+        raise ValueError("yolo_ingest_u8: out must be [n, 3, size, size]")
+    _device_bytes("yolo_ingest_u8", out=(out, torch.float32))
+    check(_lib.lib().mi355det_yolo_ingest_u8(ptr(packed), packed.numel(), C.cast(table, C.c_void_p), ptr(table_dev), n, ptr(taps_dev),
+                                             taps_dev.numel() // C.sizeof(_lib.CubicTap), ptr(lut), ptr(out), size, stream_ptr()), "yolo_ingest_u8")
+    return out
+
+
+def yolo_targets(boxes, area, box_offsets_dev, table_dev, n):
+    """mi355det_yolo_targets: all boxes of a batch in one launch.  boxes float64 [G, 4] (xmin, ymin, w, h) and area float64 [G] on the
+    device, box_offsets_dev int64 [n + 1], table_dev as for `yolo_ingest_u8`.  Returns (bbox fp32 [G, 4] relative xcycwh, flipped where the
+    image is, area / (h * w) float64 [G])."""
+    _device_bytes("yolo_targets", boxes=(boxes, torch.float64), area=(area, torch.float64), box_offsets_dev=(box_offsets_dev, torch.int64),
+                  table_dev=(table_dev, torch.uint8))
+    g = int(area.numel())
+    if tuple(boxes.shape) != (g, 4) or box_offsets_dev.numel() != n + 1 or table_dev.numel() != n * C.sizeof(_lib.YoloImage):
+        raise ValueError("yolo_targets: boxes [G, 4], area [G], box_offsets [n + 1] and a table of n images are expected")
+    bbox = torch.empty((g, 4), dtype=torch.float32, device=boxes.device)
+    rel = torch.empty((g,), dtype=torch.float64, device=boxes.device)
+    check(_lib.lib().mi355det_yolo_targets(ptr(boxes), ptr(area), g, ptr(box_offsets_dev), ptr(table_dev), int(n), ptr(bbox), ptr(rel), stream_ptr()),
+          "yolo_targets")
+    return bbox, rel
+
+
 def paste_masks(masks, boxes, img_shape, padding=1):
     """paste_masks_in_image (roi_heads.py:517-537): masks [D, 1, M, M] fp32, boxes [D, 4] -> [D, 1, H, W] fp32."""
     m = _f32c(masks)

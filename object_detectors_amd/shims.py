@@ -7,7 +7,8 @@ What gets registered (the call sites of the hot path):
 
   yolo side        nets.yolo_forw.YOLOForw, nets.yolohead.YoloHead, nets.backbone.backbone_fn,
                    utilities.helper.{bbox_iou, nms_majority, get_abs_coord}, procedures.test_one_epoch.{postprocess, to_coco_results},
-                   procedures.train_one_epoch.{get_new_scale, multiscale_batch}, procedures.initialize.{save_model, load_checkpoint}
+                   procedures.train_one_epoch.{get_new_scale, multiscale_batch}, procedures.initialize.{save_model, load_checkpoint},
+                   dsets.transformations.{ResizeToTensor, COCO91_80, Class1_0}
   torchvision side torchvision.ops.boxes.{box_iou, nms, batched_nms, clip_boxes_to_image, remove_small_boxes},
                    torchvision.ops.{sigmoid_focal_loss, roi_align, MultiScaleRoIAlign, boxes},
                    tvision.{retinanet, frcnn, mask_rcnn, _utils, anchor_utils, rpn, roi_heads, transform, image_list, coco_eval, coco_utils}
@@ -31,6 +32,7 @@ _YOLO_ATTRS = {
     "procedures.test_one_epoch": ("object_detectors_amd.yolo.procedures.test_one_epoch", ("postprocess", "to_coco_results")),
     "procedures.train_one_epoch": ("object_detectors_amd.yolo.procedures.train_one_epoch", ("get_new_scale", "multiscale_batch")),
     "procedures.initialize": ("object_detectors_amd.yolo.procedures.initialize", ("save_model", "load_checkpoint")),
+    "dsets.transformations": ("object_detectors_amd.yolo.dsets.transformations", ("ResizeToTensor", "COCO91_80", "Class1_0")),
 }
 _TV_ATTRS = {
     "torchvision.ops.boxes": ("object_detectors_amd.tvision.boxes", ("box_iou", "nms", "batched_nms", "clip_boxes_to_image", "remove_small_boxes")),
