@@ -721,6 +721,75 @@ int mi355det_ingest_u8(const uint8_t* packed, int64_t packed_bytes, const mi355d
 int mi355det_flip_resize_boxes(const float* boxes, float* out, int64_t g, const int64_t* box_offsets,
                                const mi355det_ingest_image* table_dev, int32_t n, void* stream);
 
+/* ---- SSD augmentations of the uint8 ingest (csrc/augment_kernels.hip): detection/transforms.py:54-239 on the packed bytes ------
+ * The reference's `ssd` and `ssdlite` policies (detection/presets.py:12-25) run on PIL images, so every stage is Pillow's 8-bit
+ * arithmetic.  The host decides (tvision/transforms.py) and hands over tables; the kernels apply.
+ *
+ * photometric_u8: RandomPhotometricDistort, in place on the packed bytes.  One entry per image THAT HAS OPS (m <= n), at most
+ * MI355DET_PHOTO_MAX_OPS ops in order and then a channel permutation.  The rules, per pixel (R, G, B):
+ *   blend(d, v, f)  t = d + f * (v - d) with f and the arithmetic in float32, clipped to [0, 255], truncated (Image.blend)
+ *   L               (19595 R + 38470 G + 7471 B + 0x8000) >> 16
+ *   BRIGHTNESS      blend(0, v, f) on each byte
+ *   CONTRAST        blend(D, v, f) with D = int(sum / pixels + 0.5) in float64, sum the integer sum of L over the whole image as it is
+ *                   after the ops in front; at most one per image.  A launch of its own forms the sums (`sums`, m device words that
+ *                   the entry clears), the applying launch forms D: no host read between them
+ *   SATURATION      blend(L, v, f) on each byte, L of the same pixel
+ *   HUE             RGB -> HSV, H = (H + shift) mod 256, HSV -> RGB.  factor carries the shift, np.uint8(hue_factor * 255), as a whole
+ *                   number in [0, 255].  RGB -> HSV: V = max; S = int(255 * s), s = cr / max in float32, cr = max - min; the three
+ *                   quotients (max - c) / cr in float32, h = bc - gc, 2 + rc - bc or 4 + gc - rc (in float64, rounded to float32),
+ *                   h = fmod(h / 6 + 1, 1) in float64, rounded to float32, H = int(255 * h); grey has H = S = 0.  HSV -> RGB: S == 0
+ *                   gives grey; else h = H * 6 / 255, i = floor(h), f = h - i, s = S / 255, p, q, t = round(V (1 - s)),
+ *                   round(V (1 - s f)), round(V (1 - s (1 - f))) in float64, the six cases of colorsys by i mod 6
+ *   perm            output channel c is channel perm[c] of the result (identity: 0, 1, 2)
+ * Image i owns the blocks [first_block, first_block + mi355det_photo_blocks(pixels)), MI355DET_PHOTO_BLOCK_PIXELS pixels each.
+ * EINVAL, before any launch, for m <= 0, a null pointer, an image outside the packed bytes, n_ops outside [0, MAX_OPS], an op code out of
+ * range, a factor that is negative or not finite (a hue shift that is no whole number in [0, 255]), two contrast ops in one image, a
+ * perm that is no permutation, or a first_block column that is not the running sum of the block counts.
+ *
+ * ingest_aug_u8: mi355det_ingest_u8 with one other rule for fetching a tap (one tile loop serves both: csrc/ingest_body.h).  The
+ * resize sees a window [crop_h, crop_w] at (crop_top, crop_left) of a canvas [canvas_h, canvas_w] on which the source image is pasted at
+ * (paste_top, paste_left) and whose other pixels are `fill` (RandomZoomOut; without it the canvas is the image, pasted at 0, 0;
+ * RandomIoUCrop's window; without it the whole canvas).  A tap (y, x) of the window reads canvas pixel (crop_top + y, crop_left + x'),
+ * x' = crop_w - 1 - x where the image is flipped: three source bytes or the three fill bytes.  The canvas is never stored.  Sizes, scale
+ * and out_h / out_w are those of the window.  EINVAL, before any launch, for what ingest_u8 refuses and for a pasted image outside its
+ * canvas, a crop outside its canvas and a window with a zero side.  mi355det_flip_resize_boxes then takes a table of
+ * mi355det_ingest_image whose h, w are the windows'. */
+#define MI355DET_PHOTO_MAX_OPS 5
+#define MI355DET_PHOTO_BLOCK_PIXELS 4096
+#define MI355DET_PHOTO_BRIGHTNESS 1
+#define MI355DET_PHOTO_CONTRAST 2
+#define MI355DET_PHOTO_SATURATION 3
+#define MI355DET_PHOTO_HUE 4
+typedef struct {
+  int64_t offset;      /* byte offset of the image's [h, w, 3] bytes in the packed buffer */
+  int64_t pixels;      /* h * w */
+  int32_t first_block; /* index of the image's first block in the launch */
+  int32_t n_ops;
+  int32_t op[MI355DET_PHOTO_MAX_OPS];
+  float factor[MI355DET_PHOTO_MAX_OPS];
+  int32_t perm[3];
+  int32_t reserved;
+} mi355det_photo_image;
+typedef struct {
+  int64_t offset;                 /* byte offset of the source image's [h, w, 3] bytes in the packed buffer */
+  int32_t h, w;                   /* source size */
+  int32_t canvas_h, canvas_w;     /* the zoom-out canvas; h, w without one */
+  int32_t paste_top, paste_left;  /* where the source image lies on the canvas */
+  int32_t crop_top, crop_left;    /* the window of the canvas that the resize sees */
+  int32_t crop_h, crop_w;
+  int32_t out_h, out_w;           /* resized size of the window, <= the pad */
+  int32_t flip;                   /* != 0: the window is mirrored left to right */
+  int32_t first_tile;             /* index of the image's first tile in the launch */
+  uint32_t fill_rgb;              /* the canvas outside the pasted image: R | G << 8 | B << 16 */
+  int32_t reserved;
+} mi355det_ingest_aug_image;
+int32_t mi355det_photo_blocks(int64_t pixels);
+int mi355det_photometric_u8(uint8_t* packed, int64_t packed_bytes, const mi355det_photo_image* table,
+                            const mi355det_photo_image* table_dev, int32_t m, uint64_t* sums, void* stream);
+int mi355det_ingest_aug_u8(const uint8_t* packed, int64_t packed_bytes, const mi355det_ingest_aug_image* table,
+                           const mi355det_ingest_aug_image* table_dev, int32_t n, const float* mean, const float* stdv, float* out,
+                           int32_t pad_h, int32_t pad_w, void* stream);
+
 /* ---- YOLO ingest (csrc/cubic_kernels.hip): decoded uint8 images through OpenCV's bicubic resize to the square batch -----------
  * The YOLO twin of the uint8 ingest above: yolo/dsets/transformations.py:10-53 (ResizeToTensor = cv2.resize(img, (S, S), INTER_CUBIC),
  * / 255, normalise, boxes to relative xcycwh) for a whole batch, one launch for the images and one for the boxes.

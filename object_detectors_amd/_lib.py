@@ -63,6 +63,23 @@ class IngestImage(C.Structure):
     _fields_ = [("offset", i64), ("h", i32), ("w", i32), ("out_h", i32), ("out_w", i32), ("flip", i32), ("first_tile", i32)]
 
 
+PHOTO_MAX_OPS, PHOTO_BLOCK_PIXELS = 5, 4096
+PHOTO_OPS = {"brightness": 1, "contrast": 2, "saturation": 3, "hue": 4}
+
+
+class PhotoImage(C.Structure):
+    """mi355det_photo_image: the photometric ops of one image of a packed batch (mi355det_photometric_u8)."""
+    _fields_ = [("offset", i64), ("pixels", i64), ("first_block", i32), ("n_ops", i32), ("op", i32 * PHOTO_MAX_OPS),
+                ("factor", f32 * PHOTO_MAX_OPS), ("perm", i32 * 3), ("reserved", i32)]
+
+
+class IngestAugImage(C.Structure):
+    """mi355det_ingest_aug_image: one uint8 [h, w, 3] image of a packed batch seen through a window of its canvas (mi355det_ingest_aug_u8)."""
+    _fields_ = [("offset", i64), ("h", i32), ("w", i32), ("canvas_h", i32), ("canvas_w", i32), ("paste_top", i32), ("paste_left", i32),
+                ("crop_top", i32), ("crop_left", i32), ("crop_h", i32), ("crop_w", i32), ("out_h", i32), ("out_w", i32), ("flip", i32),
+                ("first_tile", i32), ("fill_rgb", C.c_uint32), ("reserved", i32)]
+
+
 YOLO_TILE_H, YOLO_TILE_W = 16, 64
 
 
@@ -197,6 +214,9 @@ PROTOTYPES = {
     "mi355det_ingest_tiles": (i32, [i32, i32]),
     "mi355det_ingest_u8": (C.c_int, [vp, i64, vp, vp, i32, vp, vp, vp, i32, i32, vp]),
     "mi355det_flip_resize_boxes": (C.c_int, [vp, vp, i64, vp, vp, i32, vp]),
+    "mi355det_photo_blocks": (i32, [i64]),
+    "mi355det_photometric_u8": (C.c_int, [vp, i64, vp, vp, i32, vp, vp]),
+    "mi355det_ingest_aug_u8": (C.c_int, [vp, i64, vp, vp, i32, vp, vp, vp, i32, i32, vp]),
     "mi355det_yolo_ingest_u8": (C.c_int, [vp, i64, vp, vp, i32, vp, i64, vp, vp, i32, vp]),
     "mi355det_yolo_targets": (C.c_int, [vp, vp, i64, vp, vp, i32, vp, vp, vp]),
     "mi355det_coco_rows": (C.c_int, [vp, i32, vp, vp, i32, i64, f32, f32, f32, i32, i32, vp, vp, vp, vp]),

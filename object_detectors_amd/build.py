@@ -26,6 +26,7 @@ SOURCES = [
     ("proposal_kernels.hip", ["-ffp-contract=off"]),
     ("frcnn_kernels.hip", ["-ffp-contract=off"]),
     ("transform_kernels.hip", ["-ffp-contract=off"]),
+    ("augment_kernels.hip", ["-ffp-contract=off"]),      # SSD augmentations: Pillow's byte rules in float32 / float64 as written: no twin
     ("cubic_kernels.hip", ["-ffp-contract=off"]),        # YOLO ingest: integer bicubic, float64 box quotients rounded once each: no twin
     ("mask_kernels.hip", ["-ffp-contract=off"]),
     ("rle_kernels.hip", ["-ffp-contract=off"]),          # shares the paste pixel rule with mask_kernels.hip (csrc/mask_paste.h): no twin

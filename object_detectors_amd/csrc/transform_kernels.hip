@@ -4,31 +4,11 @@
 // (the four taps of neighbouring outputs hit the same lines).  The uint8 route (mi355det_ingest_u8, mi355det_flip_resize_boxes) does the
 // same for a whole batch of decoded HWC images in one launch each, with the horizontal flip of detection/transforms.py:30-44 folded in.
 #include "common.h"
+#include "ingest_body.h"
 
 using namespace mi355;
 
 namespace {
-
-// One axis of ATen's upsample_bilinear2d (area_pixel_compute_source_index, align_corners = false):
-//   src = max(scale * (dst + 0.5) - 0.5, 0), i0 = (int)src, i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1
-struct Taps {
-  int i0, i1;
-  float l0, l1;
-};
-__device__ __forceinline__ Taps bilinear_taps(float scale, int dst, int in) {
-  const float s = fmaxf(scale * ((float)dst + 0.5f) - 0.5f, 0.0f);
-  Taps t;
-  t.i0 = (int)s;
-  t.i1 = t.i0 + (t.i0 < in - 1 ? 1 : 0);
-  t.l1 = s - (float)t.i0;
-  t.l0 = 1.0f - t.l1;
-  return t;
-}
-// The four-tap blend, for the float route (resize_bilinear_kernel) and the uint8 route (ingest_u8_kernel) alike:
-//   val = h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11)
-__device__ __forceinline__ float bilinear_blend(float v00, float v01, float v10, float v11, const Taps& ty, const Taps& tx) {
-  return ty.l0 * (tx.l0 * v00 + tx.l1 * v01) + ty.l1 * (tx.l0 * v10 + tx.l1 * v11);
-}
 
 // out[p][y][x] for planes p of one image (or of a same-size batch): bilinear sample of (in - mean[p % c]) / std[p % c], zero outside [oh, ow].
 __global__ __launch_bounds__(256) void resize_bilinear_kernel(const float* __restrict__ in, int planes, int c, int h, int w, const float* __restrict__ mean,
@@ -58,62 +38,25 @@ __global__ __launch_bounds__(256) void resize_bilinear_kernel(const float* __res
   }
 }
 
-// The same for a batch of uint8 HWC images of any sizes, packed back to back, in one launch (table: include/mi355det.h).  A block walks
-// tiles of TILE_H x TILE_W output pixels; a thread owns four neighbouring pixels of one row for all three channels, so each of its sixteen
-// taps is three neighbouring bytes and each plane's store is 16 bytes per lane (VEC: pw % 4 == 0 and out 16-byte aligned; else dwords).
-// The normalised value of a byte, ((float)b / 255.0f - mean) / std, has 256 values per channel: a block computes them once into LDS with
-// the two correctly rounded divisions of the float route and looks the taps up, instead of 24 divisions per pixel.  The bytes are plain
-// byte-indexed loads without an alignment assumption (rows are 3w bytes); the taps of neighbouring pixels share cache lines.
-constexpr int TILE_H = MI355DET_INGEST_TILE_H, TILE_W = MI355DET_INGEST_TILE_W;
-static_assert(TILE_H * (TILE_W / 4) == 256, "one thread per four pixels of a tile");
+// The same for a batch of uint8 HWC images of any sizes, packed back to back, in one launch: the tile loop of ingest_body.h with the plain
+// fetch rule.  A tap is a pixel of the image itself, column w - 1 - x where the image is flipped.
+struct PlainTap {
+  using Image = mi355det_ingest_image;
+  const uint8_t* packed;
+  const Image& im;
+  __device__ __forceinline__ PlainTap(const uint8_t* packed_, const Image& image) : packed(packed_), im(image) {}
+  __device__ __forceinline__ int h() const { return im.h; }
+  __device__ __forceinline__ int w() const { return im.w; }
+  __device__ __forceinline__ const uint8_t* row(int i) const { return packed + im.offset + (long long)i * im.w * 3; }
+  __device__ __forceinline__ int col(int i) const { return 3 * (im.flip ? im.w - 1 - i : i); }
+  __device__ __forceinline__ uint8_t byte(const uint8_t* r, int c0, int c) const { return r[c0 + c]; }
+};
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void ingest_u8_kernel(const uint8_t* __restrict__ packed, const mi355det_ingest_image* __restrict__ table, int n,
                                                         int tiles_x, int total_tiles, const float* __restrict__ mean,
                                                         const float* __restrict__ stdv, float* __restrict__ out, int ph, int pw) {
-  __shared__ float lut[3][256];
-  for (int e = threadIdx.x; e < 3 * 256; e += 256) lut[e >> 8][e & 255] = ((float)(e & 255) / 255.0f - mean[e >> 8]) / stdv[e >> 8];
-  __syncthreads();
-  const int lx = (threadIdx.x % (TILE_W / 4)) * 4, ly = threadIdx.x / (TILE_W / 4);
-  const long long plane = (long long)ph * pw;
-  for (int tile = blockIdx.x; tile < total_tiles; tile += gridDim.x) {
-    int lo = 0, hi = n - 1;                                  // block-uniform: the last image whose first tile is <= tile
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (table[mid].first_tile <= tile) lo = mid; else hi = mid - 1;
-    }
-    const mi355det_ingest_image im = table[lo];
-    const int t = tile - im.first_tile;
-    const int y = (t / tiles_x) * TILE_H + ly, x = (t % tiles_x) * TILE_W + lx;
-    if (y >= ph || x >= pw) continue;
-    float v[3][4] = {};
-    if (y < im.out_h && x < im.out_w) {
-      const float rh = (float)im.h / (float)im.out_h, rw = (float)im.w / (float)im.out_w;
-      const Taps ty = bilinear_taps(rh, y, im.h);
-      const uint8_t* r0 = packed + im.offset + (long long)ty.i0 * im.w * 3;
-      const uint8_t* r1 = packed + im.offset + (long long)ty.i1 * im.w * 3;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (x + j >= im.out_w) continue;
-        const Taps tx = bilinear_taps(rw, x + j, im.w);
-        const int c0 = 3 * (im.flip ? im.w - 1 - tx.i0 : tx.i0), c1 = 3 * (im.flip ? im.w - 1 - tx.i1 : tx.i1);
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-          v[c][j] = bilinear_blend(lut[c][r0[c0 + c]], lut[c][r0[c1 + c]], lut[c][r1[c0 + c]], lut[c][r1[c1 + c]], ty, tx);
-      }
-    }
-    float* o = out + ((long long)lo * 3 * ph + y) * pw + x;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      if (VEC) {
-        *(float4*)(o + c * plane) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (x + j < pw) o[c * plane + j] = v[c][j];
-      }
-    }
-  }
+  ingest_tiles<VEC, PlainTap>(packed, table, n, tiles_x, total_tiles, mean, stdv, out, ph, pw);
 }
 
 __global__ void resize_boxes_kernel(const float* __restrict__ boxes, float* __restrict__ out, long long n, float ratio_h, float ratio_w) {

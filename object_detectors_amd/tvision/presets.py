@@ -15,8 +15,9 @@ import torch
 class DetectionPresetTrain:
     def __init__(self, data_augmentation="hflip", hflip_prob=0.5):
         if data_augmentation in ("ssd", "ssdlite"):
-            raise NotImplementedError(f'data augmentation policy "{data_augmentation}": there is no SSD on this path (zoom-out, IoU crop and '
-                                      "photometric distortion have no kernels here)")
+            raise NotImplementedError(f'data augmentation policy "{data_augmentation}": the SSD augmentations need the shapes and the targets, '
+                                      "which a preset's draw(n) does not see: use transforms.SSDAugmentation(policy).draw(shapes, targets) "
+                                      "and ingest(images, targets, augment=params)")
         if data_augmentation != "hflip":
             raise ValueError(f'Unknown data augmentation policy "{data_augmentation}"')
         self.hflip_prob = hflip_prob

@@ -15,7 +15,13 @@ output SIZES are identical.
 
 is the second route: the horizontal flip of the training preset (tvision/presets.py), ToTensor's / 255, normalise, resize and pad of the
 WHOLE batch in one launch (mi355det_ingest_u8), all boxes in one more (mi355det_flip_resize_boxes); the same bits as `forward` on the
-flipped float images.  `plan_ingest` is its host-side size and layout planning."""
+flipped float images.  `plan_ingest` is its host-side size and layout planning.
+
+    params, targets = transforms.SSDAugmentation("ssd").draw(shapes, targets)
+    image_list, targets = transform.ingest(images, targets, augment=params)
+
+adds the reference's `ssd` / `ssdlite` policies (tvision/transforms.py): photometric distortion on the packed bytes
+(mi355det_photometric_u8), zoom-out, IoU crop and flip inside the image launch (mi355det_ingest_aug_u8)."""
 import collections
 import ctypes
 import math
@@ -23,7 +29,8 @@ import math
 import numpy as np
 import torch
 
-from .._lib import INGEST_TILE_H, INGEST_TILE_W, IngestImage, check, lib, ptr, stream_ptr
+from .._lib import (INGEST_TILE_H, INGEST_TILE_W, PHOTO_BLOCK_PIXELS, PHOTO_MAX_OPS, PHOTO_OPS, IngestAugImage, IngestImage, PhotoImage, check, lib,
+                    ptr, stream_ptr)
 
 
 class ImageList:
@@ -107,11 +114,17 @@ def plan_ingest(shapes, min_size, max_size, size_divisible=32, fixed_size=None):
         sizes = [resized_size(int(h), int(w), float(mn), float(max_size)) for (h, w), mn in zip(shapes, mins)]
     ph, pw = padded_size(sizes, size_divisible)
     per_image = -(-ph // INGEST_TILE_H) * -(-pw // INGEST_TILE_W)
+    offsets, total = _packed_layout(shapes)
+    return IngestPlan(sizes, (ph, pw), offsets, total, [i * per_image for i in range(n)], n * per_image)
+
+
+def _packed_layout(shapes):
+    """Byte offset of every [H, W, 3] image in the packed buffer, and their total."""
     offsets, total = [], 0
     for h, w in shapes:
         offsets.append(total)
         total += 3 * int(h) * int(w)
-    return IngestPlan(sizes, (ph, pw), offsets, total, [i * per_image for i in range(n)], n * per_image)
+    return offsets, total
 
 
 def _checked_ingest_arguments(images, targets, flips):
@@ -143,6 +156,60 @@ def _checked_ingest_arguments(images, targets, flips):
             if "masks" in t and (t["masks"].dim() != 3 or tuple(t["masks"].shape[-2:]) != tuple(img.shape[:2])):
                 raise ValueError("ingest: masks of shape {} for an image of {}".format(tuple(t["masks"].shape), tuple(img.shape[:2])))
     return images, targets, flips
+
+
+def _augment_tables(augment, shapes, targets):
+    """The refusals and the tables of `ingest(augment=...)`, on the host and ahead of any launch.  augment: one record per image with the
+    fields of `transforms.AugmentParams`.  Returns the windows [(h, w)] (the images the resize sees), the mi355det_ingest_aug_image table
+    without its offset, out_h / out_w and first_tile columns, and the mi355det_photo_image table of the images that have ops (offsets and
+    blocks from the packed layout of `shapes`)."""
+    n = len(shapes)
+    augment = list(augment)
+    if len(augment) != n:
+        raise ValueError(f"ingest: {len(augment)} augment records for {n} images")
+    if targets is not None and any("masks" in t for t in targets):
+        raise ValueError("ingest: targets with masks are not supported together with augment (the reference's IoU crop does not touch them)")
+    windows, table, photo, offset, block = [], (IngestAugImage * n)(), [], 0, 0
+    for i, (p, (h, w)) in enumerate(zip(augment, shapes)):
+        canvas_h, canvas_w, left, top, fill = p.zoom if p.zoom is not None else (h, w, 0, 0, (0, 0, 0))
+        if left < 0 or top < 0 or top + h > canvas_h or left + w > canvas_w:
+            raise ValueError(f"ingest: image {i}: the zoom-out canvas {canvas_h} x {canvas_w} does not hold the {h} x {w} image at ({top}, {left})")
+        if len(fill) != 3 or any(int(f) != f or not 0 <= f <= 255 for f in fill):
+            raise ValueError(f"ingest: image {i}: the fill is three bytes, got {fill}")
+        crop_left, crop_top, crop_w, crop_h = p.crop if p.crop is not None else (0, 0, canvas_w, canvas_h)
+        if crop_w < 1 or crop_h < 1 or crop_left < 0 or crop_top < 0 or crop_top + crop_h > canvas_h or crop_left + crop_w > canvas_w:
+            raise ValueError(f"ingest: image {i}: the crop {p.crop} is empty or lies outside its {canvas_h} x {canvas_w} canvas")
+        windows.append((int(crop_h), int(crop_w)))
+        table[i] = IngestAugImage(0, h, w, canvas_h, canvas_w, top, left, crop_top, crop_left, crop_h, crop_w, 0, 0, int(bool(p.flip)), 0,
+                                  int(fill[0]) | int(fill[1]) << 8 | int(fill[2]) << 16, 0)
+        ops, perm = tuple(p.ops), (0, 1, 2) if p.permutation is None else tuple(int(c) for c in p.permutation)
+        if sorted(perm) != [0, 1, 2]:
+            raise ValueError(f"ingest: image {i}: {p.permutation} is no permutation of the three channels")
+        if len(ops) > PHOTO_MAX_OPS or sum(name == "contrast" for name, _f in ops) > 1:
+            raise ValueError(f"ingest: image {i}: at most {PHOTO_MAX_OPS} photometric ops, one contrast among them")
+        if ops or perm != (0, 1, 2):
+            codes, factors = [], []
+            for name, f in ops:
+                if name not in PHOTO_OPS:
+                    raise ValueError(f'ingest: image {i}: unknown photometric op "{name}"')
+                if name == "hue":
+                    if not -0.5 <= f <= 0.5:
+                        raise ValueError(f"ingest: image {i}: hue factor {f} is not in [-0.5, 0.5]")
+                    f = int(float(f) * 255) & 255        # adjust_hue's np.uint8(hue_factor * 255), which H is shifted by modulo 256
+                elif not 0 <= f < math.inf:
+                    raise ValueError(f"ingest: image {i}: {name} factor {f} is negative or not finite")
+                codes.append(PHOTO_OPS[name])
+                factors.append(float(f))
+            pad = PHOTO_MAX_OPS - len(ops)
+            photo.append(PhotoImage(offset, h * w, block, len(ops), (ctypes.c_int32 * PHOTO_MAX_OPS)(*codes, *[0] * pad),
+                                    (ctypes.c_float * PHOTO_MAX_OPS)(*factors, *[0.0] * pad), (ctypes.c_int32 * 3)(*perm), 0))
+            block += -(-h * w // PHOTO_BLOCK_PIXELS)
+        offset += 3 * h * w
+    if targets is not None:
+        for i, (t, (wh, ww)) in enumerate(zip(targets, windows)):
+            if "boxes" in t and t["boxes"].numel() and (float(t["boxes"][:, 0::2].max()) > ww or float(t["boxes"][:, 1::2].max()) > wh):
+                raise ValueError(f"ingest: image {i}: boxes outside the {wh} x {ww} window: with augment, the targets are those `draw` returned")
+    return windows, table, (PhotoImage * len(photo))(*photo)
 
 
 class _Staging:
@@ -220,47 +287,68 @@ class GeneralizedRCNNTransform(torch.nn.Module):
                 targets[i]["masks"] = mask_resize_nearest(targets[i]["masks"], (oh, ow))
         return ImageList(batch, sizes), targets
 
-    def ingest(self, images, targets=None, flips=None, device=None):
+    def ingest(self, images, targets=None, flips=None, device=None, augment=None):
         """The route for images as a decoder hands them over: a list of uint8 [H, W, 3] tensors (or numpy arrays) of any sizes, all on the
         CPU or all on one device, and one horizontal-flip flag per image (detection/transforms.py:30-44; `presets.DetectionPresetTrain.draw`).
         Returns what `forward` returns for the flipped float images `img.permute(2, 0, 1).float().div(255)` and their flipped targets, bit
         for bit, from one image launch (mi355det_ingest_u8) and one box launch (mi355det_flip_resize_boxes) per batch; the ImageList
         carries `original_image_sizes`.  CPU images are packed into a pinned buffer and go up in one copy (to `device`, default the current
-        one).  Targets are copied: `boxes` and `masks` are transformed, other keys pass through, `keypoints` are refused."""
+        one).  Targets are copied: `boxes` and `masks` are transformed, other keys pass through, `keypoints` are refused.
+
+        augment: the records of `transforms.SSDAugmentation.draw`, one per image, with the targets that `draw` returned and `flips` None
+        (the flip is in the records).  The photometric ops run on the packed bytes (mi355det_photometric_u8), zoom-out, crop and flip
+        inside the image launch (mi355det_ingest_aug_u8), the boxes as before with the window's width: the same bits as `forward` on the
+        images that the reference's PIL transforms give.  Sizes and `original_image_sizes` are the windows': the images the model sees."""
+        if augment is not None and flips is not None:
+            raise ValueError("ingest: with augment the flips are in its records, flips must be None")
         images, targets, flips = _checked_ingest_arguments(images, targets, flips)
         n = len(images)
         src_dev = images[0].device
         shapes = [(int(img.shape[0]), int(img.shape[1])) for img in images]
+        windows, aug_table, photo_table = shapes, None, None
+        if augment is not None:
+            windows, aug_table, photo_table = _augment_tables(augment, shapes, targets)
+            flips = [bool(p.flip) for p in augment]
         if self.fixed_size is None and self.training:
             mins = [float(self.torch_choice(self.min_size)) for _ in images]       # one draw per image, in order, as `forward`
         else:
             mins = float(self.min_size[-1])
-        plan = plan_ingest(shapes, mins, float(self.max_size), self.size_divisible, self.fixed_size)
+        plan = plan_ingest(windows, mins, float(self.max_size), self.size_divisible, self.fixed_size)
+        offsets, nbytes = (plan.offsets, plan.nbytes) if augment is None else _packed_layout(shapes)      # the sources', not the windows'
         if src_dev.type != "cpu":
             dev = src_dev
         else:
             dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
 
-        table = (IngestImage * n)()
-        for i, ((h, w), (oh, ow)) in enumerate(zip(shapes, plan.sizes)):
-            table[i] = IngestImage(plan.offsets[i], h, w, oh, ow, int(flips[i]), plan.first_tile[i])
+        table = (IngestImage * n)()              # of the windows: the whole images without augment
+        for i, ((h, w), (oh, ow)) in enumerate(zip(windows, plan.sizes)):
+            table[i] = IngestImage(offsets[i], h, w, oh, ow, int(flips[i]), plan.first_tile[i])
+            if augment is not None:
+                aug_table[i].offset, aug_table[i].out_h, aug_table[i].out_w, aug_table[i].first_tile = offsets[i], oh, ow, plan.first_tile[i]
         with_boxes = [i for i in range(n) if targets is not None and "boxes" in targets[i]]
         box_offsets = np.zeros(n + 1, dtype=np.int64)
         for i in with_boxes:
             box_offsets[i + 1] = targets[i]["boxes"].shape[0]
         np.cumsum(box_offsets, out=box_offsets)
         ntable = ctypes.sizeof(table)
-        nmeta = ntable + box_offsets.nbytes
+        naug = nmeta = ntable + box_offsets.nbytes               # the augment tables follow: every size is a multiple of 8
+        if augment is not None:
+            nphoto = naug + ctypes.sizeof(aug_table)
+            nmeta = nphoto + ctypes.sizeof(photo_table)
         with torch.cuda.device(dev):
             stage = self._staging.setdefault(dev, _Staging())
-            pixels, meta = stage.acquire(plan.nbytes if src_dev.type == "cpu" else 0, nmeta)
+            pixels, meta = stage.acquire(nbytes if src_dev.type == "cpu" else 0, nmeta)
             meta[:ntable].copy_(torch.from_numpy(np.frombuffer(table, dtype=np.uint8)))
-            meta[ntable:nmeta].copy_(torch.from_numpy(box_offsets.view(np.uint8)))
+            meta[ntable:naug].copy_(torch.from_numpy(box_offsets.view(np.uint8)))
+            if augment is not None:
+                meta[naug:nphoto].copy_(torch.from_numpy(np.frombuffer(aug_table, dtype=np.uint8)))
+                if len(photo_table):
+                    meta[nphoto:nmeta].copy_(torch.from_numpy(np.frombuffer(photo_table, dtype=np.uint8)))
             if src_dev.type == "cpu":
-                for img, off, (h, w) in zip(images, plan.offsets, shapes):
+                for img, off, (h, w) in zip(images, offsets, shapes):
                     pixels[off:off + 3 * h * w].view(h, w, 3).copy_(img)
-                packed = torch.empty(plan.nbytes, dtype=torch.uint8, device=dev)
-                packed.copy_(pixels[:plan.nbytes], non_blocking=True)
+                packed = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                packed.copy_(pixels[:nbytes], non_blocking=True)
             else:
                 packed = torch.cat([img.reshape(-1) for img in images])
             meta_dev = torch.empty(nmeta, dtype=torch.uint8, device=dev)
@@ -271,8 +359,18 @@ class GeneralizedRCNNTransform(torch.nn.Module):
             ph, pw = plan.pad
             batch = torch.empty((n, 3, ph, pw), dtype=torch.float32, device=dev)
             L = lib()
-            check(L.mi355det_ingest_u8(ptr(packed), plan.nbytes, ctypes.cast(table, ctypes.c_void_p), table_dev, n, ptr(mean), ptr(std), ptr(batch),
-                                       ph, pw, stream_ptr()), "ingest_u8")
+            if augment is None:
+                check(L.mi355det_ingest_u8(ptr(packed), nbytes, ctypes.cast(table, ctypes.c_void_p), table_dev, n, ptr(mean), ptr(std), ptr(batch),
+                                           ph, pw, stream_ptr()), "ingest_u8")
+            else:
+                if len(photo_table):
+                    sums = torch.empty(len(photo_table), dtype=torch.int64, device=dev)
+                    check(L.mi355det_photometric_u8(ptr(packed), nbytes, ctypes.cast(photo_table, ctypes.c_void_p),
+                                                    ctypes.c_void_p(meta_dev.data_ptr() + nphoto), len(photo_table), ptr(sums),
+                                                    stream_ptr()), "photometric_u8")
+                check(L.mi355det_ingest_aug_u8(ptr(packed), nbytes, ctypes.cast(aug_table, ctypes.c_void_p),
+                                               ctypes.c_void_p(meta_dev.data_ptr() + naug), n, ptr(mean), ptr(std), ptr(batch), ph, pw,
+                                               stream_ptr()), "ingest_aug_u8")
             if with_boxes:
                 boxes = [targets[i]["boxes"].to(torch.float32) for i in with_boxes]
                 if any(b.device != boxes[0].device for b in boxes):
@@ -288,7 +386,7 @@ class GeneralizedRCNNTransform(torch.nn.Module):
                 for i, t in enumerate(targets):
                     if "masks" in t:
                         t["masks"] = _resize(t["masks"].to(dev), plan.sizes[i], flip=flips[i])
-        return ImageList(batch, plan.sizes, shapes), targets
+        return ImageList(batch, plan.sizes, windows), targets
 
     def postprocess(self, result, image_shapes, original_image_sizes, mask_format="dense"):
         """transform.py:228-247 (boxes, and masks when the result has them; no keypoint branch on this path).  mask_format "dense" is the
