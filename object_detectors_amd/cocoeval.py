@@ -25,7 +25,7 @@ import torch
 from . import ops
 from .evalcore import (MASK_TYPES, REC_THRS, GroupedEval, bootstrap_cells, category_order, cell_mean, check_weights, group_offsets,  # noqa: F401 (re-exported)
                        image_indices, load_dataset, lookup, masked_mean, rank_in_run, rle_operands, score_then_key_order, sort_ground_truth)
-from .polygons import is_polygon_segmentation
+from .polygons import PolygonRLE, is_polygon_segmentation
 from .rle import RLEBatch, boundary_dilation, boundary_dilations, counts_stats, pack_strings, string_to_counts
 
 MAX_DETS = [1, 10, 100]
@@ -113,8 +113,12 @@ class _MaskStore:
         self.add_arrays(counts, np.diff(runs), area, bbox, sizes)
 
     def add_batch(self, b):
-        area, bbox = b.stats()
-        self.add_arrays(b.counts, np.diff(np.asarray(b.offsets, np.int64)), area, bbox, [b.size] * len(b))
+        """An RLEBatch (one size for all its masks) or a polygons.PolygonRLE (a size per mask)."""
+        one_size = isinstance(b, RLEBatch)
+        if not one_size and not isinstance(b, PolygonRLE):
+            raise TypeError(f"COCOEval: masks must be an RLEBatch or a PolygonRLE, not {type(b).__name__}")
+        area, bbox = b.stats() if one_size else (b.area, b.bbox)
+        self.add_arrays(b.counts, np.diff(np.asarray(b.offsets, np.int64)), area, bbox, [b.size] * len(b) if one_size else b.sizes)
 
     def add_segmentations(self, segs):
         """Segmentations in any accepted form, in order.  On a GPU, a list of nothing but `counts` strings goes through the string kernels
@@ -141,39 +145,34 @@ class _MaskStore:
             if int(c.astype(np.int64).sum()) != size[0] * size[1] or (c < 0).any():
                 raise ValueError(f"COCOEval: run lengths that do not add up to {size[0]}x{size[1]}")
             counts.append(c)
-        groups = {}
-        for j, (size, _c) in enumerate(parsed):
-            groups.setdefault(size, []).append(j)
         flat = np.concatenate(counts) if counts else np.zeros(0, np.int32)
-        area, bbox = np.zeros(len(parsed), np.int64), np.zeros((len(parsed), 4), np.int32)
-        for size, idx in groups.items():                       # the tight boxes need the column height
-            sub_off = [0]
-            for j in idx:
-                sub_off.append(sub_off[-1] + len(counts[j]))
-            sub = np.concatenate([counts[j] for j in idx])
-            area[idx], bbox[idx] = counts_stats(sub, sub_off, size[0])
-        self.add_arrays(torch.from_numpy(np.ascontiguousarray(flat, np.int32)), [len(c) for c in counts], torch.from_numpy(area),
-                        torch.from_numpy(bbox), [size for size, _c in parsed])
+        lens = [len(c) for c in counts]
+        sizes = [size for size, _c in parsed]
+        area, bbox = counts_stats(flat, np.concatenate([[0], np.cumsum(lens, dtype=np.int64)]), [size[0] for size in sizes])
+        self.add_arrays(torch.from_numpy(np.ascontiguousarray(flat, np.int32)), lens, torch.from_numpy(area), torch.from_numpy(bbox), sizes)
+
+    def _cat(self, area=True):
+        """The five lists as one entry each: counts int32, area int64 [n] (None unless asked for), bbox int32 [n, 4] on the device; runs
+        int64 [n + 1] and sizes int32 [n, 2] on the host."""
+        cat = lambda xs, dt, shape: torch.cat(xs) if xs else torch.zeros(shape, dtype=dt, device=self.dev)
+        lens = np.concatenate(self.lens) if self.lens else np.zeros(0, np.int64)
+        return (cat(self.counts, torch.int32, (0,)).contiguous(), np.concatenate([np.zeros(1, np.int64), np.cumsum(lens)]),
+                cat(self.area, torch.int64, (0,)) if area else None, cat(self.bbox, torch.int32, (0, 4)),
+                np.concatenate(self.sizes) if self.sizes else np.zeros((0, 2), np.int32))
+
+    def _operands(self, counts, runs, area, bbox, sizes):
+        return counts, torch.from_numpy(runs).to(self.dev), area.to(torch.float64), bbox.to(torch.float64).contiguous(), sizes
 
     def boundaries(self, dilation_ratio, budget_bytes=1 << 30):
         """tensors() of the masks' boundaries (ops.rle_boundary, each mask eroded by rle.boundary_dilation of its own size): one conversion
         of the whole store, one host read of the boxes and one of the run offsets."""
-        cat = lambda xs, dt, shape: torch.cat(xs) if xs else torch.zeros(shape, dtype=dt, device=self.dev)
-        lens = np.concatenate(self.lens) if self.lens else np.zeros(0, np.int64)
-        sizes = np.concatenate(self.sizes) if self.sizes else np.zeros((0, 2), np.int32)
-        counts, runs, area, bbox = ops.rle_boundary(cat(self.counts, torch.int32, (0,)).contiguous(), np.concatenate([[0], np.cumsum(lens)]),
-                                                    sizes, boundary_dilations(sizes, dilation_ratio), cat(self.bbox, torch.int32, (0, 4)),
-                                                    budget_bytes=budget_bytes)
-        return counts, torch.from_numpy(runs).to(self.dev), area.to(torch.float64), bbox.to(torch.float64).contiguous(), sizes
+        counts, runs, _area, bbox, sizes = self._cat(area=False)
+        return self._operands(*ops.rle_boundary(counts, runs, sizes, boundary_dilations(sizes, dilation_ratio), bbox, budget_bytes=budget_bytes),
+                              sizes)
 
     def tensors(self):
         """counts int32, runs int64 [n + 1], area float64 [n], tight boxes float64 [n, 4] on the device; sizes int32 [n, 2] on the host."""
-        cat = lambda xs, dt, shape: torch.cat(xs) if xs else torch.zeros(shape, dtype=dt, device=self.dev)
-        lens = np.concatenate(self.lens) if self.lens else np.zeros(0, np.int64)
-        runs = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)).to(self.dev)
-        return (cat(self.counts, torch.int32, (0,)).contiguous(), runs, cat(self.area, torch.int64, (0,)).to(torch.float64),
-                cat(self.bbox, torch.int32, (0, 4)).to(torch.float64).contiguous(),
-                np.concatenate(self.sizes) if self.sizes else np.zeros((0, 2), np.int32))
+        return self._operands(*self._cat())
 
 
 class COCOEval(GroupedEval):

@@ -24,7 +24,7 @@
 // run offsets once.  Small boxes (at most SMALL_WORDS words a plane) get a block of one wavefront, the others 256 threads: two launches over
 // the same chunk, each block leaving at once if its mask is of the other class.
 // Integers only, no atomics, one writer per element, 64-bit offsets: the same bits every run.
-#include "common.h"
+#include "rle_protocol.h"
 
 #include <limits.h>
 
@@ -448,10 +448,8 @@ int mi355det_rle_boundary_emit(const int32_t* counts, int64_t num_counts, const 
                              index_dev, geom, geom_dev, (const long long*)slices, slices_dev, n, first, num, workspace, workspace_bytes, &ch);
   if (st != MI355DET_OK) return st;
   if (num == 0) return MI355DET_OK;
-  if (total_runs < n) return fail(MI355DET_EINVAL, "%s: total_runs %lld is below one count per mask", "rle_boundary_emit", total_runs);
-  if (capacity < total_runs)
-    return fail(MI355DET_EINVAL, "%s: capacity %lld is smaller than the %lld counts", "rle_boundary_emit", capacity, total_runs);
-  if (!run_offsets || !out_counts) return fail(MI355DET_EINVAL, "%s: missing operand", "rle_boundary_emit");
+  const int ce = check_emit("rle_boundary_emit", "%s: total_runs %lld is below one count per mask", n, total_runs, capacity, run_offsets, out_counts);
+  if (ce != MI355DET_OK) return ce;
   Args A{counts, (const long long*)runs_dev, (const long long*)index_dev, geom_dev, (const long long*)slices_dev, first, (char*)workspace,
          nullptr, (const long long*)run_offsets, out_counts, (long long)capacity, (long long*)area, bbox};
   launch<true>(A, num, ch, stream);

@@ -16,7 +16,7 @@
 //                           the running maximum of the precision and lets every detection that raises the recall write the recall thresholds
 //                           it is the first to reach.  No workspace.
 // Compiled with -ffp-contract=off: every quotient and product has to be the one correctly rounded float64 operation of the definition.
-#include "common.h"
+#include "wave_ops.h"
 
 using namespace mi355;
 
@@ -179,24 +179,6 @@ __global__ __launch_bounds__(WAVE) void coco_match_kernel(Groups S, const double
     }
     di[d] = ig;
   }
-}
-
-__device__ __forceinline__ int wave_scan_incl(int x, int lane) {
-#pragma unroll
-  for (int o = 1; o < WAVE; o <<= 1) {
-    const int y = __shfl_up(x, o, WAVE);
-    if (lane >= o) x += y;
-  }
-  return x;
-}
-
-__device__ __forceinline__ long long wave_sum_i64(long long x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned lo = __shfl_xor((unsigned)x, o, WAVE), hi = __shfl_xor((unsigned)((unsigned long long)x >> 32), o, WAVE);
-    x += (long long)(((unsigned long long)hi << 32) | lo);
-  }
-  return x;
 }
 
 struct MaxDets {

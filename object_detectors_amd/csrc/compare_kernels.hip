@@ -9,7 +9,7 @@
 // float64 throughout, no atomics, one writer per output element, 64-bit offsets, no cap on either count of an image short of
 // best_index being int32.
 // Compiled with -ffp-contract=off: the sums, the products and the quotient have to be the correctly rounded float64 operations of the rule.
-#include "common.h"
+#include "wave_ops.h"
 
 using namespace mi355;
 
@@ -29,11 +29,6 @@ __device__ __forceinline__ bool takes_over(const Best& a, const Best& b) {
   const bool an = a.v != a.v, bn = b.v != b.v;
   if (an || bn) return bn && (!an || b.i < a.i);
   return b.v > a.v || (b.v == a.v && b.i < a.i);
-}
-
-__device__ __forceinline__ long long shfl_xor_i64(long long x, int o) {
-  const unsigned lo = __shfl_xor((unsigned)x, o, WAVE), hi = __shfl_xor((unsigned)((unsigned long long)x >> 32), o, WAVE);
-  return (long long)(((unsigned long long)hi << 32) | lo);
 }
 
 struct DtSide {

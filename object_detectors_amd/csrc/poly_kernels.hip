@@ -16,10 +16,11 @@
 //   poly_runs_kernel    one wavefront per annotation.  One part: the state after a position is the parity of the points up to it.  More
 //                       parts: the state is "coverage > 0" after all events of a position.  A run boundary is a position where the state
 //                       changes; the emit pass writes the gaps, the area (sum of the odd-indexed counts) and the tight box (toBbox).
-//   scan_kernel         one block: per-item counts -> exclusive offsets, in place.
+//   offsets scan        one block (offsets_scan.h): per-item counts -> exclusive offsets, in place.
 //   rle_decode_kernel   one wavefront per mask: scans the counts 64 at a time, the wavefront writes each run of ones over a zeroed output.
 // All floating point is float64 and this file is compiled with -ffp-contract=off: ys + s*t + .5 must round twice, as the C of pycocotools does.
-#include "common.h"
+#include "offsets_scan.h"
+#include "rle_protocol.h"
 
 #include <limits.h>
 
@@ -32,15 +33,6 @@ typedef unsigned long long u64;
 constexpr long long EVENT_NONE = LLONG_MAX;               // fills the unused tail of a polygon's event slots; sorts behind every event
 
 __device__ __forceinline__ int top_bit(u64 m) { return 63 - __clzll((long long)m); }
-
-__device__ __forceinline__ int wave_scan_incl(int v, int lane) {
-#pragma unroll
-  for (int o = 1; o < WAVE; o <<= 1) {
-    const int t = __shfl_up(v, o, WAVE);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
 
 // the annotation that owns polygon p: the largest a with ann_off[a] <= p (annotations without parts repeat an offset)
 __device__ __forceinline__ int owner(const long long* __restrict__ ann_off, int A, long long p) {
@@ -130,29 +122,6 @@ __global__ __launch_bounds__(256) void poly_points_kernel(const double* __restri
     }
   }
   if (!EMIT && lane == 0) pt_off[p] = n;
-}
-
-// off[0..n) holds counts; afterwards off[d] = the sum of the counts before d and off[n] = their total
-__global__ __launch_bounds__(256) void scan_kernel(long long n, long long* __restrict__ off) {
-  __shared__ long long s[256];
-  const int t = threadIdx.x;
-  long long carry = 0;
-  for (long long base = 0; base < n; base += 256) {
-    const long long d = base + t;
-    const long long v = d < n ? off[d] : 0;
-    s[t] = v;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-      const long long a = t >= o ? s[t - o] : 0;
-      __syncthreads();
-      s[t] += a;
-      __syncthreads();
-    }
-    if (d < n) off[d] = carry + s[t] - v;
-    carry += s[255];
-    __syncthreads();
-  }
-  if (t == 0) off[n] = carry;
 }
 
 // ---- the two sorted streams a wavefront walks.  get(i): position and coverage weight of element i; state(cov): the bit after cov.
@@ -282,14 +251,11 @@ __global__ __launch_bounds__(256) void poly_runs_kernel(const long long* __restr
     if (first + T < limit) counts[first + T] = hw - carry_pos;
     if (T & 1) st.add(carry_pos, hw - 1, h);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {                      // integer sums, minima and maxima: order-free, so exact
-    st.area += __shfl_xor(st.area, o, WAVE);
-    st.xmin = min(st.xmin, __shfl_xor(st.xmin, o, WAVE));
-    st.xmax = max(st.xmax, __shfl_xor(st.xmax, o, WAVE));
-    st.ymin = min(st.ymin, __shfl_xor(st.ymin, o, WAVE));
-    st.ymax = max(st.ymax, __shfl_xor(st.ymax, o, WAVE));
-  }
+  st.area = wave_sum_i64(st.area);                        // integer sums, minima and maxima: order-free, so exact
+  st.xmin = wave_min_i(st.xmin);
+  st.xmax = wave_max_i(st.xmax);
+  st.ymin = wave_min_i(st.ymin);
+  st.ymax = wave_max_i(st.ymax);
   const bool whole = __ballot(st.whole) != 0;
   if (lane == 0) {
     if (area) area[a] = st.area;
@@ -317,13 +283,7 @@ __global__ __launch_bounds__(256) void rle_decode_kernel(const int* __restrict__
   for (long long c = s; c < e && carry < hw; c += WAVE) {
     const long long i = c + lane;
     const int n = i < e ? min(max(counts[i], 0), hw) : 0;
-    long long end = n;                                    // inclusive scan in int64: 64 counts of up to hw each
-#pragma unroll
-    for (int k = 1; k < WAVE; k <<= 1) {
-      const long long t = __shfl_up(end, k, WAVE);
-      if (lane >= k) end += t;
-    }
-    end += carry;
+    const long long end = carry + wave_scan_incl((long long)n, lane);       // in int64: 64 counts of up to hw each
     const int stop = (int)min(end, (long long)hw), start = (int)min(end - n, (long long)hw);
     const bool ones = i < e && ((i - s) & 1) && stop > start;
     u64 m = __ballot(ones);
@@ -362,7 +322,7 @@ int mi355det_poly_points_count(const double* xy, const int64_t* poly_offsets, co
   if (!xy || !point_offsets) return fail(MI355DET_EINVAL, "%s: missing operand", "poly_points_count");
   hipLaunchKernelGGL(poly_points_kernel<false>, dim3(waves4(num_polys)), dim3(256), 0, S(stream), xy, (const long long*)poly_offsets,
                      (const long long*)ann_offsets, sizes, num_polys, num_anns, (long long*)point_offsets, (long long*)nullptr, 0ll);
-  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(256), 0, S(stream), (long long)num_polys, (long long*)point_offsets);
+  launch_offsets_scan(num_polys, ScanInPlace{(const long long*)point_offsets}, (long long*)point_offsets, stream);
   return check_launch("poly_points_count");
 }
 
@@ -393,7 +353,7 @@ int mi355det_poly_events(const int64_t* keys, const int64_t* point_offsets, cons
   hipLaunchKernelGGL(poly_events_kernel, dim3(waves4(num_polys)), dim3(256), 0, S(stream), (const long long*)keys,
                      (const long long*)point_offsets, (const long long*)ann_offsets, sizes, (const long long*)event_base, num_polys, num_anns,
                      (long long*)events, (long long)capacity, (long long*)toggle_offsets);
-  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(256), 0, S(stream), (long long)num_polys, (long long*)toggle_offsets);
+  launch_offsets_scan(num_polys, ScanInPlace{(const long long*)toggle_offsets}, (long long*)toggle_offsets, stream);
   return check_launch("poly_events");
 }
 
@@ -408,7 +368,7 @@ int mi355det_poly_runs_count(const int64_t* keys, const int64_t* point_offsets, 
                      (const long long*)point_offsets, (const long long*)events, (const long long*)toggle_offsets,
                      (const long long*)ann_offsets, sizes, num_anns, (long long*)run_offsets, (int*)nullptr, 0ll, (long long*)nullptr,
                      (int*)nullptr);
-  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(256), 0, S(stream), (long long)num_anns, (long long*)run_offsets);
+  launch_offsets_scan(num_anns, ScanInPlace{(const long long*)run_offsets}, (long long*)run_offsets, stream);
   return check_launch("poly_runs_count");
 }
 
@@ -418,10 +378,9 @@ int mi355det_poly_runs_emit(const int64_t* keys, const int64_t* point_offsets, c
   const int st = check_tables("poly_runs_emit", num_polys, num_anns, point_offsets, ann_offsets, sizes);
   if (st != MI355DET_OK) return st;
   if (num_anns == 0) return MI355DET_OK;
-  if (total_runs < num_anns) return fail(MI355DET_EINVAL, "%s: total_runs %lld is below one count per annotation", "poly_runs_emit", total_runs);
-  if (capacity < total_runs)
-    return fail(MI355DET_EINVAL, "%s: capacity %lld is smaller than the %lld counts", "poly_runs_emit", capacity, total_runs);
-  if (!run_offsets || !counts || (num_polys > 0 && !toggle_offsets)) return fail(MI355DET_EINVAL, "%s: missing operand", "poly_runs_emit");
+  const int ce = check_emit("poly_runs_emit", "%s: total_runs %lld is below one count per annotation", num_anns, total_runs, capacity, run_offsets, counts);
+  if (ce != MI355DET_OK) return ce;
+  if (num_polys > 0 && !toggle_offsets) return fail(MI355DET_EINVAL, "%s: missing operand", "poly_runs_emit");
   hipLaunchKernelGGL(poly_runs_kernel<true>, dim3(waves4(num_anns)), dim3(256), 0, S(stream), (const long long*)keys,
                      (const long long*)point_offsets, (const long long*)events, (const long long*)toggle_offsets,
                      (const long long*)ann_offsets, sizes, num_anns, (long long*)run_offsets, counts, (long long)capacity, (long long*)area,

@@ -15,12 +15,14 @@
 //   rle_scan_kernel     block d: exclusive prefix sum of the transitions (the column's first index among the mask's transitions) and
 //                       exclusive prefix max of the last positions (positions grow with x, so this IS the transition before the column),
 //                       plus the mask's area and tight box.
-//   rle_offsets_kernel  one block: run_offsets[d] = sum over d' < d of (transitions + 1).
+//   offsets scan        one block (offsets_scan.h): run_offsets[d] = sum over d' < d of (transitions + 1).
 //   rle_emit_kernel     thread (d, x): walks the column again and writes each transition's gap to the one before; thread x = 0 also writes the
 //                       mask's last count, area and box.
 // Compiled with -ffp-contract=off like mask_kernels.hip: the paste predicate has to see the bits paste_masks_kernel writes.
 #include "common.h"
 #include "mask_paste.h"
+#include "offsets_scan.h"
+#include "rle_protocol.h"
 
 #include <limits.h>
 
@@ -223,27 +225,10 @@ __global__ __launch_bounds__(256) void rle_scan_kernel(int D, int W, Tables T) {
   }
 }
 
-__global__ __launch_bounds__(256) void rle_offsets_kernel(int D, Tables T, long long* __restrict__ run_offsets) {
-  __shared__ long long s[256];
-  const int t = threadIdx.x;
-  long long carry = 0;
-  for (int base = 0; base < D; base += 256) {
-    const int d = base + t;
-    const long long n = d < D ? (long long)T.total[d] + 1 : 0;
-    s[t] = n;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-      const long long a = t >= o ? s[t - o] : 0;
-      __syncthreads();
-      s[t] += a;
-      __syncthreads();
-    }
-    if (d < D) run_offsets[d] = carry + s[t] - n;
-    carry += s[255];
-    __syncthreads();
-  }
-  if (t == 0) run_offsets[D] = carry;
-}
+struct CountsOf {                                        // a mask's counts: its transitions + 1
+  const int* total;
+  __device__ __forceinline__ long long operator()(long long d) const { return (long long)total[d] + 1; }
+};
 
 template <class Src>
 __global__ __launch_bounds__(256) void rle_emit_kernel(Src S, int D, int H, int W, int chunks, Tables T, const long long* __restrict__ run_offsets,
@@ -311,7 +296,7 @@ int mi355det_mask_rle_count(const float* dense, const float* masks, const float*
     hipLaunchKernelGGL(rle_count_kernel<PasteSrc>, dim3(num_masks * chunks), dim3(256), 0, S(stream),
                        PasteSrc{masks, boxes, m, padding, im_h, im_w, threshold}, num_masks, im_h, im_w, chunks, T);
   hipLaunchKernelGGL(rle_scan_kernel, dim3(num_masks), dim3(256), 0, S(stream), num_masks, im_w, T);
-  hipLaunchKernelGGL(rle_offsets_kernel, dim3(1), dim3(256), 0, S(stream), num_masks, T, (long long*)run_offsets);
+  launch_offsets_scan(num_masks, CountsOf{T.total}, (long long*)run_offsets, stream);
   return check_launch("mask_rle_count");
 }
 
@@ -321,10 +306,8 @@ int mi355det_mask_rle_emit(const float* dense, const float* masks, const float* 
   const int st = check_args("mask_rle_emit", dense, masks, boxes, num_masks, m, padding, im_h, im_w, threshold);
   if (st != MI355DET_OK) return st;
   if (num_masks == 0) return MI355DET_OK;
-  if (total_runs < num_masks) return fail(MI355DET_EINVAL, "%s: total_runs %lld is below one count per mask", "mask_rle_emit", total_runs);
-  if (capacity < total_runs)
-    return fail(MI355DET_EINVAL, "%s: capacity %lld is smaller than the %lld counts", "mask_rle_emit", capacity, total_runs);
-  if (!run_offsets || !counts) return fail(MI355DET_EINVAL, "%s: missing operand", "mask_rle_emit");
+  const int ce = check_emit("mask_rle_emit", "%s: total_runs %lld is below one count per mask", num_masks, total_runs, capacity, run_offsets, counts);
+  if (ce != MI355DET_OK) return ce;
   if (!workspace || workspace_bytes < mi355det_mask_rle_workspace(num_masks, im_w))
     return fail(MI355DET_EWORKSPACE, "%s: workspace too small", "mask_rle_emit");
   const Tables T = tables(workspace, num_masks, im_w);

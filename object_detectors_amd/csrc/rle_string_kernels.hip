@@ -14,7 +14,8 @@
 //             into the next column spans y = 0..h-1).
 // The count pass decodes and checks everything (status, tokens per mask); the emit pass decodes again and writes.  Integers only, no
 // atomics, one writer per element, 64-bit offsets.
-#include "common.h"
+#include "offsets_scan.h"
+#include "rle_protocol.h"
 
 #include <limits.h>
 
@@ -25,38 +26,6 @@ namespace {
 constexpr int HALO = 7, STEP = WAVE - HALO;
 constexpr int WAVES = 4;                               // per block
 constexpr long long MAX_CHARS = 1ll << 28;             // per string: keeps every 64-bit sum of 35-bit tokens far from overflow
-
-__device__ __forceinline__ long long shfl_ll(long long v, int src) {
-  const int lo = __shfl((int)v, src, WAVE), hi = __shfl((int)(v >> 32), src, WAVE);
-  return ((long long)hi << 32) | (unsigned)lo;
-}
-__device__ __forceinline__ long long shfl_up_ll(long long v, int delta) {
-  const int lo = __shfl_up((int)v, delta, WAVE), hi = __shfl_up((int)(v >> 32), delta, WAVE);
-  return ((long long)hi << 32) | (unsigned)lo;
-}
-__device__ __forceinline__ long long wave_sum_ll(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int lo = __shfl_xor((int)v, o, WAVE), hi = __shfl_xor((int)(v >> 32), o, WAVE);
-    v += ((long long)hi << 32) | (unsigned)lo;
-  }
-  return v;
-}
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, WAVE));
-  return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, WAVE));
-  return v;
-}
-__device__ __forceinline__ unsigned wave_or(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v |= (unsigned)__shfl_xor((int)v, o, WAVE);
-  return v;
-}
 
 // EMIT = false: tokens[k] = the mask's number of counts, status[k].  EMIT = true: counts, area, bbox (runs = the scanned tokens).
 template <bool EMIT>
@@ -130,11 +99,11 @@ __global__ __launch_bounds__(WAVES * WAVE) void rle_strings_kernel(const unsigne
       long long v = (live && g > 0) ? tok : 0;
 #pragma unroll
       for (int o = 2; o < WAVE; o <<= 1) {
-        const long long u = shfl_up_ll(v, o);
+        const long long u = shfl_up_i64(v, o);
         if (lane >= o) v += u;
       }
       v += (g & 1) ? carry_odd : carry_even;
-      const long long last1 = shfl_ll(v, (T - 1) & (WAVE - 1)), last2 = shfl_ll(v, (T - 2) & (WAVE - 1));
+      const long long last1 = shfl_i64(v, (T - 1) & (WAVE - 1)), last2 = shfl_i64(v, (T - 2) & (WAVE - 1));
       if (T >= 2) {
         if ((base + T) & 1) { carry_even = last1; carry_odd = last2; } else { carry_odd = last1; carry_even = last2; }
       } else if (T == 1) {
@@ -177,7 +146,7 @@ __global__ __launch_bounds__(WAVES * WAVE) void rle_strings_kernel(const unsigne
       base += T;
     }
     if (!EMIT) {
-      total = wave_sum_ll(total);
+      total = wave_sum_i64(total);
       bad = wave_or(bad);
       if (total != (long long)h * w) bad |= MI355DET_RLESTR_SUM;
       if (lane == 0) {
@@ -185,7 +154,7 @@ __global__ __launch_bounds__(WAVES * WAVE) void rle_strings_kernel(const unsigne
         status[k] = (unsigned char)bad;
       }
     } else {
-      ones = wave_sum_ll(ones);
+      ones = wave_sum_i64(ones);
       xmin = wave_min_i(xmin);
       xmax = wave_max_i(xmax);
       ymin = wave_min_i(ymin);
@@ -208,58 +177,11 @@ __global__ __launch_bounds__(WAVES * WAVE) void rle_strings_kernel(const unsigne
   }
 }
 
-// One block: run_offsets[0..n) holds the tokens per mask and becomes their exclusive sum, run_offsets[n] their total; num_bad[0] = the
-// number of masks with a status.  A thread owns ITEMS consecutive masks of each round.
-constexpr int SCAN_THREADS = 1024, ITEMS = 8;
-
-__global__ __launch_bounds__(SCAN_THREADS) void rle_strings_offsets_kernel(long long n, long long* __restrict__ run_offsets,
-                                                                            const unsigned char* __restrict__ status,
-                                                                            long long* __restrict__ num_bad) {
-  __shared__ long long s_wave[SCAN_THREADS / WAVE];
-  __shared__ long long s_bad[SCAN_THREADS / WAVE];
-  const int t = threadIdx.x, lane = t & (WAVE - 1), wv = t >> 6;
-  long long carry = 0, nbad = 0;
-  for (long long r0 = 0; r0 < n; r0 += (long long)SCAN_THREADS * ITEMS) {
-    const long long i0 = r0 + (long long)t * ITEMS;
-    long long v[ITEMS], mine = 0;
-#pragma unroll
-    for (int j = 0; j < ITEMS; ++j) {
-      v[j] = i0 + j < n ? run_offsets[i0 + j] : 0;
-      if (i0 + j < n && status[i0 + j]) ++nbad;
-      mine += v[j];
-    }
-    long long incl = mine;
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) {
-      const long long u = shfl_up_ll(incl, o);
-      if (lane >= o) incl += u;
-    }
-    if (lane == WAVE - 1) s_wave[wv] = incl;
-    __syncthreads();
-    long long before = carry, all = 0;
-    for (int j = 0; j < SCAN_THREADS / WAVE; ++j) {
-      if (j < wv) before += s_wave[j];
-      all += s_wave[j];
-    }
-    long long at = before + incl - mine;
-#pragma unroll
-    for (int j = 0; j < ITEMS; ++j) {
-      if (i0 + j < n) run_offsets[i0 + j] = at;
-      at += v[j];
-    }
-    carry += all;
-    __syncthreads();
-  }
-  nbad = wave_sum_ll(nbad);
-  if (lane == 0) s_bad[wv] = nbad;
-  __syncthreads();
-  if (t == 0) {
-    long long b = 0;
-    for (int j = 0; j < SCAN_THREADS / WAVE; ++j) b += s_bad[j];
-    run_offsets[n] = carry;
-    num_bad[0] = b;
-  }
-}
+// the side count of mi355det_rle_strings_count's scan: the masks with a status
+struct HasStatus {
+  const unsigned char* status;
+  __device__ __forceinline__ bool operator()(long long k) const { return status[k] != 0; }
+};
 
 int check_tables(const char* what, const void* bytes, long long num_bytes, const void* str_offsets_dev, const void* sizes, long long n) {
   if (n < 0 || n >= (1ll << 31) || num_bytes < 0) return fail(MI355DET_EINVAL, "%s: bad arguments", what);
@@ -289,8 +211,7 @@ int mi355det_rle_strings_count(const uint8_t* bytes, int64_t num_bytes, const in
     hipLaunchKernelGGL(rle_strings_kernel<false>, dim3(grid_for(n)), dim3(WAVES * WAVE), 0, S(stream), bytes, (long long)num_bytes,
                        (const long long*)str_offsets_dev, sizes, (long long)n, (long long*)run_offsets, status, (const long long*)nullptr,
                        (int*)nullptr, 0ll, (long long*)nullptr, (int*)nullptr);
-  hipLaunchKernelGGL(rle_strings_offsets_kernel, dim3(1), dim3(SCAN_THREADS), 0, S(stream), (long long)n, (long long*)run_offsets, status,
-                     (long long*)num_bad);
+  launch_offsets_scan(n, ScanInPlace{(const long long*)run_offsets}, (long long*)run_offsets, stream, HasStatus{status}, (long long*)num_bad);
   return check_launch("rle_strings_count");
 }
 
@@ -300,10 +221,8 @@ int mi355det_rle_strings_emit(const uint8_t* bytes, int64_t num_bytes, const int
   const int st = check_tables("rle_strings_emit", bytes, num_bytes, str_offsets_dev, sizes, n);
   if (st != MI355DET_OK) return st;
   if (n == 0) return MI355DET_OK;
-  if (total_runs < 0) return fail(MI355DET_EINVAL, "%s: total_runs %lld is negative", "rle_strings_emit", total_runs);
-  if (capacity < total_runs)
-    return fail(MI355DET_EINVAL, "%s: capacity %lld is smaller than the %lld counts", "rle_strings_emit", capacity, total_runs);
-  if (!run_offsets || (total_runs > 0 && !counts)) return fail(MI355DET_EINVAL, "%s: missing operand", "rle_strings_emit");
+  const int ce = check_emit("rle_strings_emit", "%s: total_runs %lld is negative", 0, total_runs, capacity, run_offsets, counts);
+  if (ce != MI355DET_OK) return ce;
   hipLaunchKernelGGL(rle_strings_kernel<true>, dim3(grid_for(n)), dim3(WAVES * WAVE), 0, S(stream), bytes, (long long)num_bytes,
                      (const long long*)str_offsets_dev, sizes, (long long)n, (long long*)nullptr, (unsigned char*)nullptr,
                      (const long long*)run_offsets, counts, (long long)capacity, (long long*)area, bbox);

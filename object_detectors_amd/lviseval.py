@@ -270,7 +270,7 @@ class LVISSegmEval(LVISEval):
             hw = [tuple(int(v) for v in self._image_hw[self._img_index[anns[j]["image_id"]]]) for j in which]
             r = segmentations_to_rle([segs[j] for j in which], hw, self.device)
         if which and len(which) == len(segs):                      # LVIS's own form: the run lengths stay on the device
-            store.add_arrays(r.counts, np.diff(np.asarray(r.offsets, np.int64)), r.area, r.bbox, r.sizes)
+            store.add_batch(r)
         else:
             if which:                                              # mixed forms: the polygons join the others as count lists
                 host = np.ascontiguousarray(r.counts.detach().cpu().numpy(), dtype=np.int32)

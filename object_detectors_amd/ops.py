@@ -882,6 +882,26 @@ def _device_bytes(what, **tensors):
             raise ValueError(f"{what}: {name} must be a contiguous {dtype} CUDA/HIP tensor (no CPU fallback)")
 
 
+def _need_device(what, *tensors):
+    """The refusal of the run-length and evaluation ops: every operand named here is a tensor on the device."""
+    for t in tensors:
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise ValueError(f"{what} needs CUDA/HIP tensors (no CPU fallback)")
+
+
+def _emit_buffers(n, total, capacity, dev, out=None):
+    """What an emit pass of "count, one host read, emit" writes for n masks with `total` counts: (counts int32 [cap], area int64 [n],
+    bbox int32 [n, 4], cap).  cap = `capacity` or the exact size; `out` = the caller's counts buffer in place of a new one."""
+    cap = int(total) if capacity is None else int(capacity)
+    counts = torch.empty(max(cap, 0), dtype=torch.int32, device=dev) if out is None else out
+    return counts, torch.empty(n, dtype=torch.int64, device=dev), torch.empty((n, 4), dtype=torch.int32, device=dev), cap
+
+
+def _no_runs(dev):
+    """(counts, area, bbox) of no masks."""
+    return _emit_buffers(0, 0, None, dev)[:3]
+
+
 def yolo_ingest_u8(packed, table, table_dev, taps_dev, lut, size, out=None):
     """mi355det_yolo_ingest_u8: OpenCV's 8-bit bicubic resize to size x size, / 255 and normalise of a packed batch of uint8 images in one
     launch (the rule: include/mi355det.h).  packed: uint8 [bytes] on the device; table: a host (_lib.YoloImage * n) array, table_dev: its
@@ -935,8 +955,8 @@ def _mask_rle(dense, masks, boxes, D, M, padding, H, W, threshold, dev, capacity
     if D == 0:
         # the argument checks still run (no launch: num_masks == 0 succeeds)
         check(L.mi355det_mask_rle_count(ptr(dense), ptr(masks), ptr(boxes), 0, M, padding, H, W, threshold, None, None, 0, stream_ptr()), "mask_rle_count")
-        return RLEBatch((H, W), torch.empty(0, dtype=torch.int32, device=dev), [0], torch.empty(0, dtype=torch.int64, device=dev),
-                        torch.empty((0, 4), dtype=torch.int32, device=dev))
+        counts, area, bbox = _no_runs(dev)
+        return RLEBatch((H, W), counts, [0], area, bbox)
     nbytes = L.mi355det_mask_rle_workspace(D, W)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     run_offsets = torch.empty(D + 1, dtype=torch.int64, device=dev)
@@ -944,10 +964,7 @@ def _mask_rle(dense, masks, boxes, D, M, padding, H, W, threshold, dev, capacity
     check(L.mi355det_mask_rle_count(*src, ptr(run_offsets), ptr(ws), nbytes, stream_ptr()), "mask_rle_count")
     offsets = run_offsets.tolist()                         # the one host read: the strings are built from these numbers anyway
     total = offsets[-1]
-    cap = total if capacity is None else int(capacity)
-    counts = torch.empty(max(cap, 0), dtype=torch.int32, device=dev)
-    area = torch.empty(D, dtype=torch.int64, device=dev)
-    bbox = torch.empty((D, 4), dtype=torch.int32, device=dev)
+    counts, area, bbox, cap = _emit_buffers(D, total, capacity, dev)
     check(L.mi355det_mask_rle_emit(*src, ptr(run_offsets), total, ptr(counts), cap, ptr(area), ptr(bbox), ptr(ws), nbytes, stream_ptr()),
           "mask_rle_emit")
     return RLEBatch((H, W), counts, offsets, area, bbox)
@@ -984,9 +1001,7 @@ RLESTR_PARSE = RLESTR_ALPHABET | RLESTR_LONG | RLESTR_OPEN | RLESTR_INT32       
 
 def _rle_strings_operands(what, packed, str_offsets, str_offsets_dev, sizes):
     import numpy as np
-    for t in (packed, str_offsets_dev, sizes):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise ValueError(f"{what} needs CUDA/HIP tensors (no CPU fallback)")
+    _need_device(what, packed, str_offsets_dev, sizes)
     host = np.ascontiguousarray(str_offsets, dtype=np.int64).reshape(-1)
     n = int(host.shape[0]) - 1
     if packed.dtype != torch.uint8 or str_offsets_dev.dtype != torch.int64 or sizes.dtype != torch.int32:
@@ -1012,16 +1027,11 @@ def rle_strings_count(packed, str_offsets, str_offsets_dev, sizes):
 def rle_strings_emit(packed, str_offsets_dev, sizes, run_offsets, total_runs, capacity=None):
     """mi355det_rle_strings_emit after rle_strings_count on the same operands: run_offsets int64 [n + 1] on the device, total_runs the
     host's copy of its last entry -> (counts int32 [total_runs], area int64 [n], bbox int32 [n, 4]) on the device."""
-    for t in (packed, str_offsets_dev, sizes, run_offsets):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise ValueError("rle_strings_emit needs CUDA/HIP tensors (no CPU fallback)")
-    n, dev = int(sizes.shape[0]), packed.device
+    _need_device("rle_strings_emit", packed, str_offsets_dev, sizes, run_offsets)
+    n = int(sizes.shape[0])
     if run_offsets.dtype != torch.int64 or int(run_offsets.numel()) < n + 1 or int(str_offsets_dev.numel()) != n + 1:
         raise ValueError("rle_strings_emit: run_offsets and str_offsets_dev must be int64 [n + 1]")
-    cap = int(total_runs) if capacity is None else int(capacity)
-    counts = torch.empty(max(cap, 0), dtype=torch.int32, device=dev)
-    area = torch.empty(n, dtype=torch.int64, device=dev)
-    bbox = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    counts, area, bbox, cap = _emit_buffers(n, total_runs, capacity, packed.device)
     check(lib().mi355det_rle_strings_emit(ptr(packed), int(packed.numel()), ptr(str_offsets_dev), ptr(sizes), n, ptr(run_offsets),
                                           int(total_runs), ptr(counts), cap, ptr(area), ptr(bbox), stream_ptr()), "rle_strings_emit")
     return counts, area, bbox
@@ -1081,8 +1091,7 @@ class BoundaryPlan:
 
     def __init__(self, counts, runs, sizes, dilation, boxes, index=None, budget_bytes=1 << 30):
         import numpy as np
-        if not torch.is_tensor(counts) or not counts.is_cuda:
-            raise ValueError("rle_boundary needs CUDA/HIP tensors (no CPU fallback)")
+        _need_device("rle_boundary", counts)
         for t in (runs, sizes, dilation, boxes, index):
             if torch.is_tensor(t) and not t.is_cuda:
                 raise ValueError("rle_boundary needs CUDA/HIP tensors (no CPU fallback); tables for the host checks are numpy arrays or lists")
@@ -1131,11 +1140,9 @@ class BoundaryPlan:
         return torch.cat([torch.zeros(1, **i64), torch.cumsum(num_runs, 0)])
 
     def emit(self, run_offsets, total):
-        out = torch.empty(int(total), dtype=torch.int32, device=self.dev)
-        area = torch.empty(self.n, dtype=torch.int64, device=self.dev)
-        bbox = torch.empty((self.n, 4), dtype=torch.int32, device=self.dev)
+        out, area, bbox, cap = _emit_buffers(self.n, total, None, self.dev)
         for first, num in self.chunks:
-            check(lib().mi355det_rle_boundary_emit(*self._tables, first, num, ptr(run_offsets), int(total), ptr(out), int(total), ptr(area),
+            check(lib().mi355det_rle_boundary_emit(*self._tables, first, num, ptr(run_offsets), cap, ptr(out), cap, ptr(area),
                                                    ptr(bbox), ptr(self.ws), self.nbytes, stream_ptr()), "rle_boundary_emit")
         return out, area, bbox
 
@@ -1203,7 +1210,8 @@ def poly_rle(xy, poly_offsets, ann_offsets, sizes, capacity=None, device=None, m
     mark = mark or (lambda name: None)
     i64 = dict(dtype=torch.int64, device=dev)
     if A == 0:
-        return (torch.empty(0, dtype=torch.int32, device=dev), [0], torch.empty(0, **i64), torch.empty((0, 4), dtype=torch.int32, device=dev))
+        counts, area, bbox = _no_runs(dev)
+        return counts, [0], area, bbox
     L = lib()
     d_xy = torch.as_tensor(xy, dtype=torch.float64).to(dev).contiguous().reshape(-1)
     d_po, d_ao, d_sz = torch.from_numpy(po).to(dev), torch.from_numpy(ao).to(dev), torch.from_numpy(sz).to(dev)
@@ -1237,15 +1245,11 @@ def poly_rle(xy, poly_offsets, ann_offsets, sizes, capacity=None, device=None, m
     check(L.mi355det_poly_runs_count(*src, ptr(run_offsets), stream_ptr()), "poly_runs_count")
     offsets = run_offsets.tolist()                         # host read 2 of 2
     total = offsets[-1]
-    cap = total if capacity is None else int(capacity)
-    if out is None:
-        counts = torch.empty(max(cap, 0), dtype=torch.int32, device=dev)
-    else:                                                  # the caller's buffer: nothing is written at or past `capacity`
-        counts = out
-        if counts.dtype != torch.int32 or counts.device != d_ao.device or not counts.is_contiguous() or counts.numel() < cap:
-            raise ValueError("poly_rle: out must be a contiguous int32 device tensor of at least `capacity` elements")
-    area = torch.empty(A, **i64)
-    bbox = torch.empty((A, 4), dtype=torch.int32, device=dev)
+    # the caller's buffer: nothing is written at or past `capacity`
+    if out is not None and (out.dtype != torch.int32 or out.device != d_ao.device or not out.is_contiguous()
+                            or out.numel() < (total if capacity is None else int(capacity))):
+        raise ValueError("poly_rle: out must be a contiguous int32 device tensor of at least `capacity` elements")
+    counts, area, bbox, cap = _emit_buffers(A, total, capacity, dev, out)
     check(L.mi355det_poly_runs_emit(*src, ptr(run_offsets), total, ptr(counts), cap, ptr(area), ptr(bbox), stream_ptr()), "poly_runs_emit")
     mark("runs")
     return counts, offsets, area, bbox
@@ -1290,8 +1294,7 @@ def coco_iou(dt_offsets, gt_offsets, iou_offsets, iou_size, dt_boxes, gt_boxes, 
     on the device and dt_sizes / gt_sizes = host int32 [NG, 2]; the boxes are then the masks' tight boxes."""
     import numpy as np
     dev = dt_boxes.device
-    if not dt_boxes.is_cuda:
-        raise ValueError("coco_iou needs CUDA/HIP tensors (no CPU fallback)")
+    _need_device("coco_iou", dt_boxes)
     ng = int(dt_offsets.shape[0]) - 1
     nd, ngt = int(dt_boxes.shape[0]), int(gt_boxes.shape[0])
     out = torch.empty(int(iou_size), dtype=torch.float64, device=dev)
@@ -1331,8 +1334,7 @@ def _match(entry, what, dt_offsets, gt_offsets, iou_offsets, iou, dt_area, gt_ar
 
 def coco_match(dt_offsets, gt_offsets, iou_offsets, iou, dt_area, gt_area, gt_crowd, iou_thrs, area_rngs):
     """mi355det_coco_match -> dt_match int32 [A, T, ND], dt_ignore uint8 [A, T, ND], gt_match int32 [A, T, NG], gt_ignore uint8 [A, NG]."""
-    if not iou.is_cuda:
-        raise ValueError("coco_match needs CUDA/HIP tensors (no CPU fallback)")
+    _need_device("coco_match", iou)
     return _match(lib().mi355det_coco_match, "coco_match", dt_offsets, gt_offsets, iou_offsets, iou, dt_area, gt_area, [gt_crowd], iou_thrs,
                   area_rngs)
 
@@ -1340,8 +1342,7 @@ def coco_match(dt_offsets, gt_offsets, iou_offsets, iou, dt_area, gt_area, gt_cr
 def lvis_match(dt_offsets, gt_offsets, iou_offsets, iou, dt_area, gt_area, gt_flag, group_not_exhaustive, iou_thrs, area_rngs):
     """mi355det_lvis_match (the match under LVISEval's rules: gt_flag uint8 [NG] = the annotations' ignore flags, group_not_exhaustive uint8
     [groups]) -> the four arrays of coco_match, same layouts."""
-    if not (iou.is_cuda and group_not_exhaustive.is_cuda):
-        raise ValueError("lvis_match needs CUDA/HIP tensors (no CPU fallback)")
+    _need_device("lvis_match", iou, group_not_exhaustive)
     if group_not_exhaustive.dtype != torch.uint8 or int(group_not_exhaustive.shape[0]) != int(dt_offsets.shape[0]) - 1:
         raise ValueError("lvis_match: group_not_exhaustive must be uint8, one flag per group")
     return _match(lib().mi355det_lvis_match, "lvis_match", dt_offsets, gt_offsets, iou_offsets, iou, dt_area, gt_area,
@@ -1351,8 +1352,7 @@ def lvis_match(dt_offsets, gt_offsets, iou_offsets, iou, dt_area, gt_area, gt_fl
 def coco_accumulate(cat_dt_offsets, cat_gt_offsets, order, dt_rank, dt_score, dt_match, dt_ignore, gt_ignore, max_dets, rec_thrs):
     """mi355det_coco_accumulate -> precision [T, R, K, A, M], recall [T, K, A, M], scores [T, R, K, A, M] (float64)."""
     dev = rec_thrs.device
-    if not rec_thrs.is_cuda:
-        raise ValueError("coco_accumulate needs CUDA/HIP tensors (no CPU fallback)")
+    _need_device("coco_accumulate", rec_thrs)
     K = int(cat_dt_offsets.shape[0]) - 1
     A, T, nd = (int(v) for v in dt_match.shape)
     ngt, R, M = int(gt_ignore.shape[1]), int(rec_thrs.shape[0]), len(max_dets)
@@ -1370,8 +1370,7 @@ def coco_bootstrap(cat_dt_offsets, cat_gt_offsets, order, dt_rank, dt_match, dt_
                    weights):
     """mi355det_coco_bootstrap: coco_accumulate's operands without the scores, dt_image [ND] / gt_image [NG] int32 (each slot's image index)
     and weights int32 [num_images, B] (replicate-minor) -> ap_sum, recall float64 [B, T, K, A, M]."""
-    if not (torch.is_tensor(weights) and weights.is_cuda and rec_thrs.is_cuda):
-        raise ValueError("coco_bootstrap needs CUDA/HIP tensors (no CPU fallback)")
+    _need_device("coco_bootstrap", weights, rec_thrs)
     dev = weights.device
     if weights.dtype != torch.int32 or weights.dim() != 2 or dt_image.dtype != torch.int32 or gt_image.dtype != torch.int32:
         raise ValueError("coco_bootstrap: weights [num_images, B], dt_image and gt_image must be int32")
@@ -1399,8 +1398,7 @@ def _one_group(d, g, dev):
 def coco_box_iou(dt_xywh, gt_xywh, iscrowd):
     """pycocotools maskUtils.iou on boxes: [D, 4] against [G, 4] as [x, y, w, h], iscrowd [G] -> float64 [D, G].  float32 inputs are widened
     exactly; all arithmetic is float64."""
-    if not (torch.is_tensor(dt_xywh) and dt_xywh.is_cuda):
-        raise ValueError("coco_box_iou needs CUDA/HIP tensors (no CPU fallback)")
+    _need_device("coco_box_iou", dt_xywh)
     dev = dt_xywh.device
     dt, gt = _f64c(dt_xywh, dev).reshape(-1, 4), _f64c(gt_xywh, dev).reshape(-1, 4)
     crowd = torch.as_tensor(iscrowd, device=dev).to(torch.uint8).contiguous()
@@ -1413,8 +1411,7 @@ def coco_box_iou(dt_xywh, gt_xywh, iscrowd):
 def coco_mask_iou(dt, gt, iscrowd):
     """pycocotools maskUtils.iou on run-length encodings: RLEBatch [D] against RLEBatch [G] of the same [H, W] -> float64 [D, G]."""
     dev = dt.counts.device
-    if not dt.counts.is_cuda:
-        raise ValueError("coco_mask_iou needs CUDA/HIP tensors (no CPU fallback)")
+    _need_device("coco_mask_iou", dt.counts)
     crowd = torch.as_tensor(iscrowd, device=dev).to(torch.uint8).contiguous()
     D, G = len(dt), len(gt)
     if crowd.shape[0] != G:
@@ -1429,8 +1426,7 @@ def coco_boundary_iou(dt, gt, iscrowd, dilation_ratio=0.02):
     """The IoU that `iou_type="boundary"` matches on: min(mask IoU, boundary IoU), element by element, RLEBatch [D] against RLEBatch [G] of
     the same [H, W] -> float64 [D, G].  The boundary IoU is coco_mask_iou on RLEBatch.boundary(dilation_ratio) of both sides with the same
     iscrowd flags (a crowd ground truth divides by the detection's boundary area)."""
-    if not dt.counts.is_cuda or not gt.counts.is_cuda:
-        raise ValueError("coco_boundary_iou needs CUDA/HIP tensors (no CPU fallback)")
+    _need_device("coco_boundary_iou", dt.counts, gt.counts)
     return torch.minimum(coco_mask_iou(dt, gt, iscrowd), coco_mask_iou(dt.boundary(dilation_ratio), gt.boundary(dilation_ratio), iscrowd))
 
 
@@ -1440,8 +1436,7 @@ def box_disagreement(gt_offsets, gt_box, gt_label, dt_a, dt_b, iou_threshold):
     = (dt_offsets int64 [I + 1], dt_box float64 [D, 4], dt_label int64 [D]) of the two models, everything on the device ->
     best_iou float64 [2, G], best_index int32 [2, G] (within the image's detections; -1: the image has none), correct uint8 [2, G]."""
     tensors = (gt_offsets, gt_box, gt_label) + tuple(dt_a) + tuple(dt_b)
-    if not all(torch.is_tensor(t) and t.is_cuda for t in tensors):
-        raise ValueError("box_disagreement needs CUDA/HIP tensors (no CPU fallback)")
+    _need_device("box_disagreement", *tensors)
     dev = gt_box.device
     i64c = lambda t: t.to(torch.int64).contiguous()
     I = int(gt_offsets.shape[0]) - 1

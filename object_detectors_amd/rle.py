@@ -60,10 +60,13 @@ def pack_strings(strings):
 
 def counts_stats(counts, offsets, h):
     """Set pixels (int64 [D]) and tight boxes [xmin, ymin, xmax - xmin + 1, ymax - ymin + 1] (int32 [D, 4], zeros for an empty mask) of
-    run lengths over columns of height h: concatenated int32 counts, mask d owning counts[offsets[d]:offsets[d + 1]]."""
+    run lengths over columns of height h (one for all masks, or one per mask): concatenated int32 counts, mask d owning
+    counts[offsets[d]:offsets[d + 1]]."""
     n = len(offsets) - 1
     area, bbox = np.zeros(n, np.int64), np.zeros((n, 4), np.int32)
+    heights = np.broadcast_to(np.asarray(h, np.int64), (n,))
     for d in range(n):
+        h = int(heights[d])
         c = np.asarray(counts[offsets[d]:offsets[d + 1]], np.int64)
         end = np.cumsum(c)
         first, last = (end - c)[1::2], end[1::2] - 1           # the runs of ones: first and last pixel index

@@ -339,6 +339,18 @@ def test_refusals(sets):
                 dict(sizes=[[1 << 16, 1 << 15]]), dict(runs=[0, n + 1]), dict(index=[1])):
         with pytest.raises(ValueError, match="rle_boundary"):
             ops.rle_boundary(**args(c.to(DEV), **bad))
+    # what the emit pass says of the numbers read back from the count pass, word for word (refused before any launch)
+    from object_detectors_amd import _lib
+    plan = ops.BoundaryPlan(**args(c.to(DEV)))
+    offs, buf = plan.count(), torch.zeros(64, dtype=torch.int32, device=DEV)
+    (first, num), = plan.chunks
+    emit = lambda total=5, counts=_lib.ptr(buf), cap=5: _lib.lib().mi355det_rle_boundary_emit(
+        *plan._tables, first, num, _lib.ptr(offs), total, counts, cap, None, None, _lib.ptr(plan.ws), plan.nbytes, _lib.stream_ptr())
+    for kw, text in ((dict(cap=4), "rle_boundary_emit: capacity 4 is smaller than the 5 counts"),
+                     (dict(total=0), "rle_boundary_emit: total_runs 0 is below one count per mask"),
+                     (dict(counts=None), "rle_boundary_emit: missing operand")):
+        assert emit(**kw) == -1, kw
+        assert _lib.lib().mi355det_last_error().decode() == text
     for ratio in (0, -0.02):
         with pytest.raises(ValueError, match="dilation ratio"):
             COCOEval(sets["dataset"], "boundary", dilation_ratio=ratio)

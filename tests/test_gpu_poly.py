@@ -127,6 +127,28 @@ def test_several_sizes_in_one_call_and_no_annotations():
     assert only_empty.counts.cpu().tolist() == [35, 35] and only_empty.area.cpu().tolist() == [0, 0]
 
 
+SCAN_TRIANGLES = [[0.5, 0.5, 3.5, 0.5, 2.0, 3.5], [0.0, 0.0, 4.0, 4.0, 4.0, 0.0], [1.0, 1.0, 3.0, 1.25, 1.25, 3.0]]
+SCAN_POOL = [[t] for t in SCAN_TRIANGLES] + [[SCAN_TRIANGLES[0], SCAN_TRIANGLES[2]], []]          # one part, one part, one part, two, none
+
+
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 2048, 2049, 8191, 8192, 8193, 16385])
+def test_run_offsets_at_the_edges_of_the_scan(n):
+    """The offsets scan (csrc/offsets_scan.h: over the polygons' points and toggles and over the annotations' runs) at one item, a wave
+    boundary, the step from the small block to the large one (256 x 8 items), a round of 1024 x 8 items and the carry into a third round:
+    n annotations of triangles on 4 x 4 images, a deterministic mix of one part, two parts and none, each form encoded by the oracle once."""
+    from object_detectors_amd.polygons import polygons_to_rle
+    p_counts, p_offs, p_area, p_bbox = po.encode_annotations(SCAN_POOL, [(4, 4)] * len(SCAN_POOL))
+    p_offs = np.asarray(p_offs, np.int64)
+    i = np.arange(n)
+    kind = np.where(i % 11 == 3, 3, np.where(i % 11 == 7, 4, (i + i // 5) % 3))
+    offs = np.concatenate([[0], np.cumsum(np.diff(p_offs)[kind])])
+    assert n < 63 or len(set(np.diff(offs).tolist())) >= 3
+    b = polygons_to_rle([SCAN_POOL[k] for k in kind], 4, 4, dev())
+    want = np.concatenate([p_counts[p_offs[k]:p_offs[k + 1]] for k in kind]) if n else np.zeros(0, np.int64)
+    assert len(b) == n
+    assert_fields(b.counts, b.offsets, b.area, b.bbox, (want, offs.tolist(), np.asarray(p_area)[kind], np.asarray(p_bbox).reshape(-1, 4)[kind]))
+
+
 def test_nothing_is_written_past_the_capacity():
     from object_detectors_amd import ops
     from object_detectors_amd.polygons import flatten

@@ -72,6 +72,28 @@ def test_dense_exact(h, w):
     assert [r["counts"] for r in batch.to_coco()] == [ro.to_string(batch.counts_of(i)) for i in range(len(batch))]
 
 
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 2048, 2049, 8191, 8192, 8193, 16385])
+def test_run_offsets_at_the_edges_of_the_scan(n):
+    """The offsets scan (csrc/offsets_scan.h) at one item, a wave boundary, the step from the small block to the large one (256 x 8 items),
+    a round of 1024 x 8 items and the carry into a third round: n dense 2 x 2 masks, a deterministic mix of all 16, each pattern encoded by the oracle once."""
+    from object_detectors_amd import ops
+    pattern = ((np.arange(16)[:, None] >> np.arange(4)) & 1).astype(bool).reshape(16, 2, 2)
+    p_counts, p_offs, p_area, p_bbox = ro.encode_batch(pattern)
+    p_offs = np.asarray(p_offs, np.int64)
+    kind = (np.arange(n) * 7 + np.arange(n) // 5) % 16
+    offs = np.concatenate([[0], np.cumsum(np.diff(p_offs)[kind])])
+    assert n < 16 or len(set(np.diff(offs).tolist())) >= 4
+    batch = ops.mask_rle_dense(torch.from_numpy(pattern[kind].astype(np.float32)).to(dev()))
+    assert batch.size == (2, 2) and len(batch) == n and batch.offsets == offs.tolist()
+    want = np.concatenate([p_counts[p_offs[k]:p_offs[k + 1]] for k in kind]) if n else np.zeros(0, np.int64)
+    got = batch.counts.cpu().numpy()
+    assert got.dtype == np.int32 and np.array_equal(got.astype(np.int64), want)
+    assert batch.area.dtype == torch.int64 and np.array_equal(batch.area.cpu().numpy(), np.asarray(p_area, np.int64)[kind])
+    assert batch.bbox.dtype == torch.int32 and np.array_equal(batch.bbox.cpu().numpy(), np.asarray(p_bbox, np.int32).reshape(16, 4)[kind])
+    if 0 < n <= 65:
+        assert np.array_equal(batch.decode().numpy(), pattern[kind].astype(np.uint8))
+
+
 def test_dense_no_masks():
     from object_detectors_amd import ops
     b = ops.mask_rle_dense(torch.zeros((0, 6, 4), device=dev()))
@@ -195,6 +217,15 @@ def test_errors():
     assert b"missing operand" in L.mi355det_last_error()
     assert L.mi355det_mask_rle_count(_lib.ptr(x), None, None, 1, 1, 0, 4, 4, 0.5, _lib.ptr(ro64), _lib.ptr(ws), 8, _lib.stream_ptr()) == -3
     assert L.mi355det_mask_rle_count(_lib.ptr(x), None, None, 1, 1, 0, 0, 4, 0.5, _lib.ptr(ro64), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()) == -1
+    # what the emit pass says of the numbers read back from the count pass, word for word (refused before any launch)
+    buf = torch.zeros(8, dtype=torch.int32, device=dev())
+    emit = lambda total=3, counts=_lib.ptr(buf), cap=3: L.mi355det_mask_rle_emit(
+        _lib.ptr(x), None, None, 1, 1, 0, 4, 4, 0.5, _lib.ptr(ro64), total, counts, cap, None, None, _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+    for kw, text in ((dict(cap=2), "mask_rle_emit: capacity 2 is smaller than the 3 counts"),
+                     (dict(total=0), "mask_rle_emit: total_runs 0 is below one count per mask"),
+                     (dict(counts=None), "mask_rle_emit: missing operand")):
+        assert emit(**kw) == -1, kw
+        assert L.mi355det_last_error().decode() == text
     with pytest.raises(ValueError):
         ops.mask_rle_dense(torch.zeros((1, 4, 4)))                        # a CPU tensor
     with pytest.raises(ValueError):

@@ -124,6 +124,41 @@ def test_no_mask_and_empty_strings():
     assert status.tolist() == [ops.RLESTR_SUM, ops.RLESTR_SUM] and runs.tolist() == [0, 0, 0]
 
 
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 2048, 2049, 8191, 8192, 8193, 16385])
+def test_run_offsets_at_the_edges_of_the_scan(n):
+    """The offsets scan (csrc/offsets_scan.h) at one item, a wave boundary, the step from the small block to the large one (256 x 8 items),
+    a round of 1024 x 8 items and the carry into a third round: the smallest strings there are, a deterministic mix of six forms, and a refused one (its counts do not add up) at 0, 8191 and n - 1."""
+    from object_detectors_amd import ops
+    from object_detectors_amd.rle import pack_strings
+    pool = [([4], (2, 2)), ([0, 4], (2, 2)), ([1, 1, 2], (2, 2)), ([3], (1, 3)), ([1, 2], (1, 3)), ([1, 1, 1], (1, 3)), ([1, 2], (2, 2))]
+    refused = len(pool) - 1
+    text = [ro.to_string(c) for c, _size in pool]
+    assert all(1 <= len(s) <= 3 for s in text)
+    decoded = [ro.from_string(s).astype(np.int32) for s in text]                 # the host oracle: a string owns one count per token
+    p_area = np.asarray([ro.area(c) for c in decoded], np.int64)                 # of the refused form: never compared
+    p_bbox = np.asarray([ro.bbox(ro.decode(c, h, w)) if j != refused else [0] * 4 for j, (c, (_c, (h, w))) in enumerate(zip(decoded, pool))],
+                        np.int32)
+    kind = (np.arange(n) + np.arange(n) // 5) % refused
+    bad_at = np.asarray(sorted({j for j in (0, 8191, n - 1) if 0 <= j < n}), np.int64)
+    kind[bad_at] = refused
+    runs = np.concatenate([[0], np.cumsum(np.asarray([len(c) for c in decoded], np.int64)[kind])])
+    assert n < 6 or len(set(np.diff(runs).tolist())) == 3
+    packed, offsets = pack_strings([text[k] for k in kind])
+    sizes = np.asarray([pool[k][1] for k in kind], np.int32).reshape(-1, 2)
+    d_bytes, d_off, d_sz = torch.from_numpy(packed).to(DEV), torch.from_numpy(offsets).to(DEV), torch.from_numpy(sizes).to(DEV)
+    table, status = ops.rle_strings_count(d_bytes, offsets, d_off, d_sz)
+    host = table.cpu().numpy()
+    assert np.array_equal(host[:n + 1], runs) and int(host[n + 1]) == len(bad_at)
+    want = np.zeros(n, np.uint8)
+    want[bad_at] = ops.RLESTR_SUM
+    assert np.array_equal(status.cpu().numpy(), want)
+    counts, area, bbox = ops.rle_strings_emit(d_bytes, d_off, d_sz, table, int(runs[-1]))
+    assert np.array_equal(counts.cpu().numpy(), np.concatenate([decoded[k] for k in kind]) if n else np.zeros(0, np.int32))
+    good = kind != refused                                                       # a refused mask's area and box are of no use
+    assert np.array_equal(area.cpu().numpy()[good], p_area[kind][good])
+    assert np.array_equal(bbox.cpu().numpy()[good], p_bbox[kind][good])
+
+
 def test_status_bits(one_call):
     """Each malformed kind sets its bit on its mask only; the ranges the kernels are given are checked by them, not trusted."""
     from object_detectors_amd import ops

@@ -1,6 +1,7 @@
 """Host side of the polygon path (object_detectors_amd/polygons.py, ops.poly_rle, tvision/coco_utils.py): every refusal is a ValueError
 raised before the library or the device is touched, dataset_to_rle passes non-polygon segmentations through, and the new entry points are
 declared and bound.  No GPU."""
+import ctypes as C
 import os
 import re
 
@@ -172,6 +173,15 @@ def test_entry_points_refuse_bad_arguments_without_a_launch():
     assert b"rle_decode" in L.mi355det_last_error()
     assert L.mi355det_rle_decode(None, None, 0, 4, 4, None, None) == 0
     assert L.mi355det_poly_points_count(None, None, None, None, 0, 0, None, None) == 0
+    # what the emit pass says of the numbers read back from the count pass, word for word; refused calls touch no pointer
+    fake = C.c_void_p(4096)
+    emit = lambda total=5, counts=fake, cap=5: \
+        L.mi355det_poly_runs_emit(fake, fake, fake, fake, fake, fake, 2, 3, fake, total, counts, cap, None, None, None)
+    for kw, text in ((dict(cap=4), "poly_runs_emit: capacity 4 is smaller than the 5 counts"),
+                     (dict(total=2), "poly_runs_emit: total_runs 2 is below one count per annotation"),
+                     (dict(counts=None), "poly_runs_emit: missing operand")):
+        assert emit(**kw) == -1, kw
+        assert L.mi355det_last_error().decode() == text
 
 
 def test_shims_register_coco_utils():

@@ -78,6 +78,12 @@ def test_c_entries_refuse_bad_tables():
         assert emit(**kw) == -1, kw
         assert L.mi355det_last_error().decode().startswith("rle_strings_emit")
     assert emit(n=0, dev=None, sizes=None, runs=None, counts=None) == 0          # no mask: nothing to do, no launch
+    # what the emit pass says of the numbers read back from the count pass, word for word
+    for kw, text in ((dict(cap=3), "rle_strings_emit: capacity 3 is smaller than the 4 counts"),
+                     (dict(total=-1), "rle_strings_emit: total_runs -1 is negative"),          # a refused mask owns no counts: 0 passes
+                     (dict(counts=None), "rle_strings_emit: missing operand")):
+        assert emit(**kw) == -1, kw
+        assert L.mi355det_last_error().decode() == text
 
 
 def test_cpu_store_keeps_the_host_route():
