@@ -1128,6 +1128,32 @@ int mi355det_coco_accumulate(int32_t num_cats, const int64_t* cat_dt_offsets, co
                              int32_t num_max_dets, const double* rec_thrs, int32_t num_recs, double* precision, double* recall, double* scores,
                              void* stream);
 
+/* ---- COCO keypoint evaluation (csrc/oks_kernels.hip, csrc/cocoeval_kernels.hip): pycocotools COCOeval.computeOks and evaluateImg for
+ * `keypoints`, on the groups, offsets and guarantees of the "COCO evaluation" block above.  pycocotools is not installed where this was
+ * written: the rules below are restated from memory of its cocoeval.py, and the tests compare against a literal host form of this text.
+ *   coco_oks         the ragged buffer of coco_iou (same offsets, one wavefront per group, row-major [D, G] per group, float64) filled with
+ *                    the object keypoint similarity.  Operands ON THE DEVICE, K = num_keypoints per instance: dt_kp float64 [num_dt, K, 2] =
+ *                    x, y of each keypoint (a detection's visibility is never read); gt_kp float64 [num_gt, K, 3] = x, y, v; gt_boxes
+ *                    float64 [num_gt, 4] = [x, y, w, h]; gt_area float64 [num_gt]; vars float64 [K] = (2 * sigma)^2, built by the caller
+ *                    (never recomputed here).  Per ground truth: k1 = the number of keypoints with v > 0; x0 = bx - bw, x1 = bx + bw*2,
+ *                    y0 = by - bh, y1 = by + bh*2.  Per pair and keypoint i: if k1 > 0, dx = xd - xg, dy = yd - yg; else dx = max(0, x0 -
+ *                    xd) + max(0, xd - x1) and dy likewise; e = (dx*dx + dy*dy) / vars[i] / (area + 2^-52) / 2, left to right.  oks =
+ *                    sum(exp(-e_i)) / n over the keypoints with v > 0, n = k1, when k1 > 0; over all K keypoints, n = K, otherwise.  The
+ *                    sum runs in ascending keypoint order in one lane (the order is part of the contract); exp is the device library's
+ *                    float64 exp; the ground truths of a group are staged in LDS once per group.  Crowd plays no part.
+ *                    MI355DET_EINVAL before any launch: num_keypoints < 1 or > 64, negative sizes, a missing operand with groups present.
+ *   keypoints_match  coco_match with the two ground-truth flags apart (same kernel body through one more template switch; same outputs,
+ *                    layouts, guarantees and 64-lane limit).  gt_flag [num_gt] uint8 = the annotation's ignore flag (iscrowd, or
+ *                    num_keypoints == 0); gt_crowd [num_gt] uint8 = iscrowd alone.  gt_ignore = gt_flag, or area outside the range; a
+ *                    ground truth already matched at this threshold is skipped unless gt_crowd is set. */
+int mi355det_coco_oks(int64_t num_groups, const int64_t* dt_offsets, const int64_t* gt_offsets, const int64_t* iou_offsets, int64_t num_dt,
+                      int64_t num_gt, int64_t iou_size, int32_t num_keypoints, const double* dt_kp, const double* gt_kp,
+                      const double* gt_boxes, const double* gt_area, const double* vars, double* oks, void* stream);
+int mi355det_keypoints_match(int64_t num_groups, const int64_t* dt_offsets, const int64_t* gt_offsets, const int64_t* iou_offsets, int64_t num_dt,
+                             int64_t num_gt, int64_t iou_size, const double* iou, const double* dt_area, const double* gt_area,
+                             const uint8_t* gt_flag, const uint8_t* gt_crowd, const double* iou_thrs, int32_t num_thrs, const double* area_rngs,
+                             int32_t num_areas, int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore, void* stream);
+
 /* ---- Bootstrap replicates (csrc/bootstrap_kernels.hip): coco_accumulate for num_replicates resampled data sets at once, reduced in place to
  * one precision sum and one recall per cell.  The arguments of coco_accumulate without the scores (same layouts, same meaning; the match
  * arrays are those of coco_match / lvis_match and are not touched), plus dt_image [num_dt] / gt_image [num_gt] int32 = each slot's image

@@ -249,6 +249,8 @@ PROTOTYPES = {
     "mi355det_coco_iou": (C.c_int, [i32, i64, vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp, i64, i64, vp, vp, vp, vp]),
     "mi355det_coco_match": (C.c_int, [i64, vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
     "mi355det_lvis_match": (C.c_int, [i64, vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
+    "mi355det_coco_oks": (C.c_int, [i64, vp, vp, vp, i64, i64, i64, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "mi355det_keypoints_match": (C.c_int, [i64, vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
     "mi355det_coco_accumulate": (C.c_int, [i32, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp]),
     "mi355det_coco_bootstrap": (C.c_int, [i32, vp, vp, i64, i64, vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp]),
     "mi355det_category_frequencies_workspace": (sz, [i32, i32]),

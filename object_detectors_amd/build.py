@@ -33,6 +33,7 @@ SOURCES = [
     ("rle_string_kernels.hip", []),                      # counts strings to run lengths: integers only, no twin
     ("boundary_kernels.hip", []),                        # mask boundaries from run lengths: integers only, no twin
     ("cocoeval_kernels.hip", ["-ffp-contract=off"]),     # float64 IoU / precision quotients, compared bit for bit: no twin
+    ("oks_kernels.hip", ["-ffp-contract=off"]),          # float64 keypoint similarity, e's quotients and the fixed-order sum as written: no twin
     ("bootstrap_kernels.hip", ["-ffp-contract=off"]),    # the float64 quotients of cocoeval_kernels.hip per replicate, bit for bit: no twin
     ("dstats_kernels.hip", ["-ffp-contract=off"]),       # float64 idf columns in numpy's and Cephes' operation order: no twin
     ("kmeans_kernels.hip", ["-ffp-contract=off"]),       # float64 distances, centre quotients and fixed-order sums, bit for bit: no twin

@@ -1,4 +1,4 @@
-"""COCO evaluation on the device: the twelve COCO statistics for `bbox` and `segm` without pycocotools.
+"""COCO evaluation on the device: the twelve COCO statistics for `bbox` and `segm` and the ten of `keypoints` without pycocotools.
 
 What pycocotools' COCOeval computes with a Python loop over images x categories x area ranges is tens of thousands of small independent
 (image, category) groups; here they are three kernel passes (csrc/cocoeval_kernels.hip, include/mi355det.h "COCO evaluation"):
@@ -14,7 +14,12 @@ What pycocotools' COCOeval computes with a Python loop over images x categories 
 The slot layout evaluate() leaves behind, the detection lists and the accumulate and bootstrap passes are evalcore.py (GroupedEval); here are
 COCO's cut (each group's detections in descending score order, stable, cut to 100), its match rule, the `segm` side and the summary.  The
 LVIS rules (federated annotations, APr / APc / APf) are lviseval.py: another front end and match rule on the same base.
-Out of scope: keypoints / OKS.  Polygon ground truth is converted first: COCOEval(polygons.dataset_to_rle(dataset), "segm").
+Polygon ground truth is converted first: COCOEval(polygons.dataset_to_rle(dataset), "segm").
+
+`keypoints` (COCOEval(gt, "keypoints", sigmas=None)) is the same pipeline with another pair kernel and the two ground-truth
+flags apart: coco_oks (csrc/oks_kernels.hip: the object keypoint similarity in coco_iou's ragged layout) -> keypoints_match -> the unchanged
+coco_accumulate, at maxDets = 20 over the area ranges all / medium / large, summarised in pycocotools' ten lines.  Out of scope for
+`keypoints`: tide.ErrorBreakdown and compare.Disagreement (boxes only), LVIS, and everything in the models and in ingest.
 
 The masks of a `segm` evaluation live in a _MaskStore (also lviseval.LVISSegmEval's).  On a GPU a list of result dicts whose `counts` are
 all strings - a results file - is decoded, checked and measured by csrc/rle_string_kernels.hip in one call (add_strings); every other form
@@ -34,6 +39,16 @@ AREA_LABELS = ["all", "small", "medium", "large"]
 STAT_ROWS = [(1, None, 0, 2), (1, .5, 0, 2), (1, .75, 0, 2), (1, None, 1, 2), (1, None, 2, 2), (1, None, 3, 2),
              (0, None, 0, 0), (0, None, 0, 1), (0, None, 0, 2), (0, None, 1, 2), (0, None, 2, 2), (0, None, 3, 2)]
 STAT_NAMES = ["AP", "AP50", "AP75", "APs", "APm", "APl", "AR1", "AR10", "AR100", "ARs", "ARm", "ARl"]
+# `keypoints`: one maxDets, no small range (pycocotools' Params.setKpParams), ten statistics in the same row form
+KP_MAX_DETS = [20]
+KP_AREA_RNG = [[0, 1e10], [32 ** 2, 96 ** 2], [96 ** 2, 1e10]]
+KP_AREA_LABELS = ["all", "medium", "large"]
+KP_STAT_ROWS = [(1, None, 0, 0), (1, .5, 0, 0), (1, .75, 0, 0), (1, None, 1, 0), (1, None, 2, 0),
+                (0, None, 0, 0), (0, .5, 0, 0), (0, .75, 0, 0), (0, None, 1, 0), (0, None, 2, 0)]
+KP_STAT_NAMES = ["AP", "AP50", "AP75", "APm", "APl", "AR", "AR50", "AR75", "ARm", "ARl"]
+# COCO's per-keypoint standard deviations of the 17 person keypoints (nose, eyes, ears, shoulders, elbows, wrists, hips, knees, ankles)
+KP_SIGMAS = [v / 10 for v in (.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89)]
+KP_MAX_K = 64                             # coco_oks' limit on the keypoints per instance
 
 
 def _segmentation_counts(seg, bitmaps):
@@ -176,19 +191,43 @@ class _MaskStore:
 
 
 class COCOEval(GroupedEval):
-    """COCOeval for `bbox`, `segm` or `boundary` on the device.  `gt`: see load_dataset.  `boundary` (the COCO boundary-IoU API) takes
-    exactly the inputs of `segm` and matches on min(mask IoU, boundary IoU), the boundaries eroded by rle.boundary_dilation(h, w,
-    dilation_ratio); a detection's area and box stay its mask's.  Detections come in through add() (one image, device tensors) or
-    add_results() (COCO result dicts); evaluate(), accumulate() and summarize() then follow pycocotools' protocol."""
-    kind, flag_field, stat_names = "coco", "iscrowd", STAT_NAMES
+    """COCOeval for `bbox`, `segm`, `boundary` or `keypoints` on the device.  `gt`: see load_dataset.  `boundary` (the COCO boundary-IoU
+    API) takes exactly the inputs of `segm` and matches on min(mask IoU, boundary IoU), the boundaries eroded by rle.boundary_dilation(h,
+    w, dilation_ratio); a detection's area and box stay its mask's.  Detections come in through add() (one image, device tensors) or
+    add_results() (COCO result dicts); evaluate(), accumulate() and summarize() then follow pycocotools' protocol.
+
+    `keypoints`: `sigmas` are the K per-keypoint standard deviations (None: COCO's 17 person values, KP_SIGMAS; another length serves
+    another skeleton).  Every annotation that counts (a known image and category) must carry `keypoints`, 3K numbers x, y, v; a data set
+    without any `keypoints` annotation is refused.  A ground truth is ignored when iscrowd or num_keypoints == 0, and only iscrowd lets it
+    match again.  Where `num_keypoints` is missing, the number of keypoints with v > 0 stands in (pycocotools raises a KeyError there).  A
+    detection's area and box are those of loadRes: over all K keypoints, box = [min x, min y, max x - min x, max y - min y], area = w * h."""
+    kind, flag_field = "coco", "iscrowd"
     cuts = property(lambda self: self.max_dets)
 
-    def __init__(self, gt, iou_type="bbox", device=None, dilation_ratio=0.02):
-        if iou_type not in ("bbox",) + MASK_TYPES:
-            raise ValueError(f"COCOEval: iou_type {iou_type!r} is not supported (bbox, segm, boundary; keypoints / OKS are out of scope)")
+    def __init__(self, gt, iou_type="bbox", device=None, dilation_ratio=0.02, sigmas=None):
+        if iou_type not in ("bbox", "keypoints") + MASK_TYPES:
+            raise ValueError(f"COCOEval: iou_type {iou_type!r} is not supported (bbox, segm, boundary, keypoints)")
         boundary_dilation(1, 1, dilation_ratio)                        # refuses a ratio <= 0
         self.dilation_ratio = float(dilation_ratio)
-        super().__init__(gt, iou_type, device, list(MAX_DETS))
+        self.on_keypoints = iou_type == "keypoints"
+        self.stat_rows, self.stat_names, self.area_labels = (KP_STAT_ROWS, KP_STAT_NAMES, KP_AREA_LABELS) if self.on_keypoints else \
+            (STAT_ROWS, STAT_NAMES, AREA_LABELS)
+        if self.on_keypoints:
+            self.sigmas = np.asarray(KP_SIGMAS if sigmas is None else sigmas, np.float64).reshape(-1)
+            if not 1 <= self.sigmas.shape[0] <= KP_MAX_K or not (np.isfinite(self.sigmas).all() and (self.sigmas > 0).all()):
+                raise ValueError(f"COCOEval: sigmas must be 1..{KP_MAX_K} positive numbers, one per keypoint")
+        elif sigmas is not None:
+            raise ValueError("COCOEval: sigmas belong to iou_type 'keypoints'")
+        super().__init__(gt, iou_type, device, list(KP_MAX_DETS if self.on_keypoints else MAX_DETS))
+        if self.on_keypoints:
+            self.area_rng = np.asarray(KP_AREA_RNG, np.float64)
+            if not any("keypoints" in a for a in self.dataset.get("annotations", [])):
+                raise ValueError("COCOEval: keypoints evaluation needs a ground truth with `keypoints` annotations; this data set has none")
+            for j, a in self._anns:
+                kp = a.get("keypoints")
+                if not isinstance(kp, (list, tuple)) or len(kp) != 3 * self.num_keypoints:
+                    raise ValueError(f"COCOEval: annotation {a.get('id', j)!r} (position {j}) must have `keypoints`, a list of "
+                                     f"{3 * self.num_keypoints} numbers (x, y, v of {self.num_keypoints} keypoints)")
         if self.on_masks:
             for _j, a in self._anns:
                 if is_polygon_segmentation(a.get("segmentation")):
@@ -197,22 +236,47 @@ class COCOEval(GroupedEval):
     def reset(self):
         super().reset()
         self._masks = _MaskStore(self.device) if self.on_masks else None
+        self._kp = []                                                  # `keypoints`: float64 [n, K, 2] per addition, on the device
         self.scores = self.stats = None
 
+    num_keypoints = property(lambda self: int(self.sigmas.shape[0]))
+
     # ---- detections
-    def add(self, image_id, category_ids, scores, boxes=None, masks=None):
+    def _xy(self, keypoints, n, what):
+        """[n, K, 3] or [n, K, 2] (also flat) -> x, y as float64 [n, K, 2] on the device; a detection's visibility is dropped."""
+        K = self.num_keypoints
+        kp = (keypoints.to(self.device) if torch.is_tensor(keypoints) else torch.tensor(keypoints, dtype=torch.float64, device=self.device))
+        kp = kp.to(torch.float64)                                    # float32 model outputs are widened exactly; lists are read as float64
+        if kp.numel() not in (n * K * 3, n * K * 2) or (kp.dim() == 3 and kp.shape[1] != K):
+            raise ValueError(f"{what}: keypoints must be [n, {K}, 3] or [n, {K}, 2], one row per detection")
+        return kp.reshape(n, K, 3 if kp.numel() == n * K * 3 else 2)[:, :, :2].contiguous()
+
+    def add(self, image_id, category_ids, scores, boxes=None, masks=None, keypoints=None):
         """GroupedEval.add with, for `segm`, masks in place of boxes: an RLEBatch (MaskRCNN(mask_format="rle")) or dense [n, H, W] /
-        [n, 1, H, W] probabilities (`> 0.5` through ops.mask_rle_dense)."""
+        [n, 1, H, W] probabilities (`> 0.5` through ops.mask_rle_dense); for `keypoints`, keypoints [n, K, 3] or [n, K, 2] (Keypoint
+        R-CNN's output form; x and y are read, a third value is not)."""
+        if self.on_keypoints:
+            if keypoints is None:
+                raise ValueError("COCOEval.add: keypoints evaluation needs keypoints")
+            kp = self._xy(keypoints, int(torch.as_tensor(category_ids).numel()), "COCOEval.add")
         if self.on_masks and masks is not None and not isinstance(masks, RLEBatch):
             masks = ops.mask_rle_dense(torch.as_tensor(masks, device=self.device).to(torch.float32), 0.5)
         self._dets.add("COCOEval.add", image_id, category_ids, scores, boxes, masks)
         if self.on_masks:
             self._masks.add_batch(masks)
+        if self.on_keypoints:
+            self._kp.append(kp)
 
     def add_results(self, results):
-        """COCO result dicts (`image_id`, `category_id`, `score` and `bbox` or `segmentation`), e.g. the rows of to_coco_results."""
+        """COCO result dicts (`image_id`, `category_id`, `score` and `bbox`, `segmentation` or, flat x, y, v of the K keypoints,
+        `keypoints`), e.g. the rows of to_coco_results."""
         if results and self.on_masks:
             self._masks.add_segmentations([r["segmentation"] for r in results])
+        if results and self.on_keypoints:
+            for j, r in enumerate(results):
+                if len(r["keypoints"]) != 3 * self.num_keypoints:
+                    raise ValueError(f"COCOEval.add_results: result {j} must have {3 * self.num_keypoints} keypoint numbers")
+            self._kp.append(self._xy([r["keypoints"] for r in results], len(results), "COCOEval.add_results"))
         super().add_results(results)
 
     def _build_ground_truth(self):
@@ -223,6 +287,16 @@ class COCOEval(GroupedEval):
             gt["counts"], gt["runs"], _area, gt["box"], gt["sizes"] = store.tensors()
             if self.iou_type == "boundary":
                 gt["boundary"] = store.boundaries(self.dilation_ratio)
+        if self.on_keypoints:
+            anns = [self._anns[o][1] for o in gt["order"]]
+            kp = np.asarray([a["keypoints"] for a in anns], np.float64).reshape(-1, self.num_keypoints, 3)
+            labelled = np.asarray([int(a["num_keypoints"]) if "num_keypoints" in a else int((k[:, 2] > 0).sum()) for a, k in zip(anns, kp)],
+                                  np.int64).reshape(-1)
+            gt["flag"] = (gt["crowd"].astype(bool) | (labelled == 0)).astype(np.uint8)       # ignored; gt["crowd"] stays iscrowd alone
+            gt["flag_dev"] = torch.from_numpy(gt["flag"]).to(self.device)
+            gt["kp"] = torch.from_numpy(np.ascontiguousarray(kp)).to(self.device)
+            gt["box"] = torch.from_numpy(np.asarray([a["bbox"] for a in anns], np.float64).reshape(-1, 4)).to(self.device)
+            gt["vars"] = torch.from_numpy((self.sigmas * 2) ** 2).to(self.device)
         return gt
 
     def _group(self):
@@ -241,6 +315,13 @@ class COCOEval(GroupedEval):
         if self.iou_type == "bbox":
             self._rle = None
             return self._layout(key, dt_index, score, box, rank=rank)
+        if self.on_keypoints:                                          # loadRes: area and box over all K keypoints
+            kp = torch.cat(self._kp) if self._kp else torch.zeros((0, self.num_keypoints, 2), dtype=torch.float64, device=self.device)
+            lo, hi = kp.min(1).values, kp.max(1).values
+            wh = hi - lo
+            iou_size = self._layout(key, dt_index, score, torch.cat([lo, wh], 1), wh[:, 0] * wh[:, 1], rank)
+            self.dt_kp, self.gt_kp = kp[dt_index].contiguous(), self._ground_truth()["kp"]
+            return iou_size
         gt = self._ground_truth()
         masks = self._masks.tensors()
         iou_size = self._layout(key, dt_index, score, masks[3], masks[2], rank)
@@ -250,19 +331,26 @@ class COCOEval(GroupedEval):
     def _match(self, iou_size):
         """coco_iou (crowd pairs take the crowd union), then coco_match with iscrowd as the flag."""
         thr, rng, _rec = self._params()
+        if self.on_keypoints:                                          # coco_oks (no crowd rule), then the match with the two flags apart
+            self.iou = ops.coco_oks(self.dt_offsets, self.gt_offsets, self.iou_offsets, iou_size, self.dt_kp, self.gt_kp, self.gt_boxes,
+                                    self.gt_area, self._ground_truth()["vars"])
+            self.dt_match, self.dt_ignore, self.gt_match, self.gt_ignore = ops.keypoints_match(
+                self.dt_offsets, self.gt_offsets, self.iou_offsets, self.iou, self.dt_area, self.gt_area, self.gt_flag, self.gt_crowd, thr, rng)
+            return
         self.iou = self._iou(iou_size)
         self.dt_match, self.dt_ignore, self.gt_match, self.gt_ignore = ops.coco_match(
             self.dt_offsets, self.gt_offsets, self.iou_offsets, self.iou, self.dt_area, self.gt_area, self.gt_flag, thr, rng)
 
     def accumulate(self):
-        """precision [10, 101, K, 4, 3], recall [10, K, 4, 3], scores [10, 101, K, 4, 3] as float64 numpy arrays."""
+        """precision [10, 101, K, 4, 3], recall [10, K, 4, 3], scores [10, 101, K, 4, 3] as float64 numpy arrays (`keypoints`: 3 area
+        ranges and 1 maxDets in place of 4 and 3)."""
         self.precision, self.recall, self.scores = (x.cpu().numpy() for x in self._accumulate())
         return self
 
     def _stat_rows(self, ap_sum, recall):
-        """bootstrap(): the twelve statistics in STAT_ROWS order."""
+        """bootstrap(): the twelve (`keypoints`: ten) statistics in stat_rows order."""
         out = []
-        for ap, thr, a, m in STAT_ROWS:
+        for ap, thr, a, m in self.stat_rows:
             cells = ap_sum if ap else recall
             if thr is not None:
                 cells = cells[:, [int(j) for j in np.flatnonzero(np.isclose(self.iou_thrs, thr))]]
@@ -278,26 +366,26 @@ class COCOEval(GroupedEval):
         return masked_mean(s[:, :, :, area, max_det] if ap else s[:, :, area, max_det])
 
     def summarize(self, file=None):
-        """Prints pycocotools' twelve lines and sets .stats (float64 [12])."""
+        """Prints pycocotools' twelve lines (`keypoints`: its ten, all at maxDets= 20) and sets .stats (float64 [12] or [10])."""
         if self.precision is None:
             raise RuntimeError("COCOEval.summarize: call accumulate() first")
-        stats = np.zeros(12, np.float64)
-        for n, (ap, thr, a, m) in enumerate(STAT_ROWS):
+        stats = np.zeros(len(self.stat_rows), np.float64)
+        for n, (ap, thr, a, m) in enumerate(self.stat_rows):
             stats[n] = self._stat(ap, thr, a, m)
             title, kind = ("Average Precision", "(AP)") if ap else ("Average Recall", "(AR)")
             span = f"{self.iou_thrs[0]:0.2f}:{self.iou_thrs[-1]:0.2f}" if thr is None else f"{thr:0.2f}"
-            print(f" {title:<18} {kind} @[ IoU={span:<9} | area={AREA_LABELS[a]:>6s} | maxDets={self.max_dets[m]:>3d} ] = {stats[n]:0.3f}", file=file)
+            print(f" {title:<18} {kind} @[ IoU={span:<9} | area={self.area_labels[a]:>6s} | maxDets={self.max_dets[m]:>3d} ] = {stats[n]:0.3f}", file=file)
         self.stats = stats
         return stats
 
     def summarize_per_category(self):
-        """The twelve statistics of every category on its own, float64 [K, 12]: row k is what summarize() would give with only cat_ids[k]
+        """The twelve (`keypoints`: ten) statistics of every category on its own, float64 [K, 12]: row k is what summarize() would give with only cat_ids[k]
         evaluated (pycocotools with params.catIds = [cat_ids[k]], which the reference's notebooks/get_map.py:54-60 runs once per category).
         Read out of precision / recall by category: no new pass, nothing printed, .stats untouched."""
         if self.precision is None:
             raise RuntimeError("COCOEval.summarize_per_category: call accumulate() first")
-        out = np.zeros((len(self.cat_ids), 12), np.float64)
+        out = np.zeros((len(self.cat_ids), len(self.stat_rows)), np.float64)
         for k in range(len(self.cat_ids)):
-            for n, (ap, thr, a, m) in enumerate(STAT_ROWS):
+            for n, (ap, thr, a, m) in enumerate(self.stat_rows):
                 out[k, n] = self._stat(ap, thr, a, m, cat=k)
         return out

@@ -212,6 +212,9 @@ def per_category_table(evaluators, metric_columns=(0,)):
     for name, ev in evaluators.items():
         if name == "columns":
             raise ValueError("per_category_table: an experiment cannot be named 'columns'")
+        if getattr(ev, "iou_type", None) == "keypoints":          # ten statistics under other names (COCOEval.stat_names)
+            raise NotImplementedError("per_category_table: the columns are the twelve bbox / segm statistics; for a keypoints evaluator "
+                                      "read summarize_per_category() with its stat_names")
         stats = ev.summarize_per_category()
         table[name] = {STAT_NAMES[c]: [float(v) for v in stats[:, c]] for c in cols}
     return table

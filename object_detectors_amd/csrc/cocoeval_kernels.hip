@@ -10,12 +10,14 @@
 //                           never stored.  The "already matched" state is gt_match itself.
 //                           One body, two rules (template switch): COCO re-matches a taken crowd; LVIS (lvis-api's LVISEval) has no
 //                           crowds, takes the annotation's ignore flag in their place and ignores an unmatched detection of a group whose
-//                           category is not exhaustively annotated in its image.
+//                           category is not exhaustively annotated in its image.  A second switch keeps the two COCO flags apart for
+//                           `keypoints`: the ignore flag (iscrowd or num_keypoints == 0) ignores, iscrowd alone re-matches.
 //   coco_accumulate_kernel  wave = (category, area range, maxDets, threshold): a forward walk over the category's detections in score order
 //                           for the totals, then a backward walk that rebuilds the cumulative sums from the totals (integers: exact), carries
 //                           the running maximum of the precision and lets every detection that raises the recall write the recall thresholds
 //                           it is the first to reach.  No workspace.
 // Compiled with -ffp-contract=off: every quotient and product has to be the one correctly rounded float64 operation of the definition.
+#include "eval_groups.h"
 #include "wave_ops.h"
 
 using namespace mi355;
@@ -67,28 +69,6 @@ __device__ __forceinline__ void rle_overlap(const int* __restrict__ ca, long lon
   }
 }
 
-struct Groups {
-  const long long *dt_off, *gt_off, *iou_off;      // [NG + 1] each, on the device
-  long long num_dt, num_gt, iou_size;              // the last offsets as the host knows them: a group that does not fit is skipped
-};
-
-struct GroupView {
-  long long d0, g0, o;
-  int D, G;
-};
-
-__device__ __forceinline__ bool group_view(const Groups& S, long long grp, GroupView& v) {
-  v.d0 = S.dt_off[grp];
-  v.g0 = S.gt_off[grp];
-  v.o = S.iou_off[grp];
-  const long long d1 = S.dt_off[grp + 1], g1 = S.gt_off[grp + 1];
-  if (v.d0 < 0 || d1 < v.d0 || d1 > S.num_dt || v.g0 < 0 || g1 < v.g0 || g1 > S.num_gt || d1 - v.d0 > INT32_MAX || g1 - v.g0 > INT32_MAX)
-    return false;
-  v.D = (int)(d1 - v.d0);
-  v.G = (int)(g1 - v.g0);
-  return v.o >= 0 && v.o + (long long)v.D * v.G <= S.iou_size;
-}
-
 struct RleSide {
   const int* counts;             // the masks' counts one after the other
   const long long* runs;         // [num_masks + 1]: mask k owns counts[runs[k]:runs[k + 1]]
@@ -125,10 +105,12 @@ __global__ __launch_bounds__(WAVE) void coco_iou_kernel(Groups S, const double* 
 
 // gt_ignore [A, num_gt]; dt_match / dt_ignore [A, T, num_dt]; gt_match [A, T, num_gt] (zeroed by the entry point).  gt_flag [num_gt]: COCO's
 // iscrowd, or (LVIS) the annotation's ignore flag; group_nel [num_groups], read by the LVIS variant only: the group's category is not
-// exhaustively annotated in its image.
-template <bool LVIS>
+// exhaustively annotated in its image.  gt_crowd [num_gt], read by the SPLIT variant only (keypoints): the flag that lets a taken ground
+// truth match again, where gt_flag only ignores; without SPLIT gt_flag is both.
+template <bool LVIS, bool SPLIT>
 __global__ __launch_bounds__(WAVE) void coco_match_kernel(Groups S, const double* __restrict__ iou, const double* __restrict__ dt_area,
                                                           const double* __restrict__ gt_area, const unsigned char* __restrict__ gt_flag,
+                                                          const unsigned char* __restrict__ gt_crowd,
                                                           const unsigned char* __restrict__ group_nel, const double* __restrict__ iou_thrs, int T,
                                                           const double* __restrict__ area_rngs, int A, int* __restrict__ dt_match,
                                                           unsigned char* __restrict__ dt_ignore, int* __restrict__ gt_match,
@@ -149,7 +131,7 @@ __global__ __launch_bounds__(WAVE) void coco_match_kernel(Groups S, const double
   const double lo = area_rngs[2 * a], hi = area_rngs[2 * a + 1];
   const double thr = fmin(iou_thrs[t], 1 - 1e-10);
   const unsigned char* gi = gt_ignore + (size_t)a * S.num_gt + v.g0;
-  const unsigned char* gc = gt_flag + v.g0;
+  const unsigned char* gc = (SPLIT ? gt_crowd : gt_flag) + v.g0;
   int* gm = gt_match + ((size_t)a * T + t) * S.num_gt + v.g0;
   int* dm = dt_match + ((size_t)a * T + t) * S.num_dt + v.d0;
   unsigned char* di = dt_ignore + ((size_t)a * T + t) * S.num_dt + v.d0;
@@ -299,19 +281,11 @@ __global__ __launch_bounds__(WAVE) void coco_accumulate_kernel(int K, const long
   }
 }
 
-int check_groups(const char* what, long long num_groups, const void* dt_off, const void* gt_off, const void* iou_off, long long num_dt,
-                 long long num_gt, long long iou_size) {
-  if (num_groups < 0 || num_dt < 0 || num_gt < 0 || iou_size < 0) return fail(MI355DET_EINVAL, "%s: bad arguments", what);
-  if (num_groups >= (1ll << 31)) return fail(MI355DET_EINVAL, "%s: too many groups", what);
-  if (num_groups > 0 && (!dt_off || !gt_off || !iou_off)) return fail(MI355DET_EINVAL, "%s: missing offsets", what);
-  return MI355DET_OK;
-}
-
-// the two match entry points: `lvis` picks the rule, `group_nel` is read by the LVIS rule only
-int match_entry(const char* what, bool lvis, int64_t num_groups, const int64_t* dt_offsets, const int64_t* gt_offsets, const int64_t* iou_offsets,
+// the three match entry points: `lvis` picks the rule, `group_nel` is read by the LVIS rule only; `split`: gt_crowd is its own array
+int match_entry(const char* what, bool lvis, bool split, int64_t num_groups, const int64_t* dt_offsets, const int64_t* gt_offsets, const int64_t* iou_offsets,
                 int64_t num_dt, int64_t num_gt, int64_t iou_size, const double* iou, const double* dt_area, const double* gt_area,
-                const uint8_t* gt_flag, const uint8_t* group_nel, const double* iou_thrs, int32_t num_thrs, const double* area_rngs,
-                int32_t num_areas, int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore, void* stream) {
+                const uint8_t* gt_flag, const uint8_t* gt_crowd, const uint8_t* group_nel, const double* iou_thrs, int32_t num_thrs,
+                const double* area_rngs, int32_t num_areas, int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore, void* stream) {
   const int st = check_groups(what, num_groups, dt_offsets, gt_offsets, iou_offsets, num_dt, num_gt, iou_size);
   if (st != MI355DET_OK) return st;
   if (num_thrs <= 0 || num_areas <= 0 || (long long)num_thrs * num_areas > WAVE)
@@ -319,19 +293,20 @@ int match_entry(const char* what, bool lvis, int64_t num_groups, const int64_t* 
   if (num_groups == 0) return MI355DET_OK;
   if (!iou_thrs || !area_rngs) return fail(MI355DET_EINVAL, "%s: missing parameters", what);
   if (lvis && !group_nel) return fail(MI355DET_EINVAL, "%s: missing group_not_exhaustive", what);
-  if ((num_dt > 0 && (!dt_area || !dt_match || !dt_ignore)) || (num_gt > 0 && (!gt_area || !gt_flag || !gt_match || !gt_ignore)) ||
+  if ((num_dt > 0 && (!dt_area || !dt_match || !dt_ignore)) || (num_gt > 0 && (!gt_area || !gt_flag || (split && !gt_crowd) || !gt_match || !gt_ignore)) ||
       (iou_size > 0 && !iou))
     return fail(MI355DET_EINVAL, "%s: missing operand", what);
   const size_t cells = (size_t)num_thrs * num_areas;
   if (num_dt > 0 && hipMemsetAsync(dt_match, 0, cells * num_dt * sizeof(int32_t), S(stream)) != hipSuccess) return check_launch(what);
   if (num_gt > 0 && hipMemsetAsync(gt_match, 0, cells * num_gt * sizeof(int32_t), S(stream)) != hipSuccess) return check_launch(what);
   const Groups G{(const long long*)dt_offsets, (const long long*)gt_offsets, (const long long*)iou_offsets, num_dt, num_gt, iou_size};
-  if (lvis)
-    hipLaunchKernelGGL(coco_match_kernel<true>, dim3((unsigned)num_groups), dim3(WAVE), 0, S(stream), G, iou, dt_area, gt_area, gt_flag, group_nel,
-                       iou_thrs, num_thrs, area_rngs, num_areas, dt_match, dt_ignore, gt_match, gt_ignore);
-  else
-    hipLaunchKernelGGL(coco_match_kernel<false>, dim3((unsigned)num_groups), dim3(WAVE), 0, S(stream), G, iou, dt_area, gt_area, gt_flag, group_nel,
-                       iou_thrs, num_thrs, area_rngs, num_areas, dt_match, dt_ignore, gt_match, gt_ignore);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)num_groups), dim3(WAVE), 0, S(stream), G, iou, dt_area, gt_area, gt_flag, gt_crowd, group_nel, iou_thrs,
+                       num_thrs, area_rngs, num_areas, dt_match, dt_ignore, gt_match, gt_ignore);
+  };
+  if (lvis) launch(coco_match_kernel<true, false>);
+  else if (split) launch(coco_match_kernel<false, true>);
+  else launch(coco_match_kernel<false, false>);
   return check_launch(what);
 }
 
@@ -376,8 +351,8 @@ int mi355det_coco_match(int64_t num_groups, const int64_t* dt_offsets, const int
                         int64_t num_gt, int64_t iou_size, const double* iou, const double* dt_area, const double* gt_area,
                         const uint8_t* gt_crowd, const double* iou_thrs, int32_t num_thrs, const double* area_rngs, int32_t num_areas,
                         int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore, void* stream) {
-  return match_entry("coco_match", false, num_groups, dt_offsets, gt_offsets, iou_offsets, num_dt, num_gt, iou_size, iou, dt_area, gt_area,
-                     gt_crowd, nullptr, iou_thrs, num_thrs, area_rngs, num_areas, dt_match, dt_ignore, gt_match, gt_ignore, stream);
+  return match_entry("coco_match", false, false, num_groups, dt_offsets, gt_offsets, iou_offsets, num_dt, num_gt, iou_size, iou, dt_area, gt_area,
+                     gt_crowd, nullptr, nullptr, iou_thrs, num_thrs, area_rngs, num_areas, dt_match, dt_ignore, gt_match, gt_ignore, stream);
 }
 
 int mi355det_lvis_match(int64_t num_groups, const int64_t* dt_offsets, const int64_t* gt_offsets, const int64_t* iou_offsets, int64_t num_dt,
@@ -385,8 +360,17 @@ int mi355det_lvis_match(int64_t num_groups, const int64_t* dt_offsets, const int
                         const uint8_t* gt_flag, const uint8_t* group_not_exhaustive, const double* iou_thrs, int32_t num_thrs,
                         const double* area_rngs, int32_t num_areas, int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore,
                         void* stream) {
-  return match_entry("lvis_match", true, num_groups, dt_offsets, gt_offsets, iou_offsets, num_dt, num_gt, iou_size, iou, dt_area, gt_area,
-                     gt_flag, group_not_exhaustive, iou_thrs, num_thrs, area_rngs, num_areas, dt_match, dt_ignore, gt_match, gt_ignore, stream);
+  return match_entry("lvis_match", true, false, num_groups, dt_offsets, gt_offsets, iou_offsets, num_dt, num_gt, iou_size, iou, dt_area, gt_area,
+                     gt_flag, nullptr, group_not_exhaustive, iou_thrs, num_thrs, area_rngs, num_areas, dt_match, dt_ignore, gt_match, gt_ignore, stream);
+}
+
+int mi355det_keypoints_match(int64_t num_groups, const int64_t* dt_offsets, const int64_t* gt_offsets, const int64_t* iou_offsets, int64_t num_dt,
+                             int64_t num_gt, int64_t iou_size, const double* iou, const double* dt_area, const double* gt_area,
+                             const uint8_t* gt_flag, const uint8_t* gt_crowd, const double* iou_thrs, int32_t num_thrs, const double* area_rngs,
+                             int32_t num_areas, int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore, void* stream) {
+  return match_entry("keypoints_match", false, true, num_groups, dt_offsets, gt_offsets, iou_offsets, num_dt, num_gt, iou_size, iou, dt_area,
+                     gt_area, gt_flag, gt_crowd, nullptr, iou_thrs, num_thrs, area_rngs, num_areas, dt_match, dt_ignore, gt_match, gt_ignore,
+                     stream);
 }
 
 int mi355det_coco_accumulate(int32_t num_cats, const int64_t* cat_dt_offsets, const int64_t* cat_gt_offsets, int64_t num_dt, int64_t num_gt,

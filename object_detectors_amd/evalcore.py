@@ -10,7 +10,8 @@ within a group the detections are in descending score order (stable) and the gro
 detection's position in the order it was added and to the annotation's position in the dataset.  Per detection slot: `dt_score`,
 `dt_boxes` [x, y, w, h], `dt_area`, `dt_image` (image index, int32) and `dt_rank` (rank within the group, int32; all zero where the
 evaluator has no per-group cut).  Per ground-truth slot: `gt_boxes`, `gt_area`, `gt_flag` (uint8: the flag the match rule reads, iscrowd
-or ignore), `gt_crowd` (uint8: what the IoU pass takes as crowd) and `gt_image`.  The match leaves `iou`, `dt_match`, `dt_ignore`
+or ignore), `gt_crowd` (uint8: what the IoU pass takes as crowd) and `gt_image`.  COCOEval with `keypoints` adds `dt_kp` [num_dt, K, 2] and
+`gt_kp` [num_gt, K, 3] (float64), and its `gt_flag` is the ignore flag while `gt_crowd` alone lets a ground truth match again.  The match leaves `iou`, `dt_match`, `dt_ignore`
 [4, 10, num_dt], `gt_match` [4, 10, num_gt] and `gt_ignore` [4, num_gt].  All of them are device tensors but `gt_index` (numpy)."""
 import json
 

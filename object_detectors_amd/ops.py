@@ -1349,6 +1349,35 @@ def lvis_match(dt_offsets, gt_offsets, iou_offsets, iou, dt_area, gt_area, gt_fl
                   [gt_flag, group_not_exhaustive.contiguous()], iou_thrs, area_rngs)
 
 
+def coco_oks(dt_offsets, gt_offsets, iou_offsets, iou_size, dt_kp, gt_kp, gt_boxes, gt_area, vars):
+    """mi355det_coco_oks over ragged groups (the offsets and the output layout of coco_iou): dt_kp float64 [ND, K, 2] (x, y), gt_kp float64
+    [NG, K, 3] (x, y, v), gt_boxes float64 [NG, 4] as [x, y, w, h], gt_area float64 [NG], vars float64 [K] = (2 * sigma)^2 -> the object
+    keypoint similarity, float64 [iou_size]."""
+    _need_device("coco_oks", dt_kp, gt_kp, vars)
+    for name, t in (("dt_kp", dt_kp), ("gt_kp", gt_kp), ("gt_boxes", gt_boxes), ("gt_area", gt_area), ("vars", vars)):
+        if t.dtype != torch.float64 or not t.is_contiguous():
+            raise ValueError(f"coco_oks: {name} must be contiguous float64")
+    K = int(vars.shape[0])
+    nd, ngt = int(dt_kp.shape[0]), int(gt_kp.shape[0])
+    if vars.dim() != 1 or tuple(dt_kp.shape) != (nd, K, 2) or tuple(gt_kp.shape) != (ngt, K, 3) or tuple(gt_boxes.shape) != (ngt, 4) \
+            or tuple(gt_area.shape) != (ngt,):
+        raise ValueError(f"coco_oks: with {K} vars, dt_kp must be [ND, {K}, 2], gt_kp [NG, {K}, 3], gt_boxes [NG, 4] and gt_area [NG]")
+    out = torch.empty(int(iou_size), dtype=torch.float64, device=dt_kp.device)
+    check(lib().mi355det_coco_oks(int(dt_offsets.shape[0]) - 1, ptr(dt_offsets), ptr(gt_offsets), ptr(iou_offsets), nd, ngt, int(iou_size), K,
+                                  ptr(dt_kp), ptr(gt_kp), ptr(gt_boxes), ptr(gt_area), ptr(vars), ptr(out), stream_ptr()), "coco_oks")
+    return out
+
+
+def keypoints_match(dt_offsets, gt_offsets, iou_offsets, oks, dt_area, gt_area, gt_flag, gt_crowd, iou_thrs, area_rngs):
+    """mi355det_keypoints_match (coco_match with the ignore flag gt_flag and the re-match flag gt_crowd apart, both uint8 [NG]) -> the four
+    arrays of coco_match, same layouts."""
+    _need_device("keypoints_match", oks)
+    if gt_flag.dtype != torch.uint8 or gt_crowd.dtype != torch.uint8 or gt_flag.shape != gt_area.shape or gt_crowd.shape != gt_area.shape:
+        raise ValueError("keypoints_match: gt_flag and gt_crowd must be uint8, one flag per ground truth")
+    return _match(lib().mi355det_keypoints_match, "keypoints_match", dt_offsets, gt_offsets, iou_offsets, oks, dt_area, gt_area,
+                  [gt_flag, gt_crowd], iou_thrs, area_rngs)
+
+
 def coco_accumulate(cat_dt_offsets, cat_gt_offsets, order, dt_rank, dt_score, dt_match, dt_ignore, gt_ignore, max_dets, rec_thrs):
     """mi355det_coco_accumulate -> precision [T, R, K, A, M], recall [T, K, A, M], scores [T, R, K, A, M] (float64)."""
     dev = rec_thrs.device

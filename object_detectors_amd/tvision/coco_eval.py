@@ -1,5 +1,5 @@
 """Mirror of torchvision_models/detection/coco_eval.py: the detection-to-COCO formatting (:83-105 prepare_for_coco_detection, :107-140
-prepare_for_coco_segmentation, :169-171 convert_to_xywh) and CocoEvaluator (:20-81), which scores the detections with the device
+prepare_for_coco_segmentation, :142-166 prepare_for_coco_keypoint, :169-171 convert_to_xywh) and CocoEvaluator (:20-81), which scores the detections with the device
 evaluator of object_detectors_amd/cocoeval.py instead of pycocotools."""
 import json
 
@@ -49,6 +49,21 @@ def prepare_for_coco_segmentation(predictions):
     return coco_results
 
 
+def prepare_for_coco_keypoint(predictions):
+    """coco_eval.py:142-166: {image_id: {'scores' [k], 'labels' [k], 'keypoints' [k, K, 3]}} -> list of result dicts with the reference's
+    four fields; 'keypoints' is each detection's flat x, y, v list."""
+    coco_results = []
+    for original_id, prediction in predictions.items():
+        if len(prediction) == 0:
+            continue
+        scores = prediction["scores"].tolist()
+        labels = prediction["labels"].tolist()
+        keypoints = prediction["keypoints"].flatten(start_dim=1).tolist()
+        coco_results.extend([{"image_id": original_id, "category_id": labels[k], "keypoints": keypoint, "score": scores[k]}
+                             for k, keypoint in enumerate(keypoints)])
+    return coco_results
+
+
 class CocoEvaluator:
     """coco_eval.py:20-81 on top of cocoeval.COCOEval.  update() only stores the predictions (tensors stay where they are; dense masks become
     run lengths at once); evaluation runs in accumulate(), over everything stored, so nothing is copied to the host per batch.  The result
@@ -59,13 +74,11 @@ class CocoEvaluator:
         if not isinstance(iou_types, (list, tuple)):
             raise TypeError("CocoEvaluator: iou_types must be a list or tuple")
         for t in iou_types:
-            if t == "keypoints":
-                raise ValueError("CocoEvaluator: keypoints (OKS) evaluation is not supported")
-            if t not in ("bbox", "segm", "boundary"):
+            if t not in ("bbox", "segm", "boundary", "keypoints"):
                 raise ValueError("Unknown iou type {}".format(t))
         self.coco_gt = load_dataset(coco_gt)
         self.iou_types = list(iou_types)
-        self.coco_eval = {t: COCOEval(self.coco_gt, t) for t in self.iou_types}
+        self.coco_eval = {t: COCOEval(self.coco_gt, t) for t in self.iou_types}       # keypoints: refused for a data set without any
         self.img_ids = []
         self.predictions = {}                                  # image id -> its prediction, the first one seen
 
@@ -82,6 +95,8 @@ class CocoEvaluator:
             if "segm" in self.iou_types or "boundary" in self.iou_types:
                 masks = prediction["masks"]
                 kept["masks"] = masks if isinstance(masks, RLEBatch) else mask_rle_dense(masks, 0.5)
+            if "keypoints" in self.iou_types:
+                kept["keypoints"] = prediction["keypoints"].detach()
             self.predictions[image_id] = kept
 
     def synchronize_between_processes(self):
@@ -113,6 +128,8 @@ class CocoEvaluator:
                 dev = ev.device
                 if iou_type == "bbox":
                     ev.add(image_id, p["labels"], p["scores"], boxes=convert_to_xywh(p["boxes"].to(dev)))
+                elif iou_type == "keypoints":
+                    ev.add(image_id, p["labels"], p["scores"], keypoints=p["keypoints"])
                 else:
                     ev.add(image_id, p["labels"], p["scores"], masks=p["masks"])
             ev.evaluate()
@@ -128,6 +145,8 @@ class CocoEvaluator:
             return prepare_for_coco_detection(predictions)
         if iou_type in ("segm", "boundary"):                   # boundary IoU reads the same masks
             return prepare_for_coco_segmentation(predictions)
+        if iou_type == "keypoints":
+            return prepare_for_coco_keypoint(predictions)
         raise ValueError("Unknown iou type {}".format(iou_type))
 
     def save_detections(self, path):
