@@ -1345,6 +1345,48 @@ int mi355det_tide_fixes(int64_t num_images, const int64_t* img_dt_offsets, const
                         const uint8_t* kind, const int64_t* partner, const uint8_t* missed, int32_t* fix_dt_match, uint8_t* fix_dt_ignore,
                         uint8_t* fix_gt_ignore, int32_t* cls_cat, int32_t* cls_match, uint8_t* cls_ignore, void* stream);
 
+/* ---- Weighted boxes fusion (csrc/fusion_kernels.hip): two or more result sets, or several passes of one model, merged into one by
+ * weighted boxes fusion (Solovyev, Wang, Gabruseva 2021).  The rule below is stated from the paper and from memory of its authors' package
+ * `ensemble-boxes`, with three stated deviations; it was not run against that package.  The front end (object_detectors_amd/ensemble.py)
+ * makes the candidates and the groups; the entry point clusters every group in one launch.
+ * The rule (float64 throughout, no contraction, IEEE division).
+ *   Inputs.  M >= 1 result sets, model m with weight w_m > 0; iou_thr in [0, 1) (default 0.55), skip_box_thr (default 0), conf_type avg or
+ *     max.  W = w_0 + .. + w_{M-1} summed in that order, wmax = the largest weight.
+ *   Candidates.  A detection (image, category, score s, box [x, y, w, h]) of model m becomes a candidate with s' = s * w_m and the corners
+ *     x1 = x, y1 = y, x2 = x + w, y2 = y + h.  It is dropped, for the first reason that holds, when its image is unknown; s < skip_box_thr;
+ *     s' is not finite or s' <= 0 (deviation 1: the package keeps a zero score and divides by it); x, y, w, h, x2 or y2 is not finite;
+ *     w <= 0 or h <= 0.
+ *   Groups and order.  A group is one (image, category) pair; its candidates stand in descending s', ties by model index, then by the order
+ *     added: a stable sort over the model-major concatenation (deviation 2: the package's argsort is reversed and unstable).
+ *   Clustering.  A group starts without clusters.  A cluster keeps its member count n, the sums S1..S4 and C, the maximum mx and its fused box
+ *     F = (X1, Y1, X2, Y2).  For each candidate b in order and every cluster in creation order: iw = min(X2, b.x2) - max(X1, b.x1), iw <= 0
+ *     gives the overlap 0, ih likewise in y, i = iw * ih, v = i / ((X2 - X1) * (Y2 - Y1) + (b.x2 - b.x1) * (b.y2 - b.y1) - i).  The cluster
+ *     with the largest v is taken, the first made among equals.  v > iou_thr (strict): b joins it, n += 1, S_k = S_k + s' * coordinate_k (the
+ *     product rounded first), C = C + s', mx = max(mx, s'), F_k = S_k / C.  Otherwise b founds a cluster: n = 1, S_k = s' * coordinate_k,
+ *     C = mx = s' and F = the box itself, not S_k / C ((s' * x) / s' is not x for about one coordinate in ten).
+ *   Scores, after the group's last candidate.  avg: score = ((C / n) * min(n, W)) / W with n as a double; max: score = mx / wmax
+ *     (deviation 3: the package's box_and_model_avg, absent_model_aware_avg and allows_overflow are not provided).
+ *   Result.  One detection per cluster: the group's image and category, the score, the box [X1, Y1, X2 - X1, Y2 - Y1] and members = n.
+ * The entry point.  group_offsets [num_groups + 1] int64 ON THE DEVICE: group j owns the slots group_offsets[j]..group_offsets[j + 1] of
+ *   boxes float64 [num_boxes, 4] (corners x1, y1, x2, y2) and scores float64 [num_boxes] (s'), both in fusion order; a slot no group owns is
+ *   neither read nor written, and an empty group costs nothing.  num_groups and num_boxes are the caller's host copies: they size the arrays,
+ *   a group whose offsets do not fit num_boxes is skipped, nothing is read or written past them; a group has no size cap.
+ *   conf_type 0 = avg, 1 = max; weight_sum = W, weight_max = wmax.
+ *   A cluster is identified with the slot of its founder.  Outputs, every array with num_boxes leading entries: leader int64 (per candidate:
+ *   the founder slot of the cluster it ended in, its own slot for a founder) and founders int64 (row group_offsets[j] + c: the founder slot of
+ *   group j's cluster c, creation order; the other rows of a group are not written); written AT FOUNDER SLOTS ONLY: sums float64 [*, 6]
+ *   (S1..S4, C, mx), fused float64 [*, 4] (F as corners), out_scores float64 and members int32.  The caller finds the founders by
+ *   leader[slot] == slot (after filling leader with -1 where slots may belong to no group) and compacts them; there is no count pass.
+ * One wavefront per group, cluster c of a group always on lane c % 64; the fused boxes of a group's first mi355det_wbf_lds_clusters()
+ * clusters are cached in LDS, the others are read back from `fused`.  Only the cluster that changed is re-divided.  No atomics, every element
+ * has one writer, so the output is bit-identical from run to run.  No workspace.  MI355DET_EINVAL before any launch for a negative size, for
+ * iou_thr outside [0, 1) or NaN, an unknown conf_type, weight_sum or weight_max not positive and finite, and for a missing operand with
+ * num_boxes > 0; no launch when there are no groups or no boxes. */
+int mi355det_wbf_lds_clusters(void);
+int mi355det_wbf_fuse(const int64_t* group_offsets, int64_t num_groups, int64_t num_boxes, const double* boxes, const double* scores,
+                      double iou_thr, int32_t conf_type, double weight_sum, double weight_max, int64_t* leader, int64_t* founders, double* sums,
+                      double* fused, double* out_scores, int32_t* members, void* stream);
+
 /* layout / dtype converters at the module boundary */
 int mi355det_nhwc_to_nchw_f32(const void* x, int x_is_bf16, int32_t x_ld, int32_t n, int32_t c, int32_t h,
                               int32_t w, float* out, void* stream);

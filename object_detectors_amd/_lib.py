@@ -267,6 +267,8 @@ PROTOTYPES = {
     "mi355det_box_disagreement": (C.c_int, [i64, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, C.c_double, vp, vp, vp, vp]),
     "mi355det_tide_classify": (C.c_int, [i64, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]),
     "mi355det_tide_fixes": (C.c_int, [i64, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "mi355det_wbf_lds_clusters": (C.c_int, []),
+    "mi355det_wbf_fuse": (C.c_int, [vp, i64, i64, vp, vp, C.c_double, i32, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp, vp]),
 }
 
 def _f16_twins():

@@ -1549,3 +1549,39 @@ def tide_fixes(view, dt_match, dt_ignore, dt_cat, gt_cat, gt_counted, gt_free, k
                                     ptr(partner), ptr(missed), ptr(fix_dt_match), ptr(fix_dt_ignore), ptr(fix_gt_ignore), ptr(cls_cat),
                                     ptr(cls_match), ptr(cls_ignore), stream_ptr()), what)
     return fix_dt_match, fix_dt_ignore, fix_gt_ignore, cls_cat, cls_match, cls_ignore
+
+
+# ---- weighted boxes fusion (csrc/fusion_kernels.hip; the front end on top of it is object_detectors_amd/ensemble.py)
+WBF_CONF_TYPES = {"avg": 0, "max": 1}
+
+
+def wbf_lds_clusters():
+    """The number of a group's clusters whose fused boxes mi355det_wbf_fuse keeps in LDS; later clusters go through global memory."""
+    return int(lib().mi355det_wbf_lds_clusters())
+
+
+def wbf_fuse(group_offsets, boxes, scores, iou_thr=0.55, conf_type="avg", weight_sum=1.0, weight_max=1.0):
+    """mi355det_wbf_fuse: group_offsets int64 [G + 1], boxes float64 [N, 4] as corners and scores float64 [N] (the weighted scores), both in
+    fusion order, all on the device -> leader int64 [N] (the founder slot of each candidate's cluster; -1 for a slot no group owns), fused
+    float64 [N, 4] (corners), score float64 [N], members int32 [N] and sums float64 [N, 6] (S1..S4, C, mx), the last four written at founder
+    slots (leader[slot] == slot) only."""
+    what = "wbf_fuse"
+    _need_device(what, group_offsets, boxes, scores)
+    if conf_type not in WBF_CONF_TYPES:
+        raise ValueError(f"{what}: conf_type must be one of {sorted(WBF_CONF_TYPES)}, not {conf_type!r}")
+    dev = boxes.device
+    group_offsets = group_offsets.to(torch.int64).contiguous()
+    boxes, scores = _f64c(boxes, dev).reshape(-1, 4), _f64c(scores, dev).reshape(-1)
+    G, N = int(group_offsets.shape[0]) - 1, int(boxes.shape[0])
+    if G < 0 or int(scores.shape[0]) != N:
+        raise ValueError(f"{what}: group_offsets must hold G + 1 entries and every box one score")
+    leader = torch.full((N,), -1, dtype=torch.int64, device=dev)
+    founders = torch.empty(N, dtype=torch.int64, device=dev)
+    sums = torch.empty((N, 6), dtype=torch.float64, device=dev)
+    fused = torch.empty((N, 4), dtype=torch.float64, device=dev)
+    score = torch.empty(N, dtype=torch.float64, device=dev)
+    members = torch.empty(N, dtype=torch.int32, device=dev)
+    check(lib().mi355det_wbf_fuse(ptr(group_offsets), G, N, ptr(boxes), ptr(scores), float(iou_thr), WBF_CONF_TYPES[conf_type], float(weight_sum),
+                                  float(weight_max), ptr(leader), ptr(founders), ptr(sums), ptr(fused), ptr(score), ptr(members), stream_ptr()),
+          what)
+    return leader, fused, score, members, sums

@@ -5,7 +5,9 @@
         --iou_threshold 0.5 --confidence 0.0 --alpha 0.05 --metric_columns 0 1 --table per_category.json
 The first result file is the baseline (model 0, "Correct1" in the table).  No plots.
 --bootstrap B [--seed S] [--lvis] adds a last block: is the difference in AP more than noise?  Percentile intervals of AP, AP50
-and AP75 per model over B resamples of the images (all replicates in one kernel: COCOEval.bootstrap) and the paired difference with its p."""
+and AP75 per model over B resamples of the images (all replicates in one kernel: COCOEval.bootstrap) and the paired difference with its p.
+--fuse adds a last block: what the two models score together - the statistics of A, B and their weighted boxes fusion at default parameters
+side by side (under --lvis the LVIS statistics; tools/fuse_models.py takes more than two files, weights and the other parameters)."""
 import argparse
 import json
 import os
@@ -31,6 +33,7 @@ def main(argv=None):
                     help="add a block with bootstrap intervals of AP / AP50 / AP75 per model and their paired difference over B resamples of the images")
     ap.add_argument("--seed", type=int, default=0, help="seed of the resamples")
     ap.add_argument("--lvis", action="store_true", help="the bootstrap block under the LVIS rules (an LVIS ground truth; adds APr / APc / APf)")
+    ap.add_argument("--fuse", action="store_true", help="add a block with the statistics of A, B and their weighted boxes fusion side by side")
     args = ap.parse_args(argv)
 
     import torch
@@ -74,6 +77,18 @@ def main(argv=None):
     d.report(alpha=args.alpha)
     if args.bootstrap:
         bootstrap_block(args, dataset, results, names, evaluators, dev)
+    if args.fuse:
+        fuse_block(args, dataset, results, names, dev)
+
+
+def fuse_block(args, dataset, results, names, dev):
+    """The statistics of both models and of their weighted boxes fusion (default parameters, equal weights) side by side."""
+    from object_detectors_amd import ensemble
+    columns = [n + "_" + str(k) for k, n in enumerate(names)] if "fusion" in names else names
+    stat_names, table, fusion = ensemble.evaluate_with_fusion(dataset, results, columns, lvis=args.lvis, device=dev)
+    print(f"== fusion: weighted boxes fusion of {names}, iou_thr {fusion.iou_thr}, conf_type {fusion.conf_type}, equal weights: "
+          f"{int(fusion.result['score'].shape[0])} fused detections{' (LVIS rules)' if args.lvis else ''}")
+    ensemble.print_stats_table(stat_names, table)
 
 
 def bootstrap_block(args, dataset, results, names, evaluators, dev):
