@@ -1387,6 +1387,39 @@ int mi355det_wbf_fuse(const int64_t* group_offsets, int64_t num_groups, int64_t 
                       double iou_thr, int32_t conf_type, double weight_sum, double weight_max, int64_t* leader, int64_t* founders, double* sums,
                       double* fused, double* out_scores, int32_t* members, void* stream);
 
+/* ---- Pooled precision-recall (csrc/pooled_kernels.hip): AP-pool of Dave et al., "Evaluating Large-Vocabulary Object Detectors: The Devil
+ * is in the Details" (2021) - all categories' detections ranked in one list, one precision-recall curve - on the match arrays of the "COCO
+ * evaluation" block above.  The paper's fork of lvis-api is not installed where this was written: the rules below are restated from memory
+ * of the paper and of that fork, and the tests compare against a literal host form of this text.
+ *   Pools.  A pool is a set of categories; its list is every detection slot of those categories that survives the evaluator's largest cut, in
+ *     descending dt_score, stable over the slot index.  The caller builds the lists (a mask and a stable sort) and concatenates them:
+ *     pool_order [num_order] int64, pool s owns pool_offsets[s]..pool_offsets[s + 1] (int64 [num_pools + 1] ON THE DEVICE;
+ *     pool_offsets_host is the caller's HOST copy of the same table: it sizes the launches, the one host read of the caller).  An entry of
+ *     pool_order outside 0..num_dt - 1 keeps its position and counts as ignored.  pool_npig [num_pools, num_areas] int64 on the device: the
+ *     pool's ground truths with gt_ignore[a] == 0, summed by the caller.
+ *   Per (pool s, area range a, threshold t), walking the list: tp counts the slots with dt_match != 0 and dt_ignore == 0, fp those with
+ *     dt_match == 0 and dt_ignore == 0 (dt_match, dt_ignore [num_areas, num_thrs, num_dt] as the match entries write them); rc = tp / npig;
+ *     pr = tp / (fp + tp + 2^-52), made non-increasing from the right; precision / scores [num_thrs, num_recs, num_pools, num_areas] = pr and
+ *     dt_score at the first position with rc >= rec_thrs[r], 0 past the end; recall [num_thrs, num_pools, num_areas] = the last rc, 0 for an
+ *     empty list; everything -1 where npig == 0.  These are coco_accumulate's expressions in float64 without contraction: a pool equals
+ *     coco_accumulate on a single category that holds the pool's slots, bit for bit.
+ *   How.  The list is cut into tiles of mi355det_pooled_tile() positions, one wavefront per tile and pass; the phases are separate launches
+ *     and no kernel waits on another workgroup.  One gather pass packs each position's flags into a 64-bit tp mask and a 64-bit fp mask (bit
+ *     a * num_thrs + t) and leaves the tile totals; their scan, the tiles' largest precision and its maximum over the later tiles are small
+ *     tables between launches; the last pass lets every true positive write the thresholds it is the first to reach.  No atomics, one writer
+ *     per output element, 64-bit positions: bit-identical from run to run.
+ *   workspace: mi355det_pooled_accumulate_workspace(num_order, num_pools, num_thrs, num_areas) bytes on the device (0 for arguments the
+ *     entry refuses), 16-byte aligned; its contents mean nothing to the caller.
+ * MI355DET_EINVAL before any launch for a negative size; num_pools, num_thrs, num_areas or num_recs <= 0; num_thrs * num_areas > 64;
+ * num_recs > 4096; a missing operand; host offsets that decrease, start below 0 or end past num_order; a workspace that is too small.  With
+ * num_order == 0 the call writes the 0 / -1 cells and returns. */
+int mi355det_pooled_tile(void);
+size_t mi355det_pooled_accumulate_workspace(int64_t num_order, int32_t num_pools, int32_t num_thrs, int32_t num_areas);
+int mi355det_pooled_accumulate(const int64_t* pool_order, int64_t num_order, const int64_t* pool_offsets, const int64_t* pool_offsets_host,
+                               int32_t num_pools, const int64_t* pool_npig, int64_t num_dt, const double* dt_score, const int32_t* dt_match,
+                               const uint8_t* dt_ignore, int32_t num_thrs, int32_t num_areas, const double* rec_thrs, int32_t num_recs,
+                               double* precision, double* recall, double* scores, void* workspace, size_t workspace_bytes, void* stream);
+
 /* layout / dtype converters at the module boundary */
 int mi355det_nhwc_to_nchw_f32(const void* x, int x_is_bf16, int32_t x_ld, int32_t n, int32_t c, int32_t h,
                               int32_t w, float* out, void* stream);

@@ -269,6 +269,9 @@ PROTOTYPES = {
     "mi355det_tide_fixes": (C.c_int, [i64, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "mi355det_wbf_lds_clusters": (C.c_int, []),
     "mi355det_wbf_fuse": (C.c_int, [vp, i64, i64, vp, vp, C.c_double, i32, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp, vp]),
+    "mi355det_pooled_tile": (C.c_int, []),
+    "mi355det_pooled_accumulate_workspace": (sz, [i64, i32, i32, i32]),
+    "mi355det_pooled_accumulate": (C.c_int, [vp, i64, vp, vp, i32, vp, i64, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, sz, vp]),
 }
 
 def _f16_twins():

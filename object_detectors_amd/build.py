@@ -41,6 +41,7 @@ SOURCES = [
     ("compare_kernels.hip", ["-ffp-contract=off"]),      # float64 box IoU and its arg-max, compared bit for bit: no twin
     ("tide_kernels.hip", ["-ffp-contract=off"]),         # the float64 overlap of cocoeval_kernels.hip across categories, bit for bit: no twin
     ("fusion_kernels.hip", ["-ffp-contract=off"]),       # float64 weighted boxes fusion, s' * x rounded before the sum, bit for bit: no twin
+    ("pooled_kernels.hip", ["-ffp-contract=off"]),       # the float64 precision quotients of cocoeval_kernels.hip on pooled lists, bit for bit: no twin
     ("resnet_kernels.hip", []),
     ("conv_kernels.hip", []),
     ("igemm8_kernels.hip", []),

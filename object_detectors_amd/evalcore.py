@@ -298,7 +298,7 @@ class GroupedEval:
     def reset(self):
         """Forget the detections (the ground truth stays)."""
         self._dets = DetectionStore(self.device, self.img_ids, self._img_index, self.iou_type == "bbox", self.on_masks)
-        self.precision = self.recall = self.iou = None
+        self.precision = self.recall = self.iou = self.precision_pool = None
 
     num_added = property(lambda self: self._dets.num_added)
     on_masks = property(lambda self: self.iou_type in MASK_TYPES)
@@ -399,6 +399,73 @@ class GroupedEval:
         self.order = category_order(self.cat_dt_offsets, self.dt_score)
         return ops.coco_accumulate(self.cat_dt_offsets, self.cat_gt_offsets, self.order, self.dt_rank, self.dt_score, self.dt_match,
                                    self.dt_ignore, self.gt_ignore, self.cuts, self._params()[2])
+
+    # ---- AP-pool (csrc/pooled_kernels.hip; include/mi355det.h, "Pooled precision-recall")
+    area_labels = ("all", "small", "medium", "large")
+
+    def default_pools(self):
+        """[(name, category indices)]: the pools accumulate_pooled() draws without arguments; a name is the suffix of the pool's key."""
+        return [("", list(range(len(self.cat_ids))))]
+
+    def pool_lists(self, pools):
+        """The operands of ops.pooled_accumulate for `pools` (lists of category indices): pool_order int64 [P], pool_offsets int64 [S + 1]
+        and pool_npig int64 [S, A] on the device.  A pool's list: the slots of its categories with dt_rank below the largest cut, in
+        descending score, stable over the slot index (torch masks and sorts: plumbing)."""
+        dev, K = self.device, len(self.cat_ids)
+        cat_of_dt = torch.searchsorted(self.cat_dt_offsets, torch.arange(self.num_dt, device=dev), right=True) - 1
+        cat_of_gt = torch.searchsorted(self.cat_gt_offsets, torch.arange(self.num_gt, device=dev), right=True) - 1
+        kept = self.dt_rank < max(self.cuts)
+        by_score = torch.sort(-self.dt_score, stable=True).indices            # one sort serves every pool: a subsequence of it stays sorted
+        orders, npig = [], []
+        for cats in pools:
+            cats = np.asarray(cats, np.int64).reshape(-1)
+            if cats.size and (cats.min() < 0 or cats.max() >= K):
+                raise ValueError(f"{self.name}.accumulate_pooled: a pool holds category indices 0..{K - 1}")
+            inside = torch.zeros(K + 1, dtype=torch.bool, device=dev)
+            inside[torch.from_numpy(cats).to(dev)] = True
+            orders.append(by_score[(inside[cat_of_dt] & kept)[by_score]])
+            npig.append(((self.gt_ignore == 0) & inside[cat_of_gt][None, :]).sum(1))
+        host_offsets = np.cumsum([0] + [int(o.shape[0]) for o in orders]).astype(np.int64)       # the masks above sized the lists on the host
+        return torch.cat(orders).contiguous(), torch.from_numpy(host_offsets).to(dev), torch.stack(npig).contiguous(), host_offsets
+
+    def accumulate_pooled(self, pools=None):
+        """AP-pool: one precision-recall curve per pool of categories, every category's detections ranked in one list.  `pools`: lists of
+        category indices (None: default_pools()).  Sets precision_pool and scores_pool [T, R, S, A] and recall_pool [T, S, A], float64 numpy.
+        Needs evaluate() only, and leaves precision, recall and the results of accumulate() as they are."""
+        if self.iou is None:
+            raise RuntimeError(f"{self.name}.accumulate_pooled: call evaluate() first")
+        named = self.default_pools() if pools is None else [(f"[{j}]", p) for j, p in enumerate(pools)]
+        if not named:
+            raise ValueError(f"{self.name}.accumulate_pooled: no pools")
+        self.pool_names = [n for n, _p in named]
+        order, offsets, npig, host_offsets = self.pool_lists([p for _n, p in named])
+        p, r, s = ops.pooled_accumulate(order, offsets, npig, self.dt_score, self.dt_match, self.dt_ignore, self._params()[2], host_offsets)
+        self.precision_pool, self.recall_pool, self.scores_pool = p.cpu().numpy(), r.cpu().numpy(), s.cpu().numpy()
+        return self
+
+    def summarize_pooled(self):
+        """-> an ordered dict: APpool, APpool50, APpool75, one APpool<s|m|l> per area range after the first and ARpool over the first pool,
+        then APpool<name> for every further pool; each the masked_mean of its cells."""
+        from collections import OrderedDict
+        if getattr(self, "precision_pool", None) is None:
+            raise RuntimeError(f"{self.name}.summarize_pooled: call accumulate_pooled() first")
+        pr, rc = self.precision_pool, self.recall_pool
+        at = lambda thr: np.isclose(self.iou_thrs, thr)
+        res = OrderedDict()
+        res["APpool"], res["APpool50"], res["APpool75"] = masked_mean(pr[:, :, 0, 0]), masked_mean(pr[at(.5)][:, :, 0, 0]), masked_mean(pr[at(.75)][:, :, 0, 0])
+        for a in range(1, pr.shape[3]):
+            res["APpool" + self.area_labels[a][0]] = masked_mean(pr[:, :, 0, a])
+        for s in range(1, pr.shape[2]):
+            res["APpool" + self.pool_names[s]] = masked_mean(pr[:, :, s, 0])
+        res["ARpool"] = masked_mean(rc[:, 0, 0])
+        self.results_pool = res
+        return res
+
+    def print_pooled(self, file=None):
+        """One line per key of summarize_pooled()."""
+        import sys
+        for key, value in self.summarize_pooled().items():
+            print(f" {key:<10} = {value:0.3f}", file=sys.stdout if file is None else file)
 
     def bootstrap(self, weights, return_cells=False, cell_budget_bytes=1 << 30):
         """The statistics of resampled data sets, float64 numpy [B, len(stat_names)].  `weights`: integers [B, len(img_ids)] (numpy or tensor,

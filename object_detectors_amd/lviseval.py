@@ -15,6 +15,13 @@ walk with a compile-time switch):
 
 After evaluate() there is no per-group cut (`dt_rank` is zero), and `group_not_exhaustive` [groups] uint8 joins the slot layout.
 
+The 2021 protocol (Dave et al., "Evaluating Large-Vocabulary Object Detectors: The Devil is in the Details"; restated from memory of the paper
+and of its fork of lvis-api, which is not installed): `max_dets=None` (or -1) drops the per-image cut, `max_dets_per_cat=K` keeps each
+category id's K best detections of the whole data set and is applied first; `LVISEval.fixed(gt, dt)` is AP-fixed, `max_dets=None,
+max_dets_per_cat=10000`.  The keys and printed rows then read `AR@-1` (lvis-api's f-string) and `stat_names` belongs to the instance.
+AP-pool - one precision-recall curve over all categories' detections, and one each over the rare, common and frequent ones - is
+`accumulate_pooled()` / `summarize_pooled()` / `print_pooled()` of evalcore.GroupedEval (csrc/pooled_kernels.hip), after evaluate().
+
 LVISEval is `bbox`; `segm` (lvis-api's `LVISEval(gt, results, 'segm')`) is LVISSegmEval below: the same cut, filter, match, accumulate and
 statistics over masks.  What differs, as in lvis-api: a result's area is its mask's set pixels and its box the mask's tight box
 (LVISResults), the IoU is maskUtils.iou of the run lengths with an all-zero iscrowd, and the ground truth's polygons become run lengths
@@ -33,6 +40,7 @@ from .polygons import is_polygon_segmentation, segmentations_to_rle
 from .rle import RLEBatch, boundary_dilation
 
 MAX_DETS = 300
+FIXED_DETS_PER_CAT = 10000                # AP-fixed (Dave et al. 2021): each category's best detections over the whole data set
 RESULT_KEYS = ("AP", "AP50", "AP75", "APs", "APm", "APl", "APr", "APc", "APf", "AR@300", "ARs@300", "ARm@300", "ARl@300")
 
 
@@ -42,13 +50,32 @@ class LVISEval(GroupedEval):
     summarize(); get_results() / print_results() as in lvis-api."""
     kind, flag_field, stat_names, cuts = "lvis", "ignore", RESULT_KEYS, [NO_CUT]
 
-    def __init__(self, lvis_gt, lvis_dt=None, iou_type="bbox", device=None):
+    def __init__(self, lvis_gt, lvis_dt=None, iou_type="bbox", device=None, max_dets=MAX_DETS, max_dets_per_cat=None):
         if iou_type != "bbox":
             raise NotImplementedError(f"LVISEval: iou_type {iou_type!r}: only bbox is evaluated here (for segm and boundary: LVISSegmEval(lvis_gt, lvis_dt, iou_type=...))")
+        self._set_cuts(max_dets, max_dets_per_cat)
         self._setup(lvis_gt, lvis_dt, iou_type, device)
 
+    @classmethod
+    def fixed(cls, lvis_gt, lvis_dt=None, **kw):
+        """The evaluator under the 2021 protocol (AP-fixed): no per-image cut, every category's 10 000 best detections of the data set."""
+        return cls(lvis_gt, lvis_dt, max_dets=None, max_dets_per_cat=FIXED_DETS_PER_CAT, **kw)
+
+    def _set_cuts(self, max_dets, max_dets_per_cat):
+        """max_dets: the per-image cut, None or -1 for none (kept as -1, the number lvis-api's keys print); max_dets_per_cat: None or the
+        per-category cut over the whole data set, applied first."""
+        is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+        max_dets = -1 if max_dets is None else max_dets
+        if not is_int(max_dets) or max_dets == 0 or max_dets < -1:
+            raise ValueError(f"{type(self).__name__}: max_dets must be a positive integer, or None / -1 for no per-image cut, not {max_dets!r}")
+        if max_dets_per_cat is not None and (not is_int(max_dets_per_cat) or max_dets_per_cat <= 0):
+            raise ValueError(f"{type(self).__name__}: max_dets_per_cat must be None or a positive integer, not {max_dets_per_cat!r}")
+        self.max_dets = int(max_dets)
+        self.max_dets_per_cat = None if max_dets_per_cat is None else int(max_dets_per_cat)
+        self.stat_names = tuple(k.replace("@300", f"@{self.max_dets}") for k in RESULT_KEYS)
+
     def _setup(self, lvis_gt, lvis_dt, iou_type, device):
-        GroupedEval.__init__(self, lvis_gt, iou_type, device, MAX_DETS)
+        GroupedEval.__init__(self, lvis_gt, iou_type, device, self.max_dets)
         for im in self.dataset["images"]:
             for field in ("neg_category_ids", "not_exhaustive_category_ids"):
                 if field not in im:
@@ -93,10 +120,15 @@ class LVISEval(GroupedEval):
         area = None
         if masks is not None:
             box, area = masks[3], masks[2]
-        # the cut: descending score (stable), then by image (stable): each image's detections of all categories in score order; rank < 300
+        # the cut: descending score (stable), then by image (stable): each image's detections of all categories in score order; rank < max_dets
         src = torch.nonzero(img >= 0).reshape(-1)
+        if self.max_dets_per_cat is not None:
+            # the category cut comes first: per category id (known or not) the best of the whole data set, back in the order added
+            o = src[score_then_key_order(score[src], cat_id[src])]
+            src = torch.sort(o[rank_in_run(cat_id[o]) < self.max_dets_per_cat]).values
         sel = src[score_then_key_order(score[src], img[src])]
-        sel = sel[rank_in_run(img[sel]) < self.max_dets]
+        if self.max_dets >= 0:
+            sel = sel[rank_in_run(img[sel]) < self.max_dets]
         # the federated filter, after the cut: known category, and (category, image) among the positive or negative keys
         cat, known = lookup(torch.tensor(self.cat_ids, dtype=torch.int64, device=self.device), cat_id[sel])
         key = cat * I + img[sel]
@@ -123,6 +155,10 @@ class LVISEval(GroupedEval):
         self.dt_match, self.dt_ignore, self.gt_match, self.gt_ignore = ops.lvis_match(
             self.dt_offsets, self.gt_offsets, self.iou_offsets, self.iou, self.dt_area, self.gt_area, self.gt_flag, self.group_not_exhaustive,
             thr, rng)
+
+    def default_pools(self):
+        """AP-pool: all categories, then the rare, the common and the frequent ones."""
+        return super().default_pools() + list(zip(("r", "c", "f"), self.freq_groups))
 
     def accumulate(self):
         """precision [10, 101, K, 4], recall [10, K, 4] as float64 numpy arrays."""
@@ -154,9 +190,9 @@ class LVISEval(GroupedEval):
         res["AP"], res["AP50"], res["AP75"] = self._stat(1), self._stat(1, .5), self._stat(1, .75)
         res["APs"], res["APm"], res["APl"] = (self._stat(1, area=a) for a in (1, 2, 3))
         res["APr"], res["APc"], res["APf"] = (self._stat(1, cats=c) for c in self.freq_groups)
-        res["AR@300"] = self._stat(0)
-        res["ARs@300"], res["ARm@300"], res["ARl@300"] = (self._stat(0, area=a) for a in (1, 2, 3))
-        assert tuple(res) == RESULT_KEYS
+        for key, a in zip(self.stat_names[9:], (0, 1, 2, 3)):
+            res[key] = self._stat(0, area=a)
+        assert tuple(res) == self.stat_names
         self.results = res
         return res
 
@@ -177,7 +213,7 @@ class LVISEval(GroupedEval):
         span = f"{self.iou_thrs[0]:0.2f}:{self.iou_thrs[-1]:0.2f}"
         rows = {"AP50": ("0.50", "all", "all"), "AP75": ("0.75", "all", "all"), "APs": (span, "s", "all"), "APm": (span, "m", "all"),
                 "APl": (span, "l", "all"), "APr": (span, "all", "r"), "APc": (span, "all", "c"), "APf": (span, "all", "f"),
-                "ARs@300": (span, "s", "all"), "ARm@300": (span, "m", "all"), "ARl@300": (span, "l", "all")}
+                self.stat_names[10]: (span, "s", "all"), self.stat_names[11]: (span, "m", "all"), self.stat_names[12]: (span, "l", "all")}
         for key, value in self.get_results().items():
             title, kind = ("Average Precision", "(AP)") if key.startswith("AP") else ("Average Recall", "(AR)")
             iou, area, cats = rows.get(key, (span, "all", "all"))
@@ -193,11 +229,12 @@ class LVISSegmEval(LVISEval):
     iou_type="boundary" is lvis-api's `LVISEval(lvis_gt, lvis_dt, 'boundary')`, Boundary AP: the same inputs and rules, matched on
     min(mask IoU, boundary IoU) with the boundaries eroded by rle.boundary_dilation(h, w, dilation_ratio)."""
 
-    def __init__(self, lvis_gt, lvis_dt=None, device=None, iou_type="segm", dilation_ratio=0.02):
+    def __init__(self, lvis_gt, lvis_dt=None, device=None, iou_type="segm", dilation_ratio=0.02, max_dets=MAX_DETS, max_dets_per_cat=None):
         if iou_type not in MASK_TYPES:
             raise ValueError(f"LVISSegmEval: iou_type {iou_type!r} is not supported (segm, boundary; for bbox: LVISEval)")
         boundary_dilation(1, 1, dilation_ratio)                    # refuses a ratio <= 0
         self.dilation_ratio = float(dilation_ratio)
+        self._set_cuts(max_dets, max_dets_per_cat)
         self._setup(lvis_gt, lvis_dt, iou_type, device)
 
     def _setup(self, lvis_gt, lvis_dt, iou_type, device):

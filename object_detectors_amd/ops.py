@@ -1395,6 +1395,44 @@ def coco_accumulate(cat_dt_offsets, cat_gt_offsets, order, dt_rank, dt_score, dt
     return precision, recall, scores
 
 
+def pooled_tile():
+    """The number of list positions one wavefront of mi355det_pooled_accumulate owns per pass."""
+    return int(lib().mi355det_pooled_tile())
+
+
+def pooled_accumulate(pool_order, pool_offsets, pool_npig, dt_score, dt_match, dt_ignore, rec_thrs, pool_offsets_host=None):
+    """mi355det_pooled_accumulate: pool_order int64 [P] (the pools' lists of detection slots, each in descending score order, concatenated),
+    pool_offsets int64 [S + 1], pool_npig int64 [S, A], dt_score float64 [ND], dt_match int32 / dt_ignore uint8 [A, T, ND], rec_thrs
+    float64 [R], all on the device -> precision [T, R, S, A], recall [T, S, A], scores [T, R, S, A] (float64).  `pool_offsets_host`: the
+    caller's host copy of the offsets (a sequence of S + 1 ints); without it the offsets are read back here, the one host read."""
+    import numpy as np
+    what = "pooled_accumulate"
+    _need_device(what, pool_order, pool_offsets, pool_npig, dt_score, dt_match, dt_ignore, rec_thrs)
+    dev = rec_thrs.device
+    for name, t, dt in (("pool_order", pool_order, torch.int64), ("pool_offsets", pool_offsets, torch.int64), ("pool_npig", pool_npig, torch.int64),
+                        ("dt_score", dt_score, torch.float64), ("dt_match", dt_match, torch.int32), ("dt_ignore", dt_ignore, torch.uint8),
+                        ("rec_thrs", rec_thrs, torch.float64)):
+        if t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous {dt}")
+    S = int(pool_offsets.shape[0]) - 1
+    A, T, nd = (int(v) for v in dt_match.shape)
+    P, R = int(pool_order.shape[0]), int(rec_thrs.shape[0])
+    if tuple(dt_ignore.shape) != (A, T, nd) or int(dt_score.shape[0]) != nd or tuple(pool_npig.shape) != (S, A):
+        raise ValueError(f"{what}: dt_ignore must be [A, T, ND] like dt_match, dt_score [ND] and pool_npig [S, A]")
+    host = np.ascontiguousarray(pool_offsets.cpu().numpy() if pool_offsets_host is None else pool_offsets_host, dtype=np.int64).reshape(-1)
+    if host.shape[0] != S + 1:
+        raise ValueError(f"{what}: the host copy of the offsets must hold S + 1 entries")
+    precision = torch.empty((T, R, S, A), dtype=torch.float64, device=dev)
+    recall = torch.empty((T, S, A), dtype=torch.float64, device=dev)
+    scores = torch.empty((T, R, S, A), dtype=torch.float64, device=dev)
+    nbytes = int(lib().mi355det_pooled_accumulate_workspace(P, S, T, A))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    check(lib().mi355det_pooled_accumulate(ptr(pool_order), P, ptr(pool_offsets), host.ctypes.data_as(C.c_void_p), S, ptr(pool_npig), nd,
+                                           ptr(dt_score), ptr(dt_match), ptr(dt_ignore), T, A, ptr(rec_thrs), R, ptr(precision), ptr(recall),
+                                           ptr(scores), ptr(ws), nbytes, stream_ptr()), what)
+    return precision, recall, scores
+
+
 def coco_bootstrap(cat_dt_offsets, cat_gt_offsets, order, dt_rank, dt_match, dt_ignore, gt_ignore, max_dets, rec_thrs, dt_image, gt_image,
                    weights):
     """mi355det_coco_bootstrap: coco_accumulate's operands without the scores, dt_image [ND] / gt_image [NG] int32 (each slot's image index)
