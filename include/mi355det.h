@@ -940,6 +940,54 @@ int mi355det_mask_rle_emit(const float* dense, const float* masks, const float* 
 int64_t mi355det_rle_to_string(const int32_t* counts, int64_t n, char* out, int64_t cap);
 int64_t mi355det_rle_from_string(const char* s, int32_t* counts, int64_t cap);
 
+/* ---- Keypoint R-CNN keypoint branch (csrc/keypoint_kernels.hip): tvision/roi_heads.py:186-379,891-932, the keypoint parts of
+ * tvision/transform.py:169-172,244-275 and detection/transforms.py:10-19.  The head (8 x Conv2d 3x3 + ReLU) and the transposed
+ * convolution run on the convolution entries above; ConvTranspose2d(512, K, 4, 2, 1) as a 3x3 / padding 1 convolution to 4 * KP channels
+ * with fp32 output.  SUB-PIXEL LAYOUT of its output and of the gradient that comes back: [rows, 14, 14, ld], channel (2a + b) * KP + k of
+ * pixel (i, j) = keypoint k at pixel (2i + a, 2j + b) of the 28 x 28 map; KP >= K (padded channels: zero weights, zero gradients).
+ *   flip_resize_keypoints  keypoints fp32 [g, K, 3] of a whole batch, image b owning rows [kp_offsets[b], kp_offsets[b + 1]) (int64
+ *                          [n + 1] ON THE DEVICE), table (host) and table_dev (its device copy) as for mi355det_ingest_u8.  Flipped image:
+ *                          _flip_coco_person_keypoints (the COCO left/right index permutation of 17 indices: EINVAL, before the launch,
+ *                          where a table entry has flip set and K != 17;
+ *                          x = w - x, the triple zeroed where v == 0); then resize_keypoints: x * (out_w / w), y * (out_h / h) with
+ *                          float32 ratios, v untouched.
+ *   keypoint_targets       keypoints_to_heatmap for all RoIs in one launch: rois [rows, 5] = (image, x1, y1, x2, y2), gt_index [rows]
+ *                          int64 = matched ground truth inside the image, keypoints / kp_offsets as above ->
+ *                          target int32 [rows, K] = y * size + x (0 where not valid), valid int32 [rows, K], count int32 [1] = number of
+ *                          valid pairs, left on the device.  Float32 in the reference's order: floor((x - x1) * (size / (x2 - x1))), IEEE
+ *                          division; x == x2 (y == y2) -> size - 1; valid = inside [0, size)^2 and v > 0.  Rows >= valid_rows (bucket
+ *                          padding) and matches outside their image's keypoints are not valid.
+ *   keypoint_heatmaps      logits fp32 in the sub-pixel layout -> out fp32 [rows, K, 56, 56]: F.interpolate(scale_factor=2, bilinear,
+ *                          align_corners=False) (source (d + 0.5) / 2 - 0.5 clamped at 0: weights 0.25 / 0.75).
+ *   keypoint_loss          keypointrcnn_loss on those 56 x 56 logits, formed on the fly: loss [1] = mean over the valid pairs of
+ *                          logsumexp - logit[target]; dlogits bf16 in the sub-pixel layout (pitch logits_ld; all of it is written, zeros
+ *                          in padded channels) = the gradient (softmax - onehot) / count gathered back through the x2, each low-resolution
+ *                          cell summing its at most 16 contributors in a fixed order; dlogits_f32 (nullable) fp32 [rows, K, 28, 28] =
+ *                          that gradient before its rounding to bf16; dbias [K] = the transposed convolution's bias
+ *                          gradient.  count is read on the device.  No float atomics, bit-identical from run to run.  rows == 0 or
+ *                          count == 0: loss 0 and zero gradients.  workspace: mi355det_keypoint_loss_workspace bytes; on return it holds, as
+ *                          fp32 [rows, K, 2], every pair's loss term lse - logit[target] (0 where not valid) and the sum of its gradient.
+ *   heatmaps_to_keypoints  maps fp32 [rows, K, 56, 56], rois [rows, roi_ld] (roi_ld 4: box; 5: (image, box)) -> xy fp32 [rows, K, 3],
+ *                          scores fp32 [rows, K], one launch, no host read.  Per pair: w = max(x2 - x1, 1), wc = ceil(w) (h likewise;
+ *                          sides above MI355DET_KEYPOINT_MAX_SIDE are cut there), torch's bicubic upsample to hc x wc (A = -0.75,
+ *                          align_corners False, source (d + 0.5) * (56 / size) - 0.5, tap indices clamped), arg-max with the lowest
+ *                          linear index on ties, x = (x_int + 0.5) * (w / wc) + x1 (y likewise), third column 1, score = the upsampled
+ *                          value there.  The upsampled map is never stored. */
+#define MI355DET_KEYPOINT_MAX_SIDE 4096
+int mi355det_flip_resize_keypoints(const float* keypoints, float* out, int64_t g, int32_t num_keypoints, const int64_t* kp_offsets,
+                                   const mi355det_ingest_image* table, const mi355det_ingest_image* table_dev, int32_t n, void* stream);
+int mi355det_keypoint_targets(const float* keypoints, const int64_t* kp_offsets, int32_t n_images, const float* rois,
+                              const int64_t* gt_index, int32_t rows, int32_t valid_rows, int32_t num_keypoints, int32_t heatmap_size,
+                              int32_t* target, int32_t* valid, int32_t* count, void* stream);
+int mi355det_keypoint_heatmaps(const float* logits, int32_t logits_ld, int32_t padded_keypoints, int32_t rows, int32_t num_keypoints,
+                               float* out, void* stream);
+size_t mi355det_keypoint_loss_workspace(int32_t rows, int32_t num_keypoints);
+int mi355det_keypoint_loss(const float* logits, int32_t logits_ld, int32_t padded_keypoints, int32_t rows, int32_t num_keypoints,
+                           const int32_t* target, const int32_t* valid, const int32_t* count, float* loss, void* dlogits,
+                           float* dlogits_f32, float* dbias, void* workspace, size_t workspace_bytes, void* stream);
+int mi355det_heatmaps_to_keypoints(const float* maps, const float* rois, int32_t roi_ld, int32_t rows, int32_t num_keypoints, float* xy,
+                                   float* scores, void* stream);
+
 /* ---- Run lengths from counts strings (csrc/rle_string_kernels.hip): mi355det_rle_from_string for the n masks of a results file at once,
  * with the checks, the area and the tight box that the evaluators need of every mask.  bytes: all strings back to back, no separators,
  * num_bytes in all, ON THE DEVICE.  str_offsets int64 [n + 1]: mask k owns bytes[str_offsets[k]:str_offsets[k + 1]]; the same table is

@@ -233,6 +233,12 @@ PROTOTYPES = {
     "mi355det_mask_rle_workspace": (sz, [i32, i32]),
     "mi355det_mask_rle_count": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, sz, vp]),
     "mi355det_mask_rle_emit": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, i64, vp, i64, vp, vp, vp, sz, vp]),
+    "mi355det_flip_resize_keypoints": (C.c_int, [vp, vp, i64, i32, vp, vp, vp, i32, vp]),
+    "mi355det_keypoint_targets": (C.c_int, [vp, vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "mi355det_keypoint_heatmaps": (C.c_int, [vp, i32, i32, i32, i32, vp, vp]),
+    "mi355det_keypoint_loss_workspace": (sz, [i32, i32]),
+    "mi355det_keypoint_loss": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "mi355det_heatmaps_to_keypoints": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp]),
     "mi355det_rle_to_string": (i64, [vp, i64, C.c_char_p, i64]),
     "mi355det_rle_from_string": (i64, [C.c_char_p, vp, i64]),
     "mi355det_rle_strings_count": (C.c_int, [vp, i64, vp, vp, vp, i64, vp, vp, vp, vp]),

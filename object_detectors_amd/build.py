@@ -29,6 +29,7 @@ SOURCES = [
     ("augment_kernels.hip", ["-ffp-contract=off"]),      # SSD augmentations: Pillow's byte rules in float32 / float64 as written: no twin
     ("cubic_kernels.hip", ["-ffp-contract=off"]),        # YOLO ingest: integer bicubic, float64 box quotients rounded once each: no twin
     ("mask_kernels.hip", ["-ffp-contract=off"]),
+    ("keypoint_kernels.hip", ["-ffp-contract=off"]),     # targets, decode and keypoint resize in torch's float32 order; bf16 path only: no twin
     ("rle_kernels.hip", ["-ffp-contract=off"]),          # shares the paste pixel rule with mask_kernels.hip (csrc/mask_paste.h): no twin
     ("rle_string_kernels.hip", []),                      # counts strings to run lengths: integers only, no twin
     ("boundary_kernels.hip", []),                        # mask boundaries from run lengths: integers only, no twin

@@ -876,6 +876,102 @@ def mask_resize_nearest(masks, size, flip=False):
     return out
 
 
+# ------------------------------------------------------------------------------------ Keypoint R-CNN keypoint branch (csrc/keypoint_kernels.hip)
+def _kp_batch(keypoints, what):
+    """Per-image keypoints [G_b, K, 3] -> (fp32 [G, K, 3] on the device, int64 offsets [n + 1] on the device, K).  No host read."""
+    if not keypoints:
+        raise ValueError(f"{what}: no images")
+    for kp in keypoints:
+        if kp.dim() != 3 or kp.shape[2] != 3 or not kp.is_cuda:
+            raise ValueError(f"{what}: keypoints must be CUDA [G, K, 3] per image")
+    K = int(keypoints[0].shape[1])
+    if any(int(kp.shape[1]) != K for kp in keypoints):
+        raise ValueError(f"{what}: every image must have the same number of keypoints")
+    offsets = [0]
+    for kp in keypoints:
+        offsets.append(offsets[-1] + int(kp.shape[0]))
+    dev = keypoints[0].device
+    return torch.cat([_f32c(kp) for kp in keypoints]), torch.tensor(offsets, dtype=torch.int64).to(dev, non_blocking=True), K
+
+
+def keypoint_targets(keypoints, rois, gt_index, size=56, valid_rows=None):
+    """keypoints_to_heatmap (roi_heads.py:186-219) for a whole batch in one launch: keypoints = per-image [G_b, K, 3]; rois [rows, 5] =
+    (image, box); gt_index [rows] = matched gt inside the image -> (target int32 [rows, K], valid int32 [rows, K], count int32 [1], all on
+    the device).  Rows >= valid_rows (bucket padding) are not valid."""
+    rois = _f32c(rois)
+    kp, offsets, K = _kp_batch(keypoints, "keypoint_targets")
+    rows = rois.shape[0]
+    dev = rois.device
+    target = torch.empty((rows, K), dtype=torch.int32, device=dev)
+    valid = torch.empty((rows, K), dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    check(lib().mi355det_keypoint_targets(ptr(kp), ptr(offsets), len(keypoints), ptr(rois), ptr(gt_index.to(torch.int64).contiguous()), rows,
+                                          rows if valid_rows is None else int(valid_rows), K, int(size), ptr(target), ptr(valid), ptr(count),
+                                          stream_ptr()), "keypoint_targets")
+    return target, valid, count
+
+
+def _kp_logits(what, z, num_keypoints):
+    if z.dtype != torch.float32 or z.dim() != 4 or tuple(z.shape[1:3]) != (14, 14) or z.shape[3] % 4 or z.stride(3) != 1 or not z.is_cuda:
+        raise ValueError(f"{what}: logits must be CUDA fp32 [rows, 14, 14, 4 * KP] (sub-pixel layout)")
+    kp = z.shape[3] // 4
+    if not 1 <= num_keypoints <= kp:
+        raise ValueError(f"{what}: {num_keypoints} keypoints do not fit {kp} padded channels")
+    if z.stride(1) != 14 * z.stride(2) or z.stride(0) != 196 * z.stride(2):
+        raise ValueError(f"{what}: logits must be dense over the pixels")
+    return kp, z.stride(2)
+
+
+def keypoint_heatmaps(z, num_keypoints):
+    """The predictor's bilinear x2: sub-pixel logits fp32 [rows, 14, 14, 4 * KP] -> fp32 [rows, K, 56, 56]."""
+    kp, ld = _kp_logits("keypoint_heatmaps", z, num_keypoints)
+    out = torch.empty((z.shape[0], num_keypoints, 56, 56), dtype=torch.float32, device=z.device)
+    check(lib().mi355det_keypoint_heatmaps(ptr(z), ld, kp, z.shape[0], num_keypoints, ptr(out), stream_ptr()), "keypoint_heatmaps")
+    return out
+
+
+def keypoint_loss(z, target, valid, count, want_f32_grad=False, want_terms=False):
+    """keypointrcnn_loss (roi_heads.py:330-357) fused with the bilinear x2.  z: sub-pixel logits fp32 [rows, 14, 14, 4 * KP]; target, valid,
+    count: what keypoint_targets returned -> (loss [1], dz bf16 like z, dbias [K]); with want_f32_grad also the gradient before its rounding
+    to bf16, fp32 [rows, K, 28, 28]; with want_terms also the per-pair loss terms lse - logit[target], fp32 [rows, K] (0 where the pair is not
+    valid; the loss is their sum over count), read out of the kernel's workspace.  Bit-identical from run to run."""
+    K = target.shape[1]
+    kp, ld = _kp_logits("keypoint_loss", z, K)
+    rows = z.shape[0]
+    if tuple(target.shape) != (rows, K) or tuple(valid.shape) != (rows, K) or target.dtype != torch.int32 or valid.dtype != torch.int32:
+        raise ValueError("keypoint_loss: target and valid must be int32 [rows, K]")
+    dev = z.device
+    L = lib()
+    wsb = L.mi355det_keypoint_loss_workspace(rows, K)
+    ws = torch.empty(max(wsb, 4), dtype=torch.uint8, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    dz = torch.empty(z.shape[:3] + (ld,), dtype=torch.bfloat16, device=dev)[..., :z.shape[3]]
+    dbias = torch.empty(K, dtype=torch.float32, device=dev)
+    d32 = torch.empty((rows, K, 28, 28), dtype=torch.float32, device=dev) if want_f32_grad else None
+    check(L.mi355det_keypoint_loss(ptr(z), ld, kp, rows, K, ptr(target.contiguous()), ptr(valid.contiguous()), ptr(count), ptr(loss), ptr(dz),
+                                   ptr(d32), ptr(dbias), ptr(ws), wsb, stream_ptr()), "keypoint_loss")
+    out = (loss, dz, dbias) + ((d32,) if want_f32_grad else ())
+    if want_terms:
+        out += (ws[:rows * K * 8].view(torch.float32).view(rows, K, 2)[..., 0].clone(),)
+    return out
+
+
+def heatmaps_to_keypoints(maps, rois):
+    """heatmaps_to_keypoints (roi_heads.py:274-327) for all RoIs in one launch, no host read: maps fp32 [rows, K, 56, 56]; rois [rows, 4]
+    boxes or [rows, 5] (image, box) -> (xy [rows, K, 3], scores [rows, K])."""
+    maps, rois = _f32c(maps), _f32c(rois)
+    if maps.dim() != 4 or tuple(maps.shape[2:]) != (56, 56) or not maps.is_cuda:
+        raise ValueError("heatmaps_to_keypoints: maps must be CUDA fp32 [rows, K, 56, 56]")
+    rows, K = maps.shape[0], maps.shape[1]
+    if rois.dim() != 2 or rois.shape[0] != rows or rois.shape[1] not in (4, 5):
+        raise ValueError("heatmaps_to_keypoints: rois must be [rows, 4] or [rows, 5]")
+    xy = torch.empty((rows, K, 3), dtype=torch.float32, device=maps.device)
+    scores = torch.empty((rows, K), dtype=torch.float32, device=maps.device)
+    check(lib().mi355det_heatmaps_to_keypoints(ptr(maps), ptr(rois), rois.shape[1], rows, K, ptr(xy), ptr(scores), stream_ptr()),
+          "heatmaps_to_keypoints")
+    return xy, scores
+
+
 def _device_bytes(what, **tensors):
     for name, (t, dtype) in tensors.items():
         if not t.is_cuda or t.dtype != dtype or not t.is_contiguous():

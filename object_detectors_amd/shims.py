@@ -11,7 +11,7 @@ What gets registered (the call sites of the hot path):
                    dsets.transformations.{ResizeToTensor, COCO91_80, Class1_0}
   torchvision side torchvision.ops.boxes.{box_iou, nms, batched_nms, clip_boxes_to_image, remove_small_boxes},
                    torchvision.ops.{sigmoid_focal_loss, roi_align, MultiScaleRoIAlign, boxes},
-                   tvision.{retinanet, frcnn, mask_rcnn, _utils, anchor_utils, rpn, roi_heads, transform, image_list, coco_eval, coco_utils}
+                   tvision.{retinanet, frcnn, mask_rcnn, keypoint_rcnn, _utils, anchor_utils, rpn, roi_heads, transform, image_list, coco_eval, coco_utils}
 
 Two modes per name.  If the real module is importable (running inside the reference tree, or with torchvision installed) it is imported
 and only the hot-path attributes are REPLACED, so everything else it offers (collate functions, label maps, datasets ...) keeps working.
@@ -38,7 +38,7 @@ _TV_ATTRS = {
     "torchvision.ops.boxes": ("object_detectors_amd.tvision.boxes", ("box_iou", "nms", "batched_nms", "clip_boxes_to_image", "remove_small_boxes")),
     "torchvision.ops": (None, ()),          # filled below: names come from several mirror modules
 }
-_TVISION = ("retinanet", "frcnn", "mask_rcnn", "_utils", "anchor_utils", "rpn", "roi_heads", "transform", "coco_eval", "coco_utils", "boxes", "postprocess", "roi_align", "focal_loss")
+_TVISION = ("retinanet", "frcnn", "mask_rcnn", "keypoint_rcnn", "_utils", "anchor_utils", "rpn", "roi_heads", "transform", "coco_eval", "coco_utils", "boxes", "postprocess", "roi_align", "focal_loss")
 
 
 def _remember(name):

@@ -64,6 +64,19 @@ def prepare_for_coco_keypoint(predictions):
     return coco_results
 
 
+def get_iou_types(model):
+    """detection/engine.py:58-67 (_get_iou_types): what `evaluate` scores for a model - boxes, masks for MaskRCNN, keypoints for KeypointRCNN."""
+    from .keypoint_rcnn import KeypointRCNN
+    from .mask_rcnn import MaskRCNN
+    model = getattr(model, "module", model)
+    iou_types = ["bbox"]
+    if isinstance(model, MaskRCNN):
+        iou_types.append("segm")
+    if isinstance(model, KeypointRCNN):
+        iou_types.append("keypoints")
+    return iou_types
+
+
 class CocoEvaluator:
     """coco_eval.py:20-81 on top of cocoeval.COCOEval.  update() only stores the predictions (tensors stay where they are; dense masks become
     run lengths at once); evaluation runs in accumulate(), over everything stored, so nothing is copied to the host per batch.  The result

@@ -127,7 +127,16 @@ def _packed_layout(shapes):
     return offsets, total
 
 
-def _checked_ingest_arguments(images, targets, flips):
+def resize_keypoints(keypoints, original_size, new_size):
+    """transform.py:260-275: x and y scaled by the float32 ratios new / original, v untouched (a float32 multiply per coordinate)."""
+    ratio_h, ratio_w = (np.float32(s) / np.float32(o) for s, o in zip(new_size, original_size))
+    out = keypoints.clone()
+    out[..., 0] *= float(ratio_w)
+    out[..., 1] *= float(ratio_h)
+    return out
+
+
+def _checked_ingest_arguments(images, targets, flips, keypoints=False):
     """The refusals of `ingest`, all on the host and ahead of any launch.  Returns the images as tensors, the targets as copied dicts (the
     caller's dicts and tensors are not modified) and one bool per image."""
     images = [torch.as_tensor(i) for i in images]
@@ -149,8 +158,12 @@ def _checked_ingest_arguments(images, targets, flips):
             raise ValueError(f"ingest: {len(targets)} targets for {n} images")
         targets = [dict(t) for t in targets]
         for t, img in zip(targets, images):
-            if "keypoints" in t:
+            if "keypoints" in t and not keypoints:
                 raise ValueError("ingest: targets with keypoints are not supported (there is no keypoint branch on this path)")
+            if "keypoints" in t:
+                kp = t["keypoints"]
+                if kp.dim() != 3 or kp.shape[-1] != 3 or not kp.is_floating_point():
+                    raise ValueError("ingest: expected target keypoints to be a float tensor of shape [G, K, 3], got {}".format(tuple(kp.shape)))
             if "boxes" in t and (t["boxes"].dim() != 2 or t["boxes"].shape[-1] != 4):
                 raise ValueError("Expected target boxes to be a tensor of shape [N, 4], got {:}.".format(tuple(t["boxes"].shape)))
             if "masks" in t and (t["masks"].dim() != 3 or tuple(t["masks"].shape[-2:]) != tuple(img.shape[:2])):
@@ -235,8 +248,9 @@ class _Staging:
 
 
 class GeneralizedRCNNTransform(torch.nn.Module):
-    def __init__(self, min_size, max_size, image_mean, image_std, size_divisible=32, fixed_size=None):
+    def __init__(self, min_size, max_size, image_mean, image_std, size_divisible=32, fixed_size=None, keypoints=False):
         super().__init__()
+        self.keypoints = keypoints          # True for a model with a keypoint branch (KeypointRCNN): `ingest` then takes targets with keypoints
         self.min_size = tuple(min_size) if isinstance(min_size, (list, tuple)) else (min_size,)
         self.max_size = max_size
         self.image_mean, self.image_std = image_mean, image_std
@@ -285,6 +299,8 @@ class GeneralizedRCNNTransform(torch.nn.Module):
                 targets[i]["boxes"] = resize_boxes(targets[i]["boxes"], (int(img.shape[-2]), int(img.shape[-1])), (oh, ow))
             if targets is not None and targets[i] is not None and "masks" in targets[i]:      # transform.py:54-60 (nearest, uint8)
                 targets[i]["masks"] = mask_resize_nearest(targets[i]["masks"], (oh, ow))
+            if targets is not None and targets[i] is not None and "keypoints" in targets[i]:  # transform.py:169-172
+                targets[i]["keypoints"] = resize_keypoints(targets[i]["keypoints"], (int(img.shape[-2]), int(img.shape[-1])), (oh, ow))
         return ImageList(batch, sizes), targets
 
     def ingest(self, images, targets=None, flips=None, device=None, augment=None):
@@ -293,7 +309,10 @@ class GeneralizedRCNNTransform(torch.nn.Module):
         Returns what `forward` returns for the flipped float images `img.permute(2, 0, 1).float().div(255)` and their flipped targets, bit
         for bit, from one image launch (mi355det_ingest_u8) and one box launch (mi355det_flip_resize_boxes) per batch; the ImageList
         carries `original_image_sizes`.  CPU images are packed into a pinned buffer and go up in one copy (to `device`, default the current
-        one).  Targets are copied: `boxes` and `masks` are transformed, other keys pass through, `keypoints` are refused.
+        one).  Targets are copied: `boxes` and `masks` are transformed, other keys pass through.  `keypoints` (float [G, K, 3]) are refused
+        by a transform built without `keypoints=True` (a model without a keypoint branch); KeypointRCNN's transform flips them
+        (detection/transforms.py:10-19: the COCO person index permutation, x = width - x, rows with v == 0 zeroed) and resizes them
+        (transform.py:260-275), all keypoints of the batch in one launch beside the box launch (mi355det_flip_resize_keypoints).
 
         augment: the records of `transforms.SSDAugmentation.draw`, one per image, with the targets that `draw` returned and `flips` None
         (the flip is in the records).  The photometric ops run on the packed bytes (mi355det_photometric_u8), zoom-out, crop and flip
@@ -301,7 +320,9 @@ class GeneralizedRCNNTransform(torch.nn.Module):
         images that the reference's PIL transforms give.  Sizes and `original_image_sizes` are the windows': the images the model sees."""
         if augment is not None and flips is not None:
             raise ValueError("ingest: with augment the flips are in its records, flips must be None")
-        images, targets, flips = _checked_ingest_arguments(images, targets, flips)
+        images, targets, flips = _checked_ingest_arguments(images, targets, flips, self.keypoints)
+        if augment is not None and targets is not None and any("keypoints" in t for t in targets):
+            raise ValueError("ingest: targets with keypoints are not supported together with augment (the ssd / ssdlite policies do not move them)")
         n = len(images)
         src_dev = images[0].device
         shapes = [(int(img.shape[0]), int(img.shape[1])) for img in images]
@@ -330,8 +351,19 @@ class GeneralizedRCNNTransform(torch.nn.Module):
         for i in with_boxes:
             box_offsets[i + 1] = targets[i]["boxes"].shape[0]
         np.cumsum(box_offsets, out=box_offsets)
+        with_kp = [i for i in range(n) if targets is not None and "keypoints" in targets[i]]
+        kp_offsets = np.zeros(n + 1, dtype=np.int64)
+        for i in with_kp:
+            kp_offsets[i + 1] = targets[i]["keypoints"].shape[0]
+            if flips[i] and targets[i]["keypoints"].shape[1] != 17:
+                raise ValueError("ingest: the flip of keypoints is the COCO person permutation of 17 keypoints (detection/transforms.py:10-19), "
+                                 "got {}".format(int(targets[i]["keypoints"].shape[1])))
+            if targets[i]["keypoints"].shape[1] != targets[with_kp[0]]["keypoints"].shape[1]:
+                raise ValueError("ingest: every image must have the same number of keypoints per instance")
+        np.cumsum(kp_offsets, out=kp_offsets)
         ntable = ctypes.sizeof(table)
-        naug = nmeta = ntable + box_offsets.nbytes               # the augment tables follow: every size is a multiple of 8
+        nbox = ntable + box_offsets.nbytes
+        naug = nmeta = nbox + (kp_offsets.nbytes if with_kp else 0)      # the augment tables follow: every size is a multiple of 8
         if augment is not None:
             nphoto = naug + ctypes.sizeof(aug_table)
             nmeta = nphoto + ctypes.sizeof(photo_table)
@@ -339,7 +371,9 @@ class GeneralizedRCNNTransform(torch.nn.Module):
             stage = self._staging.setdefault(dev, _Staging())
             pixels, meta = stage.acquire(nbytes if src_dev.type == "cpu" else 0, nmeta)
             meta[:ntable].copy_(torch.from_numpy(np.frombuffer(table, dtype=np.uint8)))
-            meta[ntable:naug].copy_(torch.from_numpy(box_offsets.view(np.uint8)))
+            meta[ntable:nbox].copy_(torch.from_numpy(box_offsets.view(np.uint8)))
+            if with_kp:
+                meta[nbox:naug].copy_(torch.from_numpy(kp_offsets.view(np.uint8)))
             if augment is not None:
                 meta[naug:nphoto].copy_(torch.from_numpy(np.frombuffer(aug_table, dtype=np.uint8)))
                 if len(photo_table):
@@ -381,6 +415,14 @@ class GeneralizedRCNNTransform(torch.nn.Module):
                                                    stream_ptr()), "flip_resize_boxes")
                 for i, b in zip(with_boxes, out.split([int(targets[i]["boxes"].shape[0]) for i in with_boxes])):
                     targets[i]["boxes"] = b
+            if with_kp:
+                kps = [targets[i]["keypoints"].to(torch.float32).to(dev) for i in with_kp]
+                kps = torch.cat(kps).contiguous()
+                out = torch.empty_like(kps)
+                check(L.mi355det_flip_resize_keypoints(ptr(kps), ptr(out), kps.shape[0], kps.shape[1], ctypes.c_void_p(meta_dev.data_ptr() + nbox),
+                                                       ctypes.cast(table, ctypes.c_void_p), table_dev, n, stream_ptr()), "flip_resize_keypoints")
+                for i, k in zip(with_kp, out.split([int(targets[i]["keypoints"].shape[0]) for i in with_kp])):
+                    targets[i]["keypoints"] = k
             if targets is not None:
                 from ..ops import mask_resize_nearest as _resize
                 for i, t in enumerate(targets):
@@ -389,7 +431,7 @@ class GeneralizedRCNNTransform(torch.nn.Module):
         return ImageList(batch, plan.sizes, windows), targets
 
     def postprocess(self, result, image_shapes, original_image_sizes, mask_format="dense"):
-        """transform.py:228-247 (boxes, and masks when the result has them; no keypoint branch on this path).  mask_format "dense" is the
+        """transform.py:228-247 (boxes, masks and keypoints when the result has them).  mask_format "dense" is the
         reference's [D, 1, H0, W0] float masks; "rle" gives their `> 0.5` run lengths (an RLEBatch) at the original image size instead."""
         if mask_format not in ("dense", "rle"):
             raise ValueError("mask_format must be 'dense' or 'rle'")
@@ -404,6 +446,8 @@ class GeneralizedRCNNTransform(torch.nn.Module):
                 else:              # `paste_masks(...) > 0.5` as run lengths, without the full-size masks
                     from ..ops import mask_rle_paste
                     result[i]["masks"] = mask_rle_paste(pred["masks"], boxes, o_im_s)
+            if "keypoints" in pred:
+                result[i]["keypoints"] = resize_keypoints(pred["keypoints"], im_s, o_im_s)
         return result
 
 
