@@ -676,6 +676,43 @@ int mi355det_fastrcnn_loss(const float* class_logits, const float* box_regressio
                            int32_t k, int32_t loss_type, float* losses, float* grad_logits, float* grad_box, void* workspace,
                            size_t workspace_bytes, void* stream);
 
+/* ---- Long-tail baselines (csrc/longtail_kernels.hip) ---------------------------------------------------------
+ * The three standard LVIS baselines the tf-idf method is judged against, restated from the papers (nothing is run against mmdetection
+ * or detectron2): Seesaw loss, Equalization loss v1 and repeat-factor sampling.
+ *
+ * label_histogram: counts[labels[i]] += 1 for i < n with unsigned 64-bit integer atomics (exact, the same from run to run); counts [k]
+ *   int64 is NOT cleared first (it is Seesaw's cumulative state).  A label outside [0, k) is skipped.
+ *
+ * fastrcnn_loss_longtail: the operands of mi355det_fastrcnn_loss (no class weights) with its own loss_type, 0 'seesaw' or 1 'eql'.
+ *   x = class_scale * logits, column 0 is the background, gradients are w.r.t. the UNSCALED logits, the box loss is the smooth-L1 of
+ *   mi355det_fastrcnn_loss (the same device code).
+ *   seesaw (p, q, eps; the paper's 0.8, 2, 1e-2): counts [k] int64 = rows seen per label so far, background included.  With update_counts
+ *     != 0 the histogram of `labels` is added to counts BEFORE the loss reads it.  N_c = max(counts[c], 1), s = softmax(x) (no gradient);
+ *     for a row labelled y and every column j:  M_j = (N_j / N_y)^p if N_j < N_y else 1;  r_j = s_j / max(s_y, eps), C_j = r_j^q if r_j > 1
+ *     else 1;  x'_j = x_j + log(M_j C_j), both factors 1 at j = y;  loss = mean over rows of logsumexp(x') - x'_y;
+ *     d loss / d logits_j = class_scale_j (softmax(x')_j - [j = y]) / n (M and C are constants).
+ *   eql: tail [k] uint8, 1 = a tail category (tail[0] must be 0: the caller checks).  t_j = [j = y and j != 0] (the 'bce' targets),
+ *     w_j = 1 - [y > 0] tail_j (1 - t_j);  loss = sum_rows sum_j w_j BCEWithLogits(x_j, t_j) / n;
+ *     d loss / d logits_j = class_scale_j w_j (sigmoid(x_j) - t_j) / n.
+ *   A label outside [0, k) is never used as an index: that row's class loss is NaN (and so is losses[0]), its gradients are 0 and it adds
+ *   nothing to counts.  Deterministic: no float atomics.  Returns EINVAL for n < 1, k < 2, a loss_type outside 0..1, counts == NULL with
+ *   seesaw or tail == NULL with eql, p or q negative or not finite, eps outside (0, 1]; EWORKSPACE for a workspace below
+ *   fastrcnn_loss_longtail_workspace(n, k).
+ *
+ * repeat_factors: one (image, category) index pair per annotation (mi355det_category_frequencies' operands) and that call's img_freq
+ *   [n_categories] -> r_image [n_images] float64, which the CALLER pre-fills with 1.0:  f_c = img_freq[c] / n_images,
+ *   r_c = max(1, sqrt(t / f_c)) in float64, r_image[i] = max over the annotations of image i of r_c, written with a 64-bit integer
+ *   atomic maximum on the bit pattern (non-negative doubles order as unsigned integers: the result does not depend on the order).
+ *   errors [1] int32 counts the annotations with an index outside its range; they are skipped. */
+int mi355det_label_histogram(const int64_t* labels, int32_t n, int32_t k, int64_t* counts, void* stream);
+size_t mi355det_fastrcnn_loss_longtail_workspace(int32_t n, int32_t k);
+int mi355det_fastrcnn_loss_longtail(const float* class_logits, const float* box_regression, const int64_t* labels,
+                                    const float* regression_targets, const float* class_scale, int32_t n, int32_t k, int32_t loss_type,
+                                    int64_t* counts, const uint8_t* tail, float p, float q, float eps, int32_t update_counts, float* losses,
+                                    float* grad_logits, float* grad_box, void* workspace, size_t workspace_bytes, void* stream);
+int mi355det_repeat_factors(const int32_t* image_index, const int32_t* category_index, int64_t n_annotations, const int32_t* img_freq,
+                            int32_t n_images, int32_t n_categories, double t, double* r_image, int32_t* errors, void* stream);
+
 /* ---- input-side transform (csrc/transform_kernels.hip) -------------------------------------------------
  * resize_bilinear: `planes` fp32 planes [planes][h][w] -> out [planes][pad_h][pad_w]: F.interpolate(mode='bilinear', align_corners=False)
  *   to (out_h, out_w) with the sampling scale taken from the two sizes (recompute_scale_factor=True / size=...), zeros in the pad.

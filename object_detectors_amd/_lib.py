@@ -222,6 +222,10 @@ PROTOTYPES = {
     "mi355det_coco_rows": (C.c_int, [vp, i32, vp, vp, i32, i64, f32, f32, f32, i32, i32, vp, vp, vp, vp]),
     "mi355det_fastrcnn_loss_workspace": (sz, [i32]),
     "mi355det_fastrcnn_loss": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "mi355det_label_histogram": (C.c_int, [vp, i32, i32, vp, vp]),
+    "mi355det_fastrcnn_loss_longtail_workspace": (sz, [i32, i32]),
+    "mi355det_fastrcnn_loss_longtail": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, f32, f32, f32, i32, vp, vp, vp, vp, sz, vp]),
+    "mi355det_repeat_factors": (C.c_int, [vp, vp, i64, vp, i32, i32, C.c_double, vp, vp, vp]),
     "mi355det_mask_roi_pool": (C.c_int, [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, vp]),
     "mi355det_mask_targets": (C.c_int, [P(MaskImages), vp, vp, i32, i32, vp, vp]),
     "mi355det_mask_loss_workspace": (sz, [i32]),

@@ -25,6 +25,7 @@ SOURCES = [
     ("roi_kernels.hip", ["-ffp-contract=off"]),
     ("proposal_kernels.hip", ["-ffp-contract=off"]),
     ("frcnn_kernels.hip", ["-ffp-contract=off"]),
+    ("longtail_kernels.hip", ["-ffp-contract=off"]),     # Seesaw / EQL beside the five losses above, float64 repeat factors as written: no twin
     ("transform_kernels.hip", ["-ffp-contract=off"]),
     ("augment_kernels.hip", ["-ffp-contract=off"]),      # SSD augmentations: Pillow's byte rules in float32 / float64 as written: no twin
     ("cubic_kernels.hip", ["-ffp-contract=off"]),        # YOLO ingest: integer bicubic, float64 box quotients rounded once each: no twin

@@ -14,6 +14,7 @@
 // and are summed by one workgroup in a fixed order (deterministic); the gombit "/4" rescale, which depends on the total, is applied to
 // the already written gradients by a third launch only for that loss type.
 #include "common.h"
+#include "frcnn_rows.h"
 
 using namespace mi355;
 
@@ -101,21 +102,8 @@ __global__ __launch_bounds__(256) void frcnn_loss_kernel(const float* __restrict
     }
     loss = wave_sum(loss) * inv_n;
   }
-  // ---- box regression: smooth-L1 on the labelled class of positive rows, zeros elsewhere
-  float lb = 0.0f;
-  const float* br = breg + (size_t)row * 4 * k;
-  float* gb = gbox ? gbox + (size_t)row * 4 * k : nullptr;
-  for (int c = lane; c < 4 * k; c += 64) {
-    float g = 0.0f;
-    if (y > 0 && (c >> 2) == y) {
-      const float d = br[c] - tgt[(size_t)row * 4 + (c & 3)];
-      const float a = fabsf(d);
-      lb += a < 1.0f ? 0.5f * d * d : a - 0.5f;
-      g = (a < 1.0f ? d : (d > 0.0f ? 1.0f : -1.0f)) * inv_n;
-    }
-    if (gb) gb[c] = g;
-  }
-  lb = wave_sum(lb) * inv_n;
+  // ---- box regression: smooth-L1 on the labelled class of positive rows, zeros elsewhere (csrc/frcnn_rows.h)
+  const float lb = frcnn_box_row(breg, tgt, gbox, row, k, y, lane, inv_n);
   if (lane == 0) {
     row_cls[row] = loss;
     row_box[row] = lb;
@@ -138,31 +126,16 @@ __global__ __launch_bounds__(256) void frcnn_wsum_kernel(const long long* __rest
 
 __global__ __launch_bounds__(256) void frcnn_finalize_kernel(const float* __restrict__ row_cls, const float* __restrict__ row_box, int n, int type,
                                                               float* __restrict__ losses, float* __restrict__ rescale) {
-  __shared__ float s1[256], s2[256];
-  float a = 0.0f, b = 0.0f;
-  for (int i = threadIdx.x; i < n; i += 256) {
-    a += row_cls[i];
-    b += row_box[i];
-  }
-  s1[threadIdx.x] = a;
-  s2[threadIdx.x] = b;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) {
-      s1[threadIdx.x] += s1[threadIdx.x + o];
-      s2[threadIdx.x] += s2[threadIdx.x + o];
-    }
-    __syncthreads();
-  }
+  float c, b;
+  frcnn_sum_rows(row_cls, row_box, n, c, b);
   if (threadIdx.x == 0) {
-    float c = s1[0];
     float r = 1.0f;
     if (type == 3 && c > 5.0f) {     // roi_heads.py:71-72
       c *= 0.25f;
       r = 0.25f;
     }
     losses[0] = c;
-    losses[1] = s2[0];
+    losses[1] = b;
     rescale[0] = r;
   }
 }

@@ -142,6 +142,78 @@ def idf_table(dataset_or_arrays, dset_name="coco", device="cuda"):
     return table
 
 
+# ---- long-tail baselines: the tail mask of Equalization loss v1 and repeat-factor sampling
+def _arrays_and_frequencies(dataset_or_arrays, dset_name, device):
+    a = dataset_or_arrays
+    if not (isinstance(a, dict) and "image_index" in a):
+        a = dataset_arrays(a, dset_name)
+    dev = torch.device(device)
+    im = torch.as_tensor(a["image_index"]).to(device=dev, dtype=torch.int32)
+    cat = torch.as_tensor(a["category_index"]).to(device=dev, dtype=torch.int32)
+    _inst, img = category_frequencies(im, cat, a["n_images"], a["n_categories"])
+    return a, im, cat, img
+
+
+def eql_tail_mask(dataset_or_arrays, lam=1.76e-3, dset_name="lvis", device="cuda"):
+    """Equalization loss v1 (Tan et al., CVPR 2020): uint8 [n_categories] on `device`, 1 where the category's image frequency
+    img_freq / n_images (float64) is below `lam` - a category that never occurs counts as tail - and 0 at index 0, the background column
+    of the box classifier.  Takes what idf_table takes."""
+    a, _im, _cat, img = _arrays_and_frequencies(dataset_or_arrays, dset_name, device)
+    return tail_from_frequencies(img, a["n_images"], lam)
+
+
+def tail_from_frequencies(img_freq, n_images, lam=1.76e-3):
+    """eql_tail_mask's rule on a vector of image counts, on whichever device it lives: [img_freq / n_images < lam] in float64, 0 at index 0."""
+    tail = (img_freq.double() / float(n_images) < float(lam)).to(torch.uint8)
+    tail[0] = 0
+    return tail
+
+
+def repeat_factors(dataset_or_arrays, t=1e-3, dset_name="lvis", device="cuda"):
+    """Repeat-factor sampling (Gupta et al., LVIS 2019): float64 [n_images] on `device`, in listed_annotations' image order (the sorted
+    distinct ids of `images`): r_i = max over image i's annotations of max(1, sqrt(t / f_c)), f_c = img_freq_c / n_images; 1 for an image
+    without annotations (ops.repeat_factors, mi355det_repeat_factors).  Takes what idf_table takes."""
+    from . import ops
+    a, im, cat, img = _arrays_and_frequencies(dataset_or_arrays, dset_name, device)
+    return ops.repeat_factors(im, cat, img, a["n_images"], t)
+
+
+class RepeatFactorSampler(torch.utils.data.Sampler):
+    """detectron2's RepeatFactorTrainingSampler (restated from memory) on the host, one epoch per iteration: with a CPU generator seeded
+    seed + epoch, image i appears floor(r_i) + (u_i < frac(r_i)) times, u = torch.rand(n_images); the list is shuffled with
+    torch.randperm (unless shuffle=False), cut to a multiple of `world` and rank `rank` yields [rank::world]."""
+
+    def __init__(self, repeat_factors, seed=0, rank=0, world=1, shuffle=True):
+        r = torch.as_tensor(repeat_factors).detach().to("cpu", torch.float64).reshape(-1)
+        if not bool((r >= 1).all()):
+            raise ValueError("RepeatFactorSampler: repeat factors are >= 1")
+        if not (0 <= int(rank) < int(world)):
+            raise ValueError("RepeatFactorSampler: need 0 <= rank < world")
+        self._whole = torch.floor(r)
+        self._frac = r - self._whole
+        self.seed, self.rank, self.world, self.shuffle, self.epoch = int(seed), int(rank), int(world), bool(shuffle), 0
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def _indices(self):
+        g = torch.Generator()
+        g.manual_seed(self.seed + self.epoch)
+        u = torch.rand(self._whole.numel(), generator=g)
+        reps = (self._whole + (u < self._frac).to(torch.float64)).to(torch.int64)
+        idx = torch.repeat_interleave(torch.arange(reps.numel()), reps)
+        if self.shuffle:
+            idx = idx[torch.randperm(idx.numel(), generator=g)]
+        idx = idx[:idx.numel() - idx.numel() % self.world]
+        return idx[self.rank::self.world]
+
+    def __iter__(self):
+        return iter(self._indices().tolist())
+
+    def __len__(self):
+        return int(self._indices().numel())
+
+
 def _host_columns(table, columns):
     out = {}
     for c in columns:

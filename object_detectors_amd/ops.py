@@ -773,6 +773,89 @@ def fastrcnn_loss(class_logits, box_regression, labels, regression_targets, clas
     return losses, gl, gb
 
 
+# ---- long-tail baselines beside the five reference losses (csrc/longtail_kernels.hip)
+FRCNN_LONGTAIL_TYPES = {"seesaw": 0, "eql": 1}
+
+
+def label_histogram(labels, counts):
+    """counts[labels[i]] += 1 in place: counts [k] int64 on the device, integer atomics (exact, run-to-run identical).  A label outside
+    [0, k) is skipped.  -> counts."""
+    if not (labels.is_cuda and counts.is_cuda):
+        raise ValueError("mi355det ops need CUDA/HIP tensors (no CPU fallback)")
+    if counts.dtype != torch.int64 or counts.dim() != 1 or not counts.is_contiguous():
+        raise ValueError("label_histogram: counts must be a contiguous int64 vector")
+    lab = labels.to(torch.int64).contiguous().reshape(-1)
+    check(lib().mi355det_label_histogram(ptr(lab), lab.numel(), counts.numel(), ptr(counts), stream_ptr()), "label_histogram")
+    return counts
+
+
+def fastrcnn_loss_longtail(class_logits, box_regression, labels, regression_targets, loss_type, class_scale=None, counts=None, tail=None,
+                           p=0.8, q=2.0, eps=1e-2, update_counts=True, want_grad=True):
+    """Seesaw ('seesaw': counts [k] int64, updated in place with this call's labels before the loss reads it unless update_counts=False)
+    or Equalization loss v1 ('eql': tail [k] of 0/1, tail[0] == 0) with the box loss of fastrcnn_loss -> (losses [2], grad_logits, grad_box).
+    The rules: include/mi355det.h, "Long-tail baselines"."""
+    if loss_type not in FRCNN_LONGTAIL_TYPES:
+        raise ValueError(f"fastrcnn_loss_longtail: unknown loss_type {loss_type!r} ('seesaw' or 'eql')")
+    x, b = _f32c(class_logits), _f32c(box_regression)
+    n, k = x.shape
+    if b.shape != (n, 4 * k):
+        raise ValueError("fastrcnn_loss_longtail: box_regression must be [n, 4*k]")
+    lab = labels.to(torch.int64).contiguous()
+    tgt = _f32c(regression_targets)
+    cs = None if class_scale is None else _f32c(class_scale.reshape(-1))
+    if not lab.is_cuda or lab.shape != (n,) or tgt.shape != (n, 4) or (cs is not None and cs.shape != (k,)):
+        raise ValueError("fastrcnn_loss_longtail: labels [n] and regression_targets [n, 4] on the device, class_scale [k]")
+    if loss_type == "seesaw":
+        if counts is None or not counts.is_cuda or counts.dtype != torch.int64 or counts.shape != (k,) or not counts.is_contiguous():
+            raise ValueError("fastrcnn_loss_longtail: 'seesaw' needs counts, a contiguous int64 [k] tensor on the device")
+        tail = None
+    else:
+        if tail is None or not tail.is_cuda or tail.shape != (k,):
+            raise ValueError("fastrcnn_loss_longtail: 'eql' needs tail, a [k] tensor of 0/1 on the device")
+        if getattr(tail, "_mi355det_tail_checked", None) != tail._version:      # the read synchronises: once per tensor and content, not
+            if bool(tail[0] != 0):                                              # once per training step
+                raise ValueError("fastrcnn_loss_longtail: tail[0] must be 0 (the background is no tail category)")
+            tail._mi355det_tail_checked = tail._version
+        if tail.dtype != torch.uint8 or not tail.is_contiguous():
+            tail = (tail != 0).to(torch.uint8).contiguous()
+        counts = None
+    L = lib()
+    wsb = L.mi355det_fastrcnn_loss_longtail_workspace(n, k)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
+    losses = torch.empty(2, dtype=torch.float32, device=x.device)
+    gl = torch.empty_like(x) if want_grad else None
+    gb = torch.empty_like(b) if want_grad else None
+    check(L.mi355det_fastrcnn_loss_longtail(ptr(x), ptr(b), ptr(lab), ptr(tgt), ptr(cs), n, k, FRCNN_LONGTAIL_TYPES[loss_type], ptr(counts),
+                                            ptr(tail), float(p), float(q), float(eps), int(bool(update_counts)), ptr(losses), ptr(gl), ptr(gb),
+                                            ptr(ws), wsb, stream_ptr()), "fastrcnn_loss_longtail")
+    return losses, gl, gb
+
+
+def repeat_factors(image_index, category_index, img_freq, n_images, t=1e-3):
+    """Repeat-factor sampling (Gupta et al., LVIS 2019): int32 device vectors [A] of (image, category) index pairs and img_freq [n_categories]
+    int32 (category_frequencies' second result) -> r [n_images] float64, r_i = max over image i's annotations of max(1, sqrt(t / f_c)),
+    f_c = img_freq[c] / n_images; 1 for an image without annotations.  Raises ValueError for an index outside its range."""
+    for v in (image_index, category_index, img_freq):
+        if not (torch.is_tensor(v) and v.is_cuda):
+            raise ValueError("mi355det ops need CUDA/HIP tensors (no CPU fallback)")
+        if v.dtype != torch.int32 or v.dim() != 1:
+            raise ValueError("repeat_factors: int32 vectors expected")
+    if image_index.shape != category_index.shape:
+        raise ValueError("repeat_factors: one category index per image index")
+    im, cat, df = image_index.contiguous(), category_index.contiguous(), img_freq.contiguous()
+    n_images = int(n_images)
+    r = torch.ones(max(n_images, 0), dtype=torch.float64, device=im.device)
+    errors = torch.empty(1, dtype=torch.int32, device=im.device)
+    with torch.cuda.device(im.device):
+        check(lib().mi355det_repeat_factors(ptr(im), ptr(cat), int(im.shape[0]), ptr(df), n_images, int(df.shape[0]), float(t), ptr(r), ptr(errors),
+                                            stream_ptr()), "repeat_factors")
+    bad = int(errors.item())
+    if bad:
+        raise ValueError(f"repeat_factors: {bad} annotation(s) with an image index outside [0, {n_images}) or a category index outside "
+                         f"[0, {int(df.shape[0])})")
+    return r
+
+
 # ------------------------------------------------------------------------------------ Mask R-CNN mask branch (csrc/mask_kernels.hip; the pooling: csrc/roi_kernels.hip)
 def mask_roi_pool(feats, rois, scales, k_min, k_max, output_size=14, sampling_ratio=2, out=None):
     """MultiScaleRoIAlign(['0'..'3'], 14, 2) into bf16 NHWC [K, 14, 14, C] (mask_fcn1's input); == bf16(roi_align_nhwc) bit for bit."""

@@ -72,13 +72,14 @@ class FastRCNNPredictor(nn.Module):
 
 class FasterRCNN(nn.Module):
     _postprocess_kw = {}                      # extra arguments of transform.postprocess (MaskRCNN: mask_format)
+    _LONGTAIL_BUFFERS = ("roi_class_counts", "roi_eql_tail")
 
     def __init__(self, num_classes=91, trainable_backbone_layers=3, tfidf=None,
                  rpn_pre_nms_top_n_train=2000, rpn_pre_nms_top_n_test=1000, rpn_post_nms_top_n_train=2000, rpn_post_nms_top_n_test=1000,
                  rpn_nms_thresh=0.7, rpn_fg_iou_thresh=0.7, rpn_bg_iou_thresh=0.3, rpn_batch_size_per_image=256, rpn_positive_fraction=0.5,
                  rpn_score_thresh=0.0, box_score_thresh=0.05, box_nms_thresh=0.5, box_detections_per_img=100, box_fg_iou_thresh=0.5,
                  box_bg_iou_thresh=0.5, box_batch_size_per_image=512, box_positive_fraction=0.25, bbox_reg_weights=None, loss_type="ce",
-                 device=None, seed=0, body="resnet50", min_size=800, max_size=1333, image_mean=None, image_std=None):
+                 device=None, seed=0, body="resnet50", min_size=800, max_size=1333, image_mean=None, image_std=None, eql_tail=None):
         super().__init__()
         self.engine = FasterRCNNEngine(trainable_backbone_layers, device=device, seed=seed, body=body)
         self.transform = GeneralizedRCNNTransform(min_size, max_size, image_mean or list(IMAGE_MEAN), image_std or list(IMAGE_STD))   # frcnn.py:232-236
@@ -111,13 +112,39 @@ class FasterRCNN(nn.Module):
         self.tfidf_mini_batch = bool(tfidf.get("mini_batch", False))
         self.tfidf_norm = tfidf.get("tfidf_norm", 0)
         self.loss_function_name = tfidf.get("loss_function", loss_type)
-        if self.loss_function_name not in ops.FRCNN_LOSS_TYPES:
-            raise ValueError(f"FasterRCNN: unknown loss function {self.loss_function_name!r} (reference: {sorted(ops.FRCNN_LOSS_TYPES)})")
+        if self.loss_function_name not in ops.FRCNN_LOSS_TYPES and self.loss_function_name not in ops.FRCNN_LONGTAIL_TYPES:
+            raise ValueError(f"FasterRCNN: unknown loss function {self.loss_function_name!r} (reference: {sorted(ops.FRCNN_LOSS_TYPES)}; "
+                             f"long-tail baselines: {sorted(ops.FRCNN_LONGTAIL_TYPES)})")
         cw = tfidf.get("classification_weights")
         self.classification_weights = None if cw is None else cw.detach().to(dev).float()
+        # ---- the state of the long-tail baselines; a model with one of the reference's five losses registers nothing
+        if self.loss_function_name in ops.FRCNN_LONGTAIL_TYPES and cw is not None:
+            raise ValueError(f"FasterRCNN: classification_weights apply to 'ce' only, not to {self.loss_function_name!r}")
+        if self.loss_function_name == "seesaw":
+            # rows seen per label so far, background included; cumulative over the training run, per rank (never all-reduced)
+            self.register_buffer("roi_class_counts", torch.zeros(num_classes, dtype=torch.int64, device=dev))
+        elif self.loss_function_name == "eql":
+            if eql_tail is None:
+                raise ValueError("FasterRCNN: loss 'eql' needs eql_tail=, the [num_classes] 0/1 mask of the tail categories "
+                                 "(dataset_stats.eql_tail_mask)")
+            tail = torch.as_tensor(eql_tail).detach().reshape(-1)
+            if tail.numel() != num_classes:
+                raise ValueError(f"FasterRCNN: eql_tail must have num_classes = {num_classes} entries")
+            if bool(tail[0] != 0):
+                raise ValueError("FasterRCNN: eql_tail[0] must be 0 (the background is no tail category)")
+            self.register_buffer("roi_eql_tail", (tail != 0).to(device=dev, dtype=torch.uint8))
         self.loss_type = self.loss_function_name
         self.num_classes = num_classes
         self.rpn_coder = BoxCoder((1.0, 1.0, 1.0, 1.0))
+
+    @property
+    def longtail(self):
+        """The `longtail=` state of roi_heads.fastrcnn_loss, read from the buffers as they are now; None for the reference's losses."""
+        if self.loss_function_name == "seesaw":
+            return {"counts": self.roi_class_counts, "update_counts": self.training}                 # eval never counts
+        if self.loss_function_name == "eql":
+            return {"tail": self.roi_eql_tail}
+        return None
 
     def head_parameters(self):
         return list(self.box_head.parameters()) + list(self.box_predictor.parameters())
@@ -128,6 +155,9 @@ class FasterRCNN(nn.Module):
             sd["roi_heads.box_head." + k2] = v
         for k2, v in self.box_predictor.state_dict().items():
             sd["roi_heads.box_predictor." + k2] = v
+        for k2 in self._LONGTAIL_BUFFERS:                 # present only with 'seesaw' / 'eql'
+            if hasattr(self, k2):
+                sd["roi_heads." + k2] = getattr(self, k2)
         return sd
 
     def load_state_dict(self, sd, strict=True):
@@ -136,6 +166,12 @@ class FasterRCNN(nn.Module):
         self.box_head.load_state_dict({k[len("roi_heads.box_head."):]: v for k, v in sd.items() if k.startswith("roi_heads.box_head.")})
         self.box_predictor.load_state_dict({k[len("roi_heads.box_predictor."):]: v for k, v in sd.items()
                                             if k.startswith("roi_heads.box_predictor.")})
+        for k2 in self._LONGTAIL_BUFFERS:                 # copied in place, keeping the buffer's device and dtype
+            if hasattr(self, k2):
+                if "roi_heads." + k2 in sd:
+                    getattr(self, k2).copy_(sd["roi_heads." + k2])
+                elif strict:
+                    raise KeyError(f"load_state_dict: missing roi_heads.{k2}")
 
     # ------------------------------------------------------------------
     def _proposals(self, out, plan, image_shapes, counts_out=None):
@@ -257,7 +293,7 @@ class FasterRCNN(nn.Module):
         cls, reg = self.box_predictor(self.box_head(x))
         # roi_heads.py:826-827: fastrcnn_loss(self.tfidf * class_logits, ..., weights=self.classification_weights, loss_type=...)
         loss_cls, loss_box = fastrcnn_loss(cls, reg, labels, reg_targets, weights=self.classification_weights, loss_type=self.loss_function_name,
-                                           class_scale=self.tfidf)
+                                           class_scale=self.tfidf, longtail=self.longtail)
         # ---- RPN losses on leaf copies of the engine's outputs (their .grad is the engine's head gradient).  Issued AFTER the RoI branch:
         # they do not feed it, and their host time then hides behind the RoI kernels instead of sitting in front of them with the device idle
         torch.cuda.current_stream(images.device).wait_stream(self._tgt_stream)

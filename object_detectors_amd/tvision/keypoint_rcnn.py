@@ -128,7 +128,8 @@ class KeypointRCNNPredictor(nn.Module):
 
 
 class KeypointRCNN(FasterRCNN):
-    """torchvision's KeypointRCNN (constructor from memory) over tvision/frcnn.py:FasterRCNN."""
+    """torchvision's KeypointRCNN (constructor from memory) over tvision/frcnn.py:FasterRCNN; **kw are FasterRCNN's arguments, the box
+    classifier's long-tail baselines loss_type='seesaw' | 'eql' with eql_tail= among them."""
 
     def __init__(self, num_classes=2, trainable_backbone_layers=3, tfidf=None, num_keypoints=17, keypoint_roi_pool=None, keypoint_head=None,
                  keypoint_predictor=None, min_size=(640, 672, 704, 736, 768, 800), max_size=1333, **kw):

@@ -115,7 +115,8 @@ class MaskRCNNPredictor(nn.Module):
 
 
 class MaskRCNN(FasterRCNN):
-    """mask_rcnn.py:21-223 over tvision/frcnn.py:FasterRCNN (same constructor arguments)."""
+    """mask_rcnn.py:21-223 over tvision/frcnn.py:FasterRCNN (same constructor arguments, the box classifier's long-tail baselines
+    loss_type='seesaw' | 'eql' with eql_tail= among them)."""
 
     def __init__(self, num_classes=91, trainable_backbone_layers=3, tfidf=None, mask_roi_pool=None, mask_head=None, mask_predictor=None,
                  mask_format="dense", **kw):

@@ -142,12 +142,12 @@ def retinanet_postprocess_detections(cls_logits_per_level, bbox_reg_per_level, a
 def roi_heads_postprocess_detections(class_logits, box_regression, proposals, image_shapes, tfidf_post=1.0, score_thresh=0.05,
                                      nms_thresh=0.5, detections_per_img=100, weights=(10.0, 10.0, 5.0, 5.0), loss_type="ce"):
     """RoIHeads.postprocess_detections (roi_heads.py:715-781): scores by the training loss ('ce' softmax, 'gombit*' double-exponential,
-    otherwise sigmoid; :724-729), per-class batched NMS."""
+    otherwise sigmoid; :724-729; the long-tail baselines: 'seesaw' as 'ce', 'eql' sigmoid), per-class batched NMS."""
     coder = BoxCoder(weights)
     num_classes = class_logits.shape[-1]
     per_img = [len(p) for p in proposals]
     pred_boxes = coder.decode(box_regression, proposals)
-    if loss_type == "ce":
+    if loss_type in ("ce", "seesaw"):                                   # seesaw trains a softmax classifier: scored as 'ce'
         pred_scores = torch.softmax(tfidf_post * class_logits, -1)
     elif loss_type.startswith("gombit"):
         pred_scores = 1 / (torch.exp(torch.exp(-tfidf_post * (class_logits - 1.96))))
@@ -181,7 +181,7 @@ def roi_heads_postprocess_detections_batch(class_logits, box_regression, proposa
     the threshold (the caller then takes the unbounded per-image route)."""
     n, p = proposals_pad.shape[0], proposals_pad.shape[1]
     c = class_logits.shape[-1]
-    if loss_type == "ce":
+    if loss_type in ("ce", "seesaw"):                                   # seesaw trains a softmax classifier: scored as 'ce'
         scores = torch.softmax(tfidf_post * class_logits, -1)
     elif loss_type.startswith("gombit"):
         scores = 1 / (torch.exp(torch.exp(-tfidf_post * (class_logits - 1.96))))

@@ -1,6 +1,7 @@
 """Training-side mirrors of `RoIHeads` (tvision/roi_heads.py) over the HIP kernels.
 
   fastrcnn_loss                 roi_heads.py:22-98     'ce' | 'bce' | 'focal_loss' | 'gombit' | 'gombit_fl', fused forward + gradients (mi355det_fastrcnn_loss)
+                                                       + the long-tail baselines 'seesaw' | 'eql' (mi355det_fastrcnn_loss_longtail, not in the reference)
   minibatch_tfidf               roi_heads.py:801-809   per-batch smoothed idf row
   assign_targets_to_proposals   roi_heads.py:627-651   fused box_iou + Matcher(0.5, 0.5) per image
   select_training_samples       roi_heads.py:688-713   + add_gt_proposals, sampler (torch, row a19), BoxCoder(10,10,5,5).encode
@@ -29,14 +30,43 @@ class _FastRCNNLossFn(torch.autograd.Function):
         return gl * g_cls, gb * g_box, None, None, None, None, None
 
 
-def fastrcnn_loss(class_logits, box_regression, labels, regression_targets, weights=None, loss_type="ce", class_scale=None):
+class _LongTailLossFn(torch.autograd.Function):
+    """_FastRCNNLossFn for 'seesaw' / 'eql' (csrc/longtail_kernels.hip).  `state` is a plain dict (see fastrcnn_loss); Seesaw's counts are
+    updated in place by the forward."""
+
+    @staticmethod
+    def forward(ctx, class_logits, box_regression, labels, regression_targets, class_scale, loss_type, state):
+        losses, gl, gb = ops.fastrcnn_loss_longtail(class_logits, box_regression, labels, regression_targets, loss_type, class_scale,
+                                                    counts=state.get("counts"), tail=state.get("tail"), p=state.get("p", 0.8),
+                                                    q=state.get("q", 2.0), eps=state.get("eps", 1e-2),
+                                                    update_counts=state.get("update_counts", True), want_grad=True)
+        ctx.save_for_backward(gl, gb)
+        return losses[0], losses[1]
+
+    @staticmethod
+    def backward(ctx, g_cls, g_box):
+        gl, gb = ctx.saved_tensors
+        return gl * g_cls, gb * g_box, None, None, None, None, None
+
+
+def fastrcnn_loss(class_logits, box_regression, labels, regression_targets, weights=None, loss_type="ce", class_scale=None, longtail=None):
     """roi_heads.py:24-96: (classification_loss, box_loss) for loss_type 'ce' | 'bce' | 'focal_loss' | 'gombit' | 'gombit_fl'.
+
+    Beside the reference's five, the long-tail baselines 'seesaw' and 'eql'  with `longtail` their state: a dict with
+    'counts' (seesaw: int64 [k] on the device, updated in place unless 'update_counts' is False; optional 'p', 'q', 'eps') or 'tail'
+    (eql: [k] of 0/1).  `weights` with either raises.
 
     The reference multiplies the tf-idf row into the logits at the call site (:826-827 `fastrcnn_loss(self.tfidf * class_logits, ...)`);
     pass that row as `class_scale` to have the kernel apply it (the returned gradient is w.r.t. the unscaled logits), or pre-multiply and
     leave it None, as the reference's callers do."""
     labels = torch.cat(labels, dim=0)
     regression_targets = torch.cat(regression_targets, dim=0)
+    if loss_type in ops.FRCNN_LONGTAIL_TYPES:
+        if weights is not None:
+            raise ValueError(f"fastrcnn_loss: class weights apply to 'ce' only, not to {loss_type!r}")
+        if longtail is None:
+            raise ValueError(f"fastrcnn_loss: {loss_type!r} needs its state (longtail=)")
+        return _LongTailLossFn.apply(class_logits, box_regression, labels, regression_targets, class_scale, loss_type, longtail)
     if loss_type not in ops.FRCNN_LOSS_TYPES:
         raise ValueError(f"fastrcnn_loss: unknown loss_type {loss_type!r}")
     if weights is not None and loss_type != "ce":
