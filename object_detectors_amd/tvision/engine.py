@@ -18,9 +18,9 @@ import os
 
 import torch
 
-from .. import _lib, ops
+from .. import ops
 from .._lib import check, lib
-from ..plan_core import Act, BackwardSchedule, GradAccumulator, PlanBase, _vp, build_pack_table, cached_plan, check_images, comm_hook
+from ..plan_core import IMAGE, Act, BackwardSchedule, GradAccumulator, PlanBase, address, at, build_pack_table, cached_plan, check_images, comm_hook
 from .anchor_utils import AnchorGenerator
 
 LAYERS = [3, 4, 6, 3]
@@ -240,24 +240,22 @@ class RetinaNetEngine:
     def _pack_shape(self, s):
         return self._shape(s, 1, 8, 8), ops.cout_pad_of(s.cout)
 
-    def _gconv_pack_call(self, s, need_dgrad, stream):
-        """(fn, args) that repacks one grouped 3x3 weight from its fp32 master on `stream` (no synchronisation)."""
+    def _gconv_pack_call(self, s, need_dgrad):
+        """(fn, *operands before the stream) that repacks one grouped 3x3 weight from its fp32 master (no synchronisation)."""
         wf, wd = self.packed[s.name]
-        shp = self._shape(s, 1, 8, 8)
-        return (lib().mi355det_gconv_pack_weights, (shp, s.groups, _vp(self.params[s.name + ".weight"]), 1, _vp(wf), _vp(wd) if need_dgrad else None,
-                                                    stream))
+        return (lib().mi355det_gconv_pack_weights, self._shape(s, 1, 8, 8), s.groups, self.params[s.name + ".weight"], 1, wf, wd if need_dgrad else None)
 
     def _pack(self, specs, need_dgrad):
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         for s in specs:
             if s.groups > 1:
-                fn, args = self._gconv_pack_call(s, need_dgrad, st)
-                check(fn(*args), "gconv_pack_weights")
+                fn, *args = self._gconv_pack_call(s, need_dgrad)
+                check(fn(*map(address, args), st), "gconv_pack_weights")
         specs = [s for s in specs if s.groups == 1]
         if not specs:
             return
         tab, ne, nb = build_pack_table(lib(), self, specs, self._pack_shape, need_dgrad)
-        check(lib().mi355det_pack_weights_batched(_vp(tab), ne, nb, C.c_void_p(torch.cuda.current_stream().cuda_stream)), "pack_weights_batched")
+        check(lib().mi355det_pack_weights_batched(address(tab), ne, nb, st), "pack_weights_batched")
         torch.cuda.current_stream().synchronize()      # `tab` is freed on return
 
     # ------------------------------------------------------------------ plan / step
@@ -345,7 +343,7 @@ class FasterRCNNEngine(RetinaNetEngine):
         outs = []
         for f in p.features[:levels]:
             o = torch.empty((f.n, f.c, f.h, f.w), device=self.device, dtype=torch.float32)
-            check(lib().mi355det_nhwc_to_nchw_f32(f.ptr, 1, f.ld, f.n, f.c, f.h, f.w, _vp(o), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+            check(lib().mi355det_nhwc_to_nchw_f32(f.ptr, 1, f.ld, f.n, f.c, f.h, f.w, address(o), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
                   "nhwc_to_nchw_f32")
             outs.append(o)
         return outs
@@ -368,7 +366,7 @@ class FasterRCNNEngine(RetinaNetEngine):
                 rg.buf.copy_(g)
             else:
                 g = g.float().contiguous()
-                check(lib().mi355det_nchw_f32_to_nhwc(_vp(g), rg.n, rg.c, rg.h, rg.w, rg.ptr, 1, rg.ld, st), "nchw_f32_to_nhwc")
+                check(lib().mi355det_nchw_f32_to_nhwc(address(g), rg.n, rg.c, rg.h, rg.w, rg.ptr, 1, rg.ld, st), "nchw_f32_to_nhwc")
         p.load_head_grads()
         p.run_backward()
 
@@ -409,31 +407,22 @@ class RetinaPlan(PlanBase):
             s = eng.by_name[name]
             shp_f = eng._shape(s, x.n, x.h, x.w, store=False, in_ld=x.ld)
             wf, wd = eng.packed[name]
-            aff = eng.affine[s.bn] if s.bn else None
-            scale = _vp(aff[0]) if aff is not None else None
-            shift = _vp(aff[1]) if aff is not None else (_vp(eng.params[name + ".bias"]) if s.bias else None)
+            scale, shift = eng.affine[s.bn] if s.bn else (None, eng.params[name + ".bias"] if s.bias else None)
             needs = s.trainable or x.needs_grad or (res is not None and res.needs_grad)
-            rec = dict(kind="conv", name=name, spec=s, x=x, res=res, level=level, scale=aff[0] if aff is not None else None)
+            cp = ops.cout_pad_of(s.cout)
             if s.groups > 1:
                 a = new_act(x.n, shp_f.ho, shp_f.wo, s.cout, needs)
-                e = _lib.ConvEpilogue(scale, shift, None, 0, int(s.relu), 0)
-                self.fwd.append((L.mi355det_gconv_fwd_ex, (C.byref(shp_f), s.groups, x.ptr, _vp(wf), C.byref(e), a.ptr, 0, self.stream)))
+                self.emit(self.fwd, L.mi355det_gconv_fwd_ex, shp_f, s.groups, x, wf, self.epilogue(scale, shift, None, int(s.relu)), a, 0, self.stream)
             elif s.head:
-                k = K if s.head == "cls_logits" else 4
-                out = self.logits if s.head == "cls_logits" else self.bbox_reg
-                row0 = sum(self.level_rows[:level])
-                shp_f.out_ld = A * k
-                e = _lib.ConvEpilogue(None, shift, None, 0, 0, self.rows * k)
-                y = C.c_void_p(out.data_ptr() + 4 * row0 * k)
-                self.fwd.append((L.mi355det_conv_fwd_ex, (C.byref(shp_f), x.ptr, _vp(wf), C.byref(e), y, 1, ops.cout_pad_of(s.cout), self.stream)))
-                a = None
+                k, out = (K, self.logits) if s.head == "cls_logits" else (4, self.bbox_reg)
+                shp_f.out_ld, a = A * k, None
+                y = at(out, 4 * sum(self.level_rows[:level]) * k)          # this level's rows of the level-concatenated output
+                self.emit(self.fwd, L.mi355det_conv_fwd_ex, shp_f, x, wf, self.epilogue(None, shift, None, 0, self.rows * k), y, 1, cp, self.stream)
             else:
                 a = new_act(x.n, shp_f.ho, shp_f.wo, s.cout, needs)
-                e = _lib.ConvEpilogue(scale, shift, res.ptr if res is not None else None, res.ld if res is not None else 0, int(s.relu), 0)
-                self.fwd.append((L.mi355det_conv_fwd_ex, (C.byref(shp_f), x.ptr, _vp(wf), C.byref(e), a.ptr, 0, ops.cout_pad_of(s.cout), self.stream)))
+                self.emit(self.fwd, L.mi355det_conv_fwd_ex, shp_f, x, wf, self.epilogue(scale, shift, res, int(s.relu)), a, 0, cp, self.stream)
             shp_b = eng._shape(s, x.n, x.h, x.w, store=True, in_ld=x.ld)          # backward view: padded cout, dense dz pitch
-            self.keep += [shp_f, shp_b, e]
-            rec.update(a=a, shp=shp_b, shp_f=shp_f)
+            rec = dict(kind="conv", name=name, spec=s, x=x, res=res, level=level, scale=scale, a=a, shp=shp_b, shp_f=shp_f)
             self.ops.append(rec)
             self.layers.setdefault(name, []).append(rec)
             return a
@@ -441,22 +430,20 @@ class RetinaPlan(PlanBase):
         # ---- stem: normalise + im2col (7x7/2) -> GEMM + FrozenBN + ReLU -> max-pool     (resnet.py:232-235)
         h2, w2 = down(H, 1), down(W, 1)
         s1 = eng.by_name["backbone.body.conv1"]
-        self.img_call = len(self.fwd)
+        mean, inv_std = (eng.mean, eng.inv_std) if eng.normalize else (None, None)
         if not s1.trainable and H % 32 == 0 and W % 32 == 0:
             # frozen stem (the reference default, backbone_utils.py:89-104): one direct 7x7/2 convolution kernel, no im2col matrix
             wf1, _ = eng.packed["backbone.body.conv1"]
-            aff1 = eng.affine[s1.bn]
+            scale1, shift1 = eng.affine[s1.bn]
             c1 = new_act(n, h2, w2, 64, False)
-            self.fwd.append((L.mi355det_resnet_stem_fwd, [None, _vp(eng.mean) if eng.normalize else None, _vp(eng.inv_std) if eng.normalize else None,
-                                                          _vp(wf1), _vp(aff1[0]), _vp(aff1[1]), int(s1.relu), c1.ptr, c1.ld, n, H, W, self.stream]))
+            self.emit(self.fwd, L.mi355det_resnet_stem_fwd, IMAGE, mean, inv_std, wf1, scale1, shift1, int(s1.relu), c1, c1.ld, n, H, W, self.stream)
             self.ops.append(dict(kind="rstem", a=c1))
         else:
             self.col = new_act(n, h2, w2, STEM_K, False)
-            self.fwd.append((L.mi355det_im2col_nchw, [None, _vp(eng.mean) if eng.normalize else None, _vp(eng.inv_std) if eng.normalize else None,
-                                                      self.col.ptr, n, 3, H, W, 7, 2, 3, STEM_K, self.stream]))
+            self.emit(self.fwd, L.mi355det_im2col_nchw, IMAGE, mean, inv_std, self.col, n, 3, H, W, 7, 2, 3, STEM_K, self.stream)
             c1 = conv("backbone.body.conv1", self.col)
         x = new_act(n, down(h2, 1), down(w2, 1), 64, c1.needs_grad)       # only a trained stem needs the gradient through the max-pool
-        self.fwd.append((L.mi355det_maxpool3x3s2, (c1.ptr, c1.ld, n, c1.h, c1.w, 64, x.ptr, x.ld, self.stream)))
+        self.emit(self.fwd, L.mi355det_maxpool3x3s2, c1, c1.ld, n, c1.h, c1.w, 64, x, x.ld, self.stream)
         self.ops.append(dict(kind="maxpool", x=c1, a=x))
         feats = []
         for li, nb in enumerate(BODY_LAYERS[eng.body_name], 1):
@@ -477,8 +464,8 @@ class RetinaPlan(PlanBase):
         for i in range(top - 1, -1, -1):
             lat = conv(f"{Fp}inner_blocks.{i}", c_feats[i])
             merged = new_act(n, lat.h, lat.w, 256, True)
-            self.fwd.append((L.mi355det_upsample_nearest_add, (last.ptr, last.ld, n, last.h, last.w, 256, lat.ptr, lat.ld, lat.h, lat.w,
-                                                               merged.ptr, merged.ld, self.stream)))
+            self.emit(self.fwd, L.mi355det_upsample_nearest_add, last, last.ld, n, last.h, last.w, 256, lat, lat.ld, lat.h, lat.w, merged, merged.ld,
+                      self.stream)
             self.ops.append(dict(kind="up_add", top=last, lat=lat, a=merged))
             last = merged
             outs.insert(0, conv(f"{Fp}layer_blocks.{i}", last))
@@ -494,9 +481,9 @@ class RetinaPlan(PlanBase):
             p6 = conv(Fp + "extra_blocks.p6", outs[-1])
             r6 = new_act(n, p6.h, p6.w, 256, True)
             # F.relu(p6) (LastLevelP6P7.forward) on a tiny map: the BN+activation kernel with unit scale, zero shift, slope 0
-            self.unit_ss = torch.zeros(4 * 256, device=dev)
-            self.unit_ss[:256] = 1.0
-            self.fwd.append((L.mi355det_bn_act_fwd, (p6.ptr, p6.ld, _vp(self.unit_ss), 256, p6.pixels, 0.0, None, 0, r6.ptr, r6.ld, self.stream)))
+            unit_ss = torch.zeros(4 * 256, device=dev)
+            unit_ss[:256] = 1.0
+            self.emit(self.fwd, L.mi355det_bn_act_fwd, p6, p6.ld, unit_ss, 256, p6.pixels, 0.0, None, 0, r6, r6.ld, self.stream)
             self.ops.append(dict(kind="relu", x=p6, a=r6))
             p7 = conv(Fp + "extra_blocks.p7", r6)
             self.features = outs + [p6, p7]
@@ -527,7 +514,7 @@ class RetinaPlan(PlanBase):
             self.build_pack_table(tr, eng._pack_shape, need_dgrad=training)
         for s in eng.specs:
             if s.trainable and s.groups > 1:
-                self.pack.append(eng._gconv_pack_call(s, training, self.stream))
+                self.emit(self.pack, *eng._gconv_pack_call(s, training), self.stream)
         if training:
             self._build_backward()
             self._autotune()
@@ -547,9 +534,8 @@ class RetinaPlan(PlanBase):
                 ld = ops.pad_to(A * k, 64)          # = Conv.cout_store of the head convolutions
                 gbuf = torch.zeros((n, h, w, ld), device=dev, dtype=bf)
                 self.head_grads[(key, lvl)] = gbuf
-                call = (L.mi355det_cast_rows_bf16, (C.c_void_p(src.data_ptr() + 4 * row0 * k), self.rows * k, A * k, n, h * w, A * k, 1.0,
-                                                    _vp(gbuf), ld, self.stream))
-                self.cast.append(call)
+                call = self.emit(self.cast, L.mi355det_cast_rows_bf16, at(src, 4 * row0 * k), self.rows * k, A * k, n, h * w, A * k, 1.0, gbuf, ld,
+                                 self.stream)
                 if key == "bbox_reg":
                     self.cast_box.append(call)
         dz_elems = max(r["shp"].n * r["shp"].ho * r["shp"].wo * r["shp"].cout for r in self.ops if r["kind"] == "conv")
@@ -562,10 +548,10 @@ class RetinaPlan(PlanBase):
         dws_need = max(L.mi355det_conv_dgrad_workspace(C.byref(r["shp"])) for r in self.ops if r["kind"] == "conv" and r["spec"].groups == 1)
         self.dgrad_ws = torch.empty(max(dws_need, 16), device=dev, dtype=torch.uint8) if dws_need else None
 
-        def dgrad_call(shp, dy_ptr, wd, g, rptr, rld):
+        def dgrad_call(shp, dy, wd, g, r, rld):
             if self.dgrad_ws is not None and L.mi355det_conv_dgrad_workspace(C.byref(shp)):
-                return (L.mi355det_conv_dgrad_ws, (C.byref(shp), dy_ptr, _vp(wd), g.ptr, rptr, rld, _vp(self.dgrad_ws), self.dgrad_ws.numel(), self.stream))
-            return (L.mi355det_conv_dgrad, (C.byref(shp), dy_ptr, _vp(wd), g.ptr, rptr, rld, self.stream))
+                return (L.mi355det_conv_dgrad_ws, shp, dy, wd, g, r, rld, self.dgrad_ws, self.dgrad_ws.numel(), self.stream)
+            return (L.mi355det_conv_dgrad, shp, dy, wd, g, r, rld, self.stream)
         acc = GradAccumulator(L, dev, bf, self, dgrad_call)
         dense, add_tensor, finalize = acc.dense, acc.add_tensor, acc.finalize
 
@@ -598,20 +584,20 @@ class RetinaPlan(PlanBase):
                 return None                            # the split-K form keeps its own epilogue
             return pr
 
-        def add_dgrad(x, shp, dy_ptr, wd, groups=1):
+        def add_dgrad(x, shp, dy, wd, groups=1):
             pr = mask_fusable(x, shp, groups) if x.needs_grad else None
             if groups > 1:
                 # grouped 3x3 (mi355det_gconv_dgrad writes every element of dx and takes no residual): its own dense tensor, which joins the
                 # activation's other contributions like any tensor - conv1's output has this one consumer, so it becomes the gradient itself
                 if x.needs_grad:
                     d = dense(x)
-                    self.bwd.append((L.mi355det_gconv_dgrad, (C.byref(shp), groups, dy_ptr, _vp(wd), d.ptr, self.stream)))
+                    self.emit(self.bwd, L.mi355det_gconv_dgrad, shp, groups, dy, wd, d, self.stream)
                     add_tensor(x, d)
                 return
             if pr is None:
-                return acc.add_dgrad(x, shp, dy_ptr, wd)
-            acc.add_dgrad(x, shp, dy_ptr, wd, lambda shp, dy_ptr, wd, g, _rptr, _rld: (
-                L.mi355det_conv_dgrad_mask, (C.byref(shp), dy_ptr, _vp(wd), g.ptr, x.ptr, x.ld, _vp(pr["scale"]), int(pr["spec"].relu), self.stream)))
+                return acc.add_dgrad(x, shp, dy, wd)
+            acc.add_dgrad(x, shp, dy, wd, lambda shp, dy, wd, g, _r, _rld: (
+                L.mi355det_conv_dgrad_mask, shp, dy, wd, g, x, x.ld, pr["scale"], int(pr["spec"].relu), self.stream))
             pr["dz_fused"] = True                      # x.grad now holds dz of the producer, not the activation gradient
 
         self.bwd_marks = []
@@ -637,7 +623,7 @@ class RetinaPlan(PlanBase):
                     continue
                 x = rec["x"]
                 d = dense(x)
-                self.bwd.append((L.mi355det_maxpool3x3s2_bwd, (x.ptr, x.ld, g.ptr, g.ld, x.n, x.h, x.w, x.c, d.ptr, d.ld, self.stream)))
+                self.emit(self.bwd, L.mi355det_maxpool3x3s2_bwd, x, x.ld, g, g.ld, x.n, x.h, x.w, x.c, d, d.ld, self.stream)
                 add_tensor(x, d)
                 continue
             if kind == "up_add":
@@ -646,8 +632,8 @@ class RetinaPlan(PlanBase):
                     continue
                 add_tensor(rec["lat"], g)
                 top = rec["top"]          # the upsample backward accumulates like a data gradient: residual in, gradient out
-                acc.add_dgrad(top, None, None, None, lambda _s, _d, _w, gt, rptr, rld: (
-                    L.mi355det_upsample_nearest_bwd, (g.ptr, g.ld, top.n, top.h, top.w, top.c, g.h, g.w, rptr, rld, gt.ptr, gt.ld, self.stream)))
+                acc.add_dgrad(top, None, None, None, lambda _s, _d, _w, gt, r, rld: (
+                    L.mi355det_upsample_nearest_bwd, g, g.ld, top.n, top.h, top.w, top.c, g.h, g.w, r, rld, gt, gt.ld, self.stream))
                 continue
             if kind == "relu":
                 g = finalize(rec["a"])
@@ -655,14 +641,12 @@ class RetinaPlan(PlanBase):
                     continue
                 a, x = rec["a"], rec["x"]
                 d = dense(a)
-                self.bwd.append((L.mi355det_relu_affine_bwd, (g.ptr, g.ld, None, 0, a.ptr, a.ld, None, a.c, a.pixels, 1, d.ptr, d.ld, None, 0,
-                                                              self.stream)))
+                self.emit(self.bwd, L.mi355det_relu_affine_bwd, g, g.ld, None, 0, a, a.ld, None, a.c, a.pixels, 1, d, d.ld, None, 0, self.stream)
                 add_tensor(x, d)
                 continue
             s, x, a, res, shp, name = rec["spec"], rec["x"], rec["a"], rec["res"], rec["shp"], rec["name"]
             if s.head:
-                gbuf = self.head_grads[(s.head, rec["level"])]
-                dy_ptr, fresh_dz = _vp(gbuf), None
+                dy, fresh_dz = self.head_grads[(s.head, rec["level"])], None
             else:
                 g = finalize(a)
                 if g is None:
@@ -673,31 +657,30 @@ class RetinaPlan(PlanBase):
                     continue
                 scale = rec["scale"]
                 if rec.get("dz_fused"):
-                    dy_ptr, fresh_dz = g.ptr, None         # the consumer's data gradient already applied scale and mask: g IS dz
+                    dy, fresh_dz = g, None             # the consumer's data gradient already applied scale and mask: g IS dz
                 elif s.relu or scale is not None:
                     gm = dense(a) if need_gm else None
                     fresh_dz = None
                     if need_dz:
                         fresh_dz = sched.next_dz()
-                    dzp = _vp(self.dz2[fresh_dz]) if need_dz else None
-                    self.bwd.append((L.mi355det_relu_affine_bwd, (g.ptr, g.ld, None, 0, a.ptr, a.ld, _vp(scale), a.c, a.pixels, int(s.relu), dzp, a.c,
-                                                                  gm.ptr if gm else None, gm.ld if gm else 0, self.stream)))
+                    dy = self.dz2[fresh_dz] if need_dz else None
+                    self.emit(self.bwd, L.mi355det_relu_affine_bwd, g, g.ld, None, 0, a, a.ld, scale, a.c, a.pixels, int(s.relu), dy, a.c, gm,
+                              gm.ld if gm else 0, self.stream)
                     if need_gm:
                         add_tensor(res, gm)
-                    dy_ptr = dzp
                 else:
-                    dy_ptr, fresh_dz = g.ptr, None        # plain bias conv: dz is the incoming gradient itself
+                    dy, fresh_dz = g, None            # plain bias conv: dz is the incoming gradient itself
                     if need_gm:
                         add_tensor(res, g)
                 if not need_dz:
                     continue
-            rec["dy_ptr"] = dy_ptr
+            rec["dy"] = dy
             if s.trainable:
-                sched.wgrad(shp, x.ptr, dy_ptr, eng.grads[name + ".weight"], eng.grads[name + ".bias"] if s.bias else None, dz_index=fresh_dz,
+                sched.wgrad(shp, x, dy, eng.grads[name + ".weight"], eng.grads[name + ".bias"] if s.bias else None, dz_index=fresh_dz,
                             groups=s.groups)
             if x.needs_grad:
                 _, wd = eng.packed[name]
-                add_dgrad(x, shp, dy_ptr, wd, s.groups)
+                add_dgrad(x, shp, dy, wd, s.groups)
             if s.trainable:
                 self.bwd_marks.append((len(self.bwd), first_off[name + ".weight"]))
         sched.close(self)
@@ -716,8 +699,7 @@ class RetinaPlan(PlanBase):
         """Inference plans time the tile candidates of their forward launches too (the igemm tuning key includes the epilogue and the
         pixel count: an eval plan shares nothing with a training plan of another batch size).  Before: every convolution of a RetinaNet
         inference ran the default 128x128 tile - cls_logits of the 1204-class head 6.6 ms against 4.9 ms tuned."""
-        img = torch.rand((self.n, 3, self.H, self.W), device=self.eng.device)
-        self.fwd[self.img_call][1][0] = C.c_void_p(img.data_ptr())
+        self.set_image(torch.rand((self.n, 3, self.H, self.W), device=self.eng.device))
         with self.autotuning():
             self._run(self.pack)
             self._run(self.fwd)
@@ -725,8 +707,7 @@ class RetinaPlan(PlanBase):
 
     def _autotune(self):
         eng = self.eng
-        img = torch.rand((self.n, 3, self.H, self.W), device=eng.device)
-        self.fwd[self.img_call][1][0] = C.c_void_p(img.data_ptr())
+        self.set_image(torch.rand((self.n, 3, self.H, self.W), device=eng.device))
         self.glogits.normal_(0, 1e-3)
         self.gbbox.normal_(0, 1e-3)
         with self.autotuning():
@@ -737,15 +718,14 @@ class RetinaPlan(PlanBase):
             self._run(self.bwd)
         torch.cuda.synchronize()
         # (the grouped 3x3 kernels are no tuner candidates: their launches above ignore the autotune mode, their weight gradients are left out here)
-        self.autotune_wgrads((r["shp"], r["x"].ptr, r["dy_ptr"], eng.grads[r["name"] + ".weight"])
-                             for r in self.ops if r["kind"] == "conv" and r["spec"].trainable and "dy_ptr" in r and r["spec"].groups == 1)
+        self.autotune_wgrads((r["shp"], r["x"], r["dy"], eng.grads[r["name"] + ".weight"])
+                             for r in self.ops if r["kind"] == "conv" and r["spec"].trainable and "dy" in r and r["spec"].groups == 1)
         self.glogits.zero_()
         self.gbbox.zero_()
 
     # ------------------------------------------------------------------
     def run_forward(self, images):
-        self._img = images
-        self.fwd[self.img_call][1][0] = C.c_void_p(images.data_ptr())
+        self.set_image(images)
         self._run(self.pack)
         self._run(self.fwd)
 

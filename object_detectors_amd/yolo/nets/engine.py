@@ -19,7 +19,7 @@ import torch
 
 from ... import _lib, ops
 from ..._lib import lib
-from ...plan_core import Act, BackwardSchedule, GradAccumulator, PlanBase, _vp, cached_plan, check_images, comm_hook  # noqa: F401  (re-exported)
+from ...plan_core import IMAGE, Act, BackwardSchedule, GradAccumulator, PlanBase, at, cached_plan, check_images, comm_hook  # noqa: F401  (re-exported)
 
 BLOCKS = {"darknet_21": [1, 1, 2, 2, 1], "darknet_53": [1, 2, 8, 8, 4]}
 SLOPE = 0.1
@@ -380,7 +380,7 @@ class Plan(PlanBase):
 
         # ---- forward graph
         def conv_bn(name, x, out=None, res=None, fused=None):
-            """fused: (rows, emit(z, stats)) - a launch that produces this layer's z and partial statistics itself (stem + layer1.ds_conv)"""
+            """fused: (rows, launch(z, stats)) - a launch that produces this layer's z and partial statistics itself (stem + layer1.ds_conv)"""
             s = eng.by_name[name]
             shp = eng._wshape(s, x.n, x.h, x.w, in_ld=x.ld)
             x.conv_consumers += 1
@@ -395,36 +395,24 @@ class Plan(PlanBase):
                 # BN + LeakyReLU (+ residual) runs in the MFMA epilogue; the pre-BN tensor z never exists (model.eval(),
                 # test_one_epoch.py:10)
                 shp.out_ld = a.ld
-                e = _lib.ConvEpilogue(_vp(ss), _vp(ss, 4 * shp.cout), res.ptr if res else None, res.ld if res else 0, 2, 0, SLOPE)
-                self.keep += [shp, ss, e]
                 self._bn_stats(None, 0, shp.cout, cp, pixels, b, ss)
                 if fused:
                     fused[1](a, ss)            # stem activation + this convolution + its folded BN / LeakyReLU in one launch
                 else:
-                    self.fwd.append((L.mi355det_conv_fwd_ex, (C.byref(shp), x.ptr, _vp(wf), C.byref(e), a.ptr, 0, cp, self.stream)))
-                rec = dict(kind="cbl", name=name, spec=s, shp=shp, x=x, a=a, res=res, z=None, ss=ss, pixels=pixels)
-                a.producer = rec
-                self.ops.append(rec)
-                self.layers[name] = rec
-                return a
+                    self.emit(self.fwd, L.mi355det_conv_fwd_ex, shp, x, wf, self.epilogue(ss, at(ss, 4 * shp.cout), res, 2, 0, SLOPE), a, 0, cp, self.stream)
+                return self._record(dict(kind="cbl", name=name, spec=s, shp=shp, x=x, a=a, res=res, z=None, ss=ss, pixels=pixels))
             shp.out_ld = shp.cout   # z pitch
             z = torch.zeros((x.n, shp.ho, shp.wo, shp.cout), device=dev, dtype=bf)
             rows = fused[0] if fused else L.mi355det_conv_stats_rows(C.byref(shp), ops.cout_pad_of(shp.cout))
             stats = torch.zeros((rows + 64, 2, cp), device=dev, dtype=torch.float32)
-            self.keep += [shp, z, stats, ss]
             if fused:
                 fused[1](z, stats)
             else:
-                self.fwd.append((L.mi355det_conv_fwd, (C.byref(shp), x.ptr, _vp(wf), None, _vp(z), 0, _vp(stats), cp, self.stream)))
+                self.emit(self.fwd, L.mi355det_conv_fwd, shp, x, wf, None, z, 0, stats, cp, self.stream)
             self._bn_stats(stats, rows, shp.cout, cp, pixels, b, ss)
-            self.fwd.append((L.mi355det_bn_act_fwd, (_vp(z), shp.cout, _vp(ss), shp.cout, pixels, SLOPE, res.ptr if res else None,
-                                                     res.ld if res else 0, a.ptr, a.ld, self.stream)))
+            self.emit(self.fwd, L.mi355det_bn_act_fwd, z, shp.cout, ss, shp.cout, pixels, SLOPE, res, res.ld if res else 0, a, a.ld, self.stream)
             self.dz_elems = max(self.dz_elems, pixels * shp.cout)
-            rec = dict(kind="cbl", name=name, spec=s, shp=shp, x=x, a=a, res=res, z=z, ss=ss, pixels=pixels)
-            a.producer = rec
-            self.ops.append(rec)
-            self.layers[name] = rec
-            return a
+            return self._record(dict(kind="cbl", name=name, spec=s, shp=shp, x=x, a=a, res=res, z=z, ss=ss, pixels=pixels))
 
         def conv_out(name, x, k):
             s = eng.by_name[name]
@@ -433,13 +421,10 @@ class Plan(PlanBase):
             shp_f = ops.conv_shape(x.n, x.h, x.w, s.cin, s.cout, 1, 1, x.ld, eng.head_ld)   # true cout: masks the pad channel
             wf, wd = eng.packed[name]
             cp = ops.cout_pad_of(shp_f.cout)
-            self.keep += [shp, shp_f]
-            self.fwd.append((L.mi355det_conv_fwd, (C.byref(shp_f), x.ptr, _vp(wf), _vp(eng.params[name + ".bias"]), _vp(self.heads[k]), 1,
-                                                   None, cp, self.stream)))
+            self.emit(self.fwd, L.mi355det_conv_fwd, shp_f, x, wf, eng.params[name + ".bias"], self.heads[k], 1, None, cp, self.stream)
             self.ops.append(dict(kind="out", name=name, spec=s, shp=shp, shp_f=shp_f, x=x, k=k))
 
         # stem (darknet.py:41-43,74-76): recompute kernels straight from the fp32 image, no stored z / im2col matrix (csrc/stem_kernels.hip)
-        self.img_args = []       # argument lists whose first entry is the image pointer of the current step
         x = self._stem(n, H, W, new_act)
         stem_fused = self.layers["backbone.conv1"].get("fused_l1")
         feats = {}
@@ -467,12 +452,12 @@ class Plan(PlanBase):
         b0 = branch("embedding0", feats[5], 0)
         t = conv_bn("embedding1_cbl.conv", b0)
         up1 = self.cat1.slice(0, 256)
-        self.fwd.append((L.mi355det_upsample2x_fwd, (t.ptr, t.ld, t.n, t.h, t.w, t.c, up1.ptr, up1.ld, self.stream)))
+        self.emit(self.fwd, L.mi355det_upsample2x_fwd, t, t.ld, t.n, t.h, t.w, t.c, up1, up1.ld, self.stream)
         self.ops.append(dict(kind="up", x=t, cat=self.cat1, c_up=256, skip_to=feats[4]))
         b1 = branch("embedding1", self.cat1, 1)
         t = conv_bn("embedding2_cbl.conv", b1)
         up2 = self.cat2.slice(0, 128)
-        self.fwd.append((L.mi355det_upsample2x_fwd, (t.ptr, t.ld, t.n, t.h, t.w, t.c, up2.ptr, up2.ld, self.stream)))
+        self.emit(self.fwd, L.mi355det_upsample2x_fwd, t, t.ld, t.n, t.h, t.w, t.c, up2, up2.ld, self.stream)
         self.ops.append(dict(kind="up", x=t, cat=self.cat2, c_up=128, skip_to=feats[3]))
         branch("embedding2", self.cat2, 2)
 
@@ -491,22 +476,20 @@ class Plan(PlanBase):
         """Append the calls that fill `ss` (scale | shift | mean | invstd) of BatchNorm layer `b`.  Inference: from the running statistics, into
         fwd_const (stats is None).  Training: from the `rows` partial rows of `stats` [rows + 64, 2, c_pad], locally or (SyncBN) across ranks."""
         eng, L = self.eng, self.eng.L
-        gamma, beta = _vp(eng.params[b + ".weight"]), _vp(eng.params[b + ".bias"])
-        rmean, rvar = _vp(eng.buffers[b + ".running_mean"]), _vp(eng.buffers[b + ".running_var"])
+        gamma, beta = eng.params[b + ".weight"], eng.params[b + ".bias"]
+        rmean, rvar = eng.buffers[b + ".running_mean"], eng.buffers[b + ".running_var"]
         if not self.training:
-            self.fwd_const.append((L.mi355det_bn_eval_scale_shift, (c, gamma, beta, rmean, rvar, BN_EPS, _vp(ss), self.stream)))
+            self.emit(self.fwd_const, L.mi355det_bn_eval_scale_shift, c, gamma, beta, rmean, rvar, BN_EPS, ss, self.stream)
         elif self.sync_world > 1:
             # SyncBN: fold the partial rows into ONE row [sum | sum of squares], all-reduce it, and finalise from that row with the global
             # element count; folded, all-reduced and finalised in double (the local path's precision)
             row = torch.zeros((2, c_pad), device=eng.device, dtype=torch.float64)
-            self.keep.append(row)
-            self.fwd.append((L.mi355det_bn_fold_partials_f64, (_vp(stats), rows, c, c_pad, _vp(row), self.stream)))
+            self.emit(self.fwd, L.mi355det_bn_fold_partials_f64, stats, rows, c, c_pad, row, self.stream)
             self.fwd.append((comm_hook, (self._sync_sum, row)))
-            self.fwd.append((L.mi355det_bn_finalize_f64, (_vp(row), c, c_pad, pixels * self.sync_world, gamma, beta, BN_EPS, BN_MOM, rmean, rvar,
-                                                          _vp(ss), self.stream)))
+            self.emit(self.fwd, L.mi355det_bn_finalize_f64, row, c, c_pad, pixels * self.sync_world, gamma, beta, BN_EPS, BN_MOM, rmean, rvar, ss,
+                      self.stream)
         else:
-            self.fwd.append((L.mi355det_bn_finalize, (_vp(stats), rows, c, c_pad, pixels, gamma, beta, BN_EPS, BN_MOM, rmean, rvar, _vp(ss),
-                                                      self.stream)))
+            self.emit(self.fwd, L.mi355det_bn_finalize, stats, rows, c, c_pad, pixels, gamma, beta, BN_EPS, BN_MOM, rmean, rvar, ss, self.stream)
 
     def _stem(self, n, H, W, new_act):
         eng, L, dev = self.eng, self.eng.L, self.eng.device
@@ -519,17 +502,10 @@ class Plan(PlanBase):
         if rows <= 0:
             raise ValueError("stem kernels need H % 8 == 0 and W % 32 == 0")
         ss = torch.zeros(4 * 32, device=dev, dtype=torch.float32)
-        self.keep += [ss]
-
-        def img_call(fn, args):
-            args = [None] + list(args)
-            self.img_args.append(args)
-            return (fn, args)
         part = None
         if self.training:
             part = torch.zeros((rows + 64, 2, 32), device=dev, dtype=torch.float32)
-            self.keep.append(part)
-            self.fwd.append(img_call(L.mi355det_stem_fwd_stats, (_vp(wf), _vp(part), n, H, W, self.stream)))
+            self.emit(self.fwd, L.mi355det_stem_fwd_stats, IMAGE, wf, part, n, H, W, self.stream)
         self._bn_stats(part, rows, 32, 32, pixels, b, ss)
         fused = None
         l1_rows = L.mi355det_stem_l1_rows(n, H, W)
@@ -538,24 +514,26 @@ class Plan(PlanBase):
             # only as a side output for that layer's weight gradient (csrc/stem_l1_kernels.hip)
             wf1, _ = eng.packed["backbone.layer1.ds_conv"]
 
-            def emit(z1, stats1):
-                self.fwd.append(img_call(L.mi355det_stem_l1_fwd, (_vp(wf), _vp(ss), SLOPE, _vp(wf1), a.ptr, a.ld, _vp(z1), 64, _vp(stats1), n, H, W,
-                                                                  self.stream)))
-            fused = (l1_rows, emit)
+            def launch(z1, stats1):
+                self.emit(self.fwd, L.mi355det_stem_l1_fwd, IMAGE, wf, ss, SLOPE, wf1, a, a.ld, z1, 64, stats1, n, H, W, self.stream)
+            fused = (l1_rows, launch)
         elif not self.training and l1_rows > 0:
             # inference: the same launch with layer 1's folded BN + LeakyReLU in its epilogue; the stem activation is never stored
             wf1, _ = eng.packed["backbone.layer1.ds_conv"]
 
-            def emit_eval(a1, ss1):
-                self.fwd.append(img_call(L.mi355det_stem_l1_fwd_eval, (_vp(wf), _vp(ss), SLOPE, _vp(wf1), _vp(ss1), a1.ptr, a1.ld, n, H, W, self.stream)))
-            fused = (l1_rows, emit_eval)
+            def launch_eval(a1, ss1):
+                self.emit(self.fwd, L.mi355det_stem_l1_fwd_eval, IMAGE, wf, ss, SLOPE, wf1, ss1, a1, a1.ld, n, H, W, self.stream)
+            fused = (l1_rows, launch_eval)
         else:
-            self.fwd.append(img_call(L.mi355det_stem_fwd_apply, (_vp(wf), _vp(ss), SLOPE, a.ptr, a.ld, n, H, W, self.stream)))
-        rec = dict(kind="stem", name=name, spec=s, x=None, a=a, res=None, z=None, ss=ss, pixels=pixels, rows=rows, img_call=img_call, fused_l1=fused)
-        a.producer = rec
+            self.emit(self.fwd, L.mi355det_stem_fwd_apply, IMAGE, wf, ss, SLOPE, a, a.ld, n, H, W, self.stream)
+        return self._record(dict(kind="stem", name=name, spec=s, x=None, a=a, res=None, z=None, ss=ss, pixels=pixels, rows=rows, fused_l1=fused))
+
+    def _record(self, rec):
+        """Register a layer's op record for the backward builder; -> the layer's output activation."""
+        rec["a"].producer = rec
         self.ops.append(rec)
-        self.layers[name] = rec
-        return a
+        self.layers[rec["name"]] = rec
+        return rec["a"]
 
     # ------------------------------------------------------------------
     def _build_backward(self):
@@ -578,17 +556,14 @@ class Plan(PlanBase):
         # for every layer - the reduce launches are ordered on the step's stream
         red_need = max([L.mi355det_bn_act_bwd_reduce_workspace(r["shp"].cout, r["pixels"]) for r in self.ops if r["kind"] == "cbl"] + [1024])
         self.bn_red_ws = torch.zeros(red_need, device=dev, dtype=torch.uint8)
-        red_ptr, red_bytes = _vp(self.bn_red_ws), self.bn_red_ws.numel()
 
-        acc = GradAccumulator(L, dev, bf, self, lambda shp, dy_ptr, wd, g, rptr, rld: (
-            L.mi355det_conv_dgrad, (C.byref(shp), dy_ptr, _vp(wd), g.ptr, rptr, rld, self.stream)))
+        acc = GradAccumulator(L, dev, bf, self, lambda shp, dy, wd, g, r, rld: (L.mi355det_conv_dgrad, shp, dy, wd, g, r, rld, self.stream))
 
-        def emit_dgrad(shp, dy_ptr, wd, x):
+        def emit_dgrad(shp, dy, wd, x):
             g = acc.grad_of(x)
             if g.ld != shp.in_ld:     # x is a channel slice of a concat buffer; its gradient buffer is dense
                 shp = _lib.ConvShape(shp.n, shp.h, shp.w, shp.cin, shp.ho, shp.wo, shp.cout, shp.ksize, shp.stride, shp.pad, g.ld,
                                      shp.out_ld)
-                self.keep.append(shp)
             prod, call = getattr(x, "producer", None), None
             # this dgrad writes the COMPLETE gradient of a BN+LeakyReLU activation (single conv consumer, at most one skip,
             # fused as the epilogue residual): start that layer's BatchNorm backward here, while the tile is on chip
@@ -599,10 +574,9 @@ class Plan(PlanBase):
                 part = torch.zeros((rows + 64, 2, cpad), device=dev, dtype=torch.float32)
                 prod["bn_partials"] = (part, rows, cpad)
 
-                def call(shp, dy_ptr, wd, g, rptr, rld):
-                    return (L.mi355det_conv_dgrad_bn, (C.byref(shp), dy_ptr, _vp(wd), g.ptr, rptr, rld, _vp(prod["z"]), x.c, _vp(prod["ss"]), SLOPE,
-                                                       _vp(part), self.stream))
-            acc.add_dgrad(x, shp, dy_ptr, wd, call)
+                def call(shp, dy, wd, g, r, rld):
+                    return (L.mi355det_conv_dgrad_bn, shp, dy, wd, g, r, rld, prod["z"], x.c, prod["ss"], SLOPE, part, self.stream)
+            acc.add_dgrad(x, shp, dy, wd, call)
 
         self.bwd_marks = []      # (index into self.bwd after the layer's calls, lowest flat_g offset completed)
         first_off = {name: o for name, o, _n, _s in eng.param_order}
@@ -612,7 +586,7 @@ class Plan(PlanBase):
             if rec["kind"] == "stem":
                 # BatchNorm backward + weight gradient of the stem from the image and the activation gradient alone: z and dz are
                 # recomputed in registers (two passes: the per-channel sums, then dz straight into the weight-gradient MFMA)
-                name, a, ss, rows, img_call = rec["name"], rec["a"], rec["ss"], rec["rows"], rec["img_call"]
+                name, a, ss, rows = rec["name"], rec["a"], rec["ss"], rec["rows"]
                 assert a.grad is not None and a.grad_written and not a.parts, name
                 g, b = a.grad, bn_name(name)
                 wf, _ = eng.packed[name]
@@ -623,28 +597,25 @@ class Plan(PlanBase):
                 # ONE pass: A = dy^T [im2col | 1] and the Gram matrix of [im2col | 1] on MFMA; the BN sums and dW are linear in them
                 slab = torch.zeros((rows, 2048), device=dev, dtype=torch.float32)
                 ag = torch.zeros(2048, device=dev, dtype=torch.float32)
-                self.keep += [slab, ag]
-                self.bwd.append(img_call(L.mi355det_stem_bwd_fused, (_vp(wf), _vp(ss), SLOPE, g.ptr, g.ld, _vp(slab), _vp(ag), _vp(sums),
-                                                                     self.n, self.H, self.W, self.stream)))
+                self.emit(self.bwd, L.mi355det_stem_bwd_fused, IMAGE, wf, ss, SLOPE, g, g.ld, slab, ag, sums, self.n, self.H, self.W, self.stream)
                 if self.sync_world > 1:
                     py(self._sync_avg, sums)
-                self.bwd.append((L.mi355det_stem_bwd_finish, (_vp(wf), _vp(ss), _vp(ag), _vp(sums), self.n * self.H * self.W,
-                                                              _vp(eng.grads[name + ".weight"]), _vp(eng.grads[b + ".weight"]),
-                                                              _vp(eng.grads[b + ".bias"]), self.stream)))
+                self.emit(self.bwd, L.mi355det_stem_bwd_finish, wf, ss, ag, sums, self.n * self.H * self.W, eng.grads[name + ".weight"],
+                          eng.grads[b + ".weight"], eng.grads[b + ".bias"], self.stream)
                 sched.publish()        # the stem's gradients come from the main stream: the side stream (last gradient bucket) must see them
             elif rec["kind"] == "out":
                 shp, shp_f, x, k, name = rec["shp"], rec["shp_f"], rec["x"], rec["k"], rec["name"]
                 _, wd = eng.packed[name]
-                dy = _vp(self.head_grads[k])
+                dy = self.head_grads[k]
                 # (behind the head gradients: the criterion ran on the main stream)
-                sched.wgrad(shp_f, x.ptr, dy, eng.grads[name + ".weight"], eng.grads[name + ".bias"], record=False)
+                sched.wgrad(shp_f, x, dy, eng.grads[name + ".weight"], eng.grads[name + ".bias"], record=False)
                 emit_dgrad(shp, dy, wd, x)
             elif rec["kind"] == "up":
                 x, cat, c_up, skip_to = rec["x"], rec["cat"], rec["c_up"], rec["skip_to"]
                 assert cat.grad is not None and cat.grad_written
                 gup = cat.grad.slice(0, c_up)
                 gx = acc.grad_of(x)
-                self.bwd.append((L.mi355det_upsample2x_bwd, (gup.ptr, gup.ld, x.n, x.h, x.w, x.c, gx.ptr, gx.ld, self.stream)))
+                self.emit(self.bwd, L.mi355det_upsample2x_bwd, gup, gup.ld, x.n, x.h, x.w, x.c, gx, gx.ld, self.stream)
                 x.grad_written = True
                 acc.add_tensor(skip_to, cat.grad.slice(c_up, cat.c - c_up))
             else:
@@ -658,27 +629,25 @@ class Plan(PlanBase):
                     acc.add_tensor(res, g)
                 if "bn_partials" in rec:      # the dgrad that produced g already accumulated the per-channel partial sums
                     part, prows, cpad = rec["bn_partials"]
-                    self.bwd.append((L.mi355det_bn_bwd_sum_partials, (_vp(part), prows, shp.cout, cpad, _vp(sums), self.stream)))
+                    self.emit(self.bwd, L.mi355det_bn_bwd_sum_partials, part, prows, shp.cout, cpad, sums, self.stream)
                 elif eng.deterministic:
-                    self.bwd.append((L.mi355det_bn_act_bwd_reduce_det, (g.ptr, g.ld, None, 0, _vp(z), shp.cout, _vp(ss), shp.cout, pixels, SLOPE,
-                                                                        _vp(sums), red_ptr, red_bytes, self.stream)))
+                    self.emit(self.bwd, L.mi355det_bn_act_bwd_reduce_det, g, g.ld, None, 0, z, shp.cout, ss, shp.cout, pixels, SLOPE, sums,
+                              self.bn_red_ws, self.bn_red_ws.numel(), self.stream)
                 else:
-                    self.bwd.append((L.mi355det_bn_act_bwd_reduce, (g.ptr, g.ld, None, 0, _vp(z), shp.cout, _vp(ss), shp.cout, pixels, SLOPE,
-                                                                    _vp(sums), self.stream)))
+                    self.emit(self.bwd, L.mi355det_bn_act_bwd_reduce, g, g.ld, None, 0, z, shp.cout, ss, shp.cout, pixels, SLOPE, sums, self.stream)
                 if self.sync_world > 1:
                     py(self._sync_avg, sums)              # SyncBN backward: (sum dy, sum dy*xhat) of the global batch
                 di = rec["dz_index"] = sched.next_dz()    # (waits until the wgrad that last read this dz buffer has finished)
                 dzb = self.dz2[di]
-                self.bwd.append((L.mi355det_bn_act_bwd_apply, (g.ptr, g.ld, None, 0, _vp(z), shp.cout, _vp(ss), _vp(sums), None, shp.cout,
-                                                               pixels, SLOPE, _vp(dzb), shp.cout, _vp(eng.grads[b + ".weight"]),
-                                                               _vp(eng.grads[b + ".bias"]), self.stream)))
+                self.emit(self.bwd, L.mi355det_bn_act_bwd_apply, g, g.ld, None, 0, z, shp.cout, ss, sums, None, shp.cout, pixels, SLOPE, dzb, shp.cout,
+                          eng.grads[b + ".weight"], eng.grads[b + ".bias"], self.stream)
                 # (measured and removed: the weight gradients of the large maps serial on the main stream - no gain, profiles/r03_ab_results.md)
                 # (measured and removed, round 4: the weight gradient started only when its layer's data gradient has finished, so that it runs beside
                 #  the next BatchNorm passes instead of beside the data gradient: 28.17 -> 29.85 ms, profiles/r04_ab_results.md 8 - the two GEMMs
                 #  side by side fill each other's tails; serialised they do not)
-                sched.wgrad(shp, x.ptr, _vp(dzb), eng.grads[name + ".weight"], None, dz_index=di)
+                sched.wgrad(shp, x, dzb, eng.grads[name + ".weight"], None, dz_index=di)
                 _, wd = eng.packed[name]
-                emit_dgrad(shp, _vp(dzb), wd, x)
+                emit_dgrad(shp, dzb, wd, x)
             if rec["kind"] in ("out", "cbl", "stem"):
                 self.bwd_marks.append((len(self.bwd), first_off[rec["name"] + ".weight"]))
         sched.close(self)
@@ -688,8 +657,7 @@ class Plan(PlanBase):
         conv shape of this plan on the plan's own buffers (mi355det_conv_autotune_mode, _wgrad_autotune)."""
         eng = self.eng
         saved = {k: v.clone() for k, v in eng.buffers.items()}
-        img = torch.randn((self.n, 3, self.H, self.W), device=eng.device)
-        self._set_image(img)
+        self.set_image(torch.randn((self.n, 3, self.H, self.W), device=eng.device))
         for g in self.head_grads:
             g.normal_(0, 1e-2)
         with self.autotuning():
@@ -699,7 +667,7 @@ class Plan(PlanBase):
 
         def wgrad_of(r):
             shp, dy = (r["shp"], self.dz) if r["kind"] == "cbl" else (r["shp_f"], self.head_grads[r["k"]])
-            return shp, r["x"].ptr, _vp(dy), eng.grads[r["name"] + ".weight"]
+            return shp, r["x"], dy, eng.grads[r["name"] + ".weight"]
         self.autotune_wgrads(wgrad_of(r) for r in self.ops if r["kind"] in ("cbl", "out"))
         for k, v in saved.items():
             eng.buffers[k].copy_(v)
@@ -709,8 +677,7 @@ class Plan(PlanBase):
         """Eval plans run the convolutions with the BatchNorm + LeakyReLU (+ residual) epilogue, whose tile choices are keyed separately
         from the training forward's: time the candidates once on this plan's buffers (round 2 ran every eval convolution on the default
         128 x 128 tile: 9.2 ms against 7.0 ms for the same 75 convolutions in the training step)."""
-        img = torch.randn((self.n, 3, self.H, self.W), device=self.eng.device)
-        self._set_image(img)
+        self.set_image(torch.randn((self.n, 3, self.H, self.W), device=self.eng.device))
         self._run(self.pack)
         self._run(self.fwd_const)
         with self.autotuning():
@@ -718,15 +685,8 @@ class Plan(PlanBase):
         torch.cuda.synchronize()
 
     # ------------------------------------------------------------------
-    def _set_image(self, images):
-        """The stem kernels of BOTH directions read the fp32 image: it stays referenced until the next forward."""
-        self._img = images
-        ptr = C.c_void_p(images.data_ptr())
-        for a in self.img_args:
-            a[0] = ptr
-
     def run_forward(self, images):
-        self._set_image(images)
+        self.set_image(images)
         eng = self.eng
         if self.training:
             eng._weights_changed()                 # an optimizer step may follow

@@ -494,3 +494,43 @@ def test_frozen_inference_over_an_epoch_loop():
         assert all(torch.equal(u, v) for u, v in zip(a, ref)), "epoch %d: frozen eval ran on stale constants" % epoch
         seen.append(a[0])
     assert not torch.equal(seen[0], seen[1]) and not torch.equal(seen[1], seen[2])      # the weights did move between the epochs
+
+
+def test_plans_own_their_buffers_across_eviction():
+    """plan_core.audit on real plans, and the same step before and after its plan was evicted and rebuilt (MAX_PLANS = 1): every address in a
+    call list lies in a tensor that plan retains, so nothing the first plan freed can be what the rebuilt one runs on."""
+    import gc
+    from object_detectors_amd.plan_core import audit
+    from object_detectors_amd.yolo.nets.engine import YoloV3Engine
+    eng = YoloV3Engine("darknet_21", 3, 80, device=dev())
+    eng.MAX_PLANS = 1
+    x = torch.from_numpy(detrand.uniform(4242, (2, 3, 128, 128), -2.0, 2.0)).to(dev())
+    cots = None
+
+    def step():
+        nonlocal cots
+        outs = [o.clone() for o in eng.forward(x, training=True)]
+        if cots is None:
+            cots = [torch.from_numpy(detrand.uniform(4300 + k, tuple(o.shape), -1.0, 1.0)).to(dev()) for k, o in enumerate(outs)]
+        eng.backward(cots)
+        torch.cuda.synchronize()
+        return outs, eng.flat_g.clone()
+    outs1, g1 = step()
+    first = eng._last_plan
+    audit(first)
+    eng._last_plan = first = None                   # the engine's cache is the only owner left
+    audit(eng.plan(2, 160, 128, True))              # evicts the 128 x 128 plan ...
+    gc.collect()
+    assert [k[:3] for k in eng.plans] == [(2, 160, 128)]
+    audit(eng.plan(2, 128, 128, True))              # ... and this builds it again
+    assert len(eng.plans) == 1
+    outs2, g2 = step()
+    audit(eng._last_plan)
+    assert all(torch.equal(a, b) for a, b in zip(outs1, outs2)) and torch.equal(g1, g2) and float(g1.abs().sum()) > 0
+    eng.forward(x, training=False)
+    audit(eng._last_plan)
+    eng.freeze_inference()
+    eng.forward(x, training=False)
+    eng.forward(x, training=False)
+    assert not eng._last_plan.training
+    audit(eng._last_plan)

@@ -125,3 +125,49 @@ def test_fasterrcnn_module_train_and_eval(setup):
     for d in det:
         assert d["boxes"].shape[0] == d["scores"].shape[0] == d["labels"].shape[0] <= 100
         assert d["boxes"].shape[0] == 0 or (bool((d["labels"] >= 1).all()) and bool((d["scores"][:-1] >= d["scores"][1:]).all()))
+
+
+def _evict_rebuild_audit(eng, step):
+    """plan_core.audit on real plans, and the same step before and after its plan was evicted and rebuilt (MAX_PLANS = 1).  Forward outputs
+    must be equal bit for bit; the gradients agree to the tolerance of the backward-wiring test above (atomics: DESIGN 2)."""
+    import gc
+    from object_detectors_amd.plan_core import audit
+    eng.MAX_PLANS = 1
+    out1, g1 = step()
+    audit(eng._last_plan)
+    eng._last_plan = None                           # the engine's cache is the only owner left
+    audit(eng.plan(BS, 160, 128, True))             # evicts the 128 x 128 plan ...
+    gc.collect()
+    assert [k[:3] for k in eng.plans] == [(BS, 160, 128)]
+    audit(eng.plan(BS, PX, PX, True))               # ... and this builds it again
+    assert len(eng.plans) == 1
+    out2, g2 = step()
+    audit(eng._last_plan)
+    for k in out1:
+        assert torch.equal(out1[k], out2[k]), k
+    for name, _o, _n, _s in eng.param_order:
+        a, b = g1[name].cpu(), g2[name].cpu()
+        c, ratio = cos(a, b), float(a.double().norm() / (b.double().norm() + 1e-30))
+        assert float(b.abs().max()) > 0 and c > 0.94 and 0.9 < ratio < 1.1, (name, c, ratio)
+    eng.forward(torch.rand((BS, 3, PX, PX), device=dev()), training=False)
+    assert not eng._last_plan.training
+    audit(eng._last_plan)
+
+
+def test_plans_own_their_buffers_across_eviction():
+    from object_detectors_amd.tvision.engine import FasterRCNNEngine
+    eng = FasterRCNNEngine(3, device=dev(), seed=0)
+    x = torch.from_numpy(detrand.uniform(4242, (BS, 3, PX, PX), 0.0, 1.0)).to(dev())
+    cots, cf = [], []
+
+    def step():
+        out = {k: v.clone() for k, v in eng.forward(x, training=True).items()}
+        if not cots:
+            cots.extend(torch.from_numpy(detrand.uniform(11 + i, tuple(out[k].shape), -1.0, 1.0)).to(dev()) * 1e-2
+                        for i, k in enumerate(("cls_logits", "bbox_regression")))
+            cf.extend(torch.from_numpy(detrand.uniform(20 + i, (f.n, f.c, f.h, f.w), -1.0, 1.0)).to(dev()) * 1e-3
+                      for i, f in enumerate(eng._last_plan.features[:4]))
+        eng.backward(*cots, cf)
+        torch.cuda.synchronize()
+        return out, {k: v.clone() for k, v in eng.grads.items()}
+    _evict_rebuild_audit(eng, step)
