@@ -5,6 +5,7 @@
 #include "bitonic_sort.h"
 #include "box_rules.h"
 #include "common.h"
+#include "mfma_prims.h"      // FastDiv
 
 using namespace mi355;
 
@@ -713,19 +714,12 @@ __device__ __forceinline__ void sfl(float x, float t, float alpha, float gamma, 
                                // one address retire at ~90 per microsecond: 2048 of them were 23 of the kernel's 56 us at K = 91)
 // optional bf16 gradient output in the layout the head convolution's backward reads: per pyramid level an NHWC buffer [n, h*w, ld] whose
 // channel a*k + c is anchor a, class c of that pixel (row r of the level-concatenated [n, sum HWA, k] logits = pixel r / A, anchor r % A)
-struct FocalDiv {             // n / d for n < 2^31 (Granlund-Montgomery round-up form, as conv_kernels.hip)
-  unsigned mul, shift, d;
+struct FocalDiv {             // a divisor next to the shared multiply-shift form (mfma_prims.h, included for FastDiv alone): the fast path needs
+                              // the remainder too, and this layout keeps FocalLevels and the compiled kernel as they were
+  FastDiv f;
+  unsigned d;
 };
-static FocalDiv focal_div(unsigned d) {
-  FocalDiv f;
-  f.d = d;
-  unsigned l = 0;
-  while ((1ull << l) < d) ++l;
-  f.shift = l;
-  f.mul = (unsigned)(((1ull << 32) * ((1ull << l) - d)) / d + 1);
-  return f;
-}
-__device__ __forceinline__ unsigned fdivu(unsigned n, const FocalDiv f) { return (__umulhi(f.mul, n) + n) >> f.shift; }
+static FocalDiv focal_div(unsigned d) { return FocalDiv{make_fastdiv(d), d}; }
 
 struct FocalLevels {
   FocalDiv dk, drpi, da;      // divisions by k, rows_per_image, A without the ~25-instruction hardware sequence (fast path below)
@@ -762,7 +756,7 @@ __global__ __launch_bounds__(NT) void focal_kernel(const float* __restrict__ x, 
       //      evaluations - as a separate branch the straddling groups made every wave execute both branches (1.05 ms for 175 M logits
       //      against 2.2 ms for the 1.16 G of the 1204-class head).
       const unsigned iu = (unsigned)i0;
-      const unsigned r0 = fdivu(iu, lv.dk), c0 = iu - r0 * (unsigned)k;
+      const unsigned r0 = fdiv(iu, lv.dk.f), c0 = iu - r0 * (unsigned)k;
       const bool straddles = lv.fast == 2 && c0 + 3u >= (unsigned)k;
       const float4 v = *(const float4*)(x + i0);
       const float xs[4] = {v.x, v.y, v.z, v.w};
@@ -776,7 +770,7 @@ __global__ __launch_bounds__(NT) void focal_kernel(const float* __restrict__ x, 
           break;
         }
         const unsigned ru = r0 + half;
-        const unsigned bu = fdivu(ru, lv.drpi), rl = ru - bu * lv.drpi.d;
+        const unsigned bu = fdiv(ru, lv.drpi.f), rl = ru - bu * lv.drpi.d;
         unsigned st0 = 0, px = (unsigned)lv.pixels[0];
         bf16_t* base = lv.dst[0];
         int ldq = lv.ld[0];
@@ -785,7 +779,7 @@ __global__ __launch_bounds__(NT) void focal_kernel(const float* __restrict__ x, 
           if (l < lv.nlev && rl >= (unsigned)lv.start[l]) {
             st0 = (unsigned)lv.start[l]; px = (unsigned)lv.pixels[l]; base = lv.dst[l]; ldq = lv.ld[l];
           }
-        const unsigned local = rl - st0, pix = fdivu(local, lv.da);
+        const unsigned local = rl - st0, pix = fdiv(local, lv.da.f);
         drow[half] = base + ((size_t)bu * px + pix) * (size_t)ldq + (size_t)(local - pix * lv.da.d) * k;
         mi2[half] = matched[ru];
         wimg2[half] = nfg ? inv_images / fmaxf(1.f, nfg[bu]) : 1.f;

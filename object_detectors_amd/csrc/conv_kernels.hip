@@ -40,8 +40,10 @@ namespace {
 
 #define STAMP(v) do { if (PROF) { __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory"); __builtin_amdgcn_sched_barrier(0); } } while (0)
 
-// ABL (ablation, diagnostic builds only): 1 = no LDS-DMA loads, 2 = no fragment reads, 3 = no MFMAs
-template <int WM, int WN, int TM, int TN, int BK, int NST, int EPI, bool PROF = false, bool ILV = false, int OCC = 0, int ABL = 0>
+// WM x WN waves; each wave computes TM*16 pixels x TN*16 channels.  NST-deep LDS ring: the LDS-DMA of
+// k-steps s+1 .. s+NST-1 stays in flight (counted vmcnt, raw s_barrier) while k-step s runs on the MFMAs -
+// with ~1.5-2 us of loaded-memory latency the bytes in flight per CU, not the MFMA rate, set the speed.
+template <int WM, int WN, int TM, int TN, int BK, int NST, int EPI, bool PROF = false, int OCC = 0>
 __global__ __launch_bounds__(WM* WN * 64, (OCC > 0 ? OCC : (WM * WN >= 8 ? 2 : 1))) void igemm_kernel(const IgemmParams p) {
   unsigned long long t_a = 0, t_b = 0, t_c = 0, t_d = 0, t_e = 0, c_wait = 0, c_bar = 0, c_issue = 0, c_comp = 0, t_begin = 0, t_loop = 0;
   STAMP(t_begin);
@@ -77,27 +79,21 @@ __global__ __launch_bounds__(WM* WN * 64, (OCC > 0 ? OCC : (WM * WN >= 8 ? 2 : 1
     bid = q;
     nblk = __builtin_amdgcn_readfirstlane(nblk / p.ksplit);
   }
-  {
-    const int q = nblk / 8, r = nblk % 8, xcd = bid % 8, loc = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  }
+  bid = xcd_remap(bid, nblk);
   const int mt = bid / ntn, nt = bid - mt * ntn;
   const int m0 = mt * BM, n0 = nt * BN;
 
-  // scalar (per-tap) byte offsets, made non-negative by moving tap_pad into the descriptor base
-  if (tid == 0) {
+  if (tid == 0) {      // scalar (per-tap) byte offsets, looked up per k-step by a run-time tap index
 #pragma unroll
     for (int t = 0; t < MAX_TAPS; ++t)
-      if (t < p.T) s_toff[t] = ((p.dy[t] * p.Win + p.dx[t]) * p.ldin + p.tap_pad) * 2;
+      if (t < p.T) s_toff[t] = tap_byte_offset(p, p.dy[t], p.dx[t]);
   }
 
   unsigned long long t_p1 = 0, t_p2 = 0, t_p3 = 0, t_p4 = 0;
   STAMP(t_p1);
-  // ---- buffer descriptors (wave-uniform): activations relative to the first image this tile touches
-  const int n_first = (int)fdiv(fdiv((unsigned)m0, p.dMW), p.dMH);
-  const int Ktot = p.T * p.Cin;
-  const srd_t rsrc_x = make_srd(p.x + (long long)n_first * p.Hin * p.Win * p.ldin - p.tap_pad, 0x7FFFFFF0u);
-  const srd_t rsrc_w = make_srd(p.w + (long long)n0 * Ktot, 0x7FFFFFF0u);
+  const TileDescriptors td = tile_descriptors(p, m0, n0, p.T);
+  const srd_t rsrc_x = td.rsrc_x, rsrc_w = td.rsrc_w;
+  const int Ktot = td.Ktot;
 
   // ---- per-lane byte offsets of the rows this lane stages
   const int lrow = lane / CPR, cpos = lane % CPR;
@@ -105,31 +101,10 @@ __global__ __launch_bounds__(WM* WN * 64, (OCC > 0 ? OCC : (WM * WN >= 8 ? 2 : 1
   unsigned a_valid[A_PER];
 #pragma unroll
   for (int i = 0; i < A_PER; ++i) {
-    const int instr = wid * A_PER + i;
-    const int row = instr * R + lrow;
-    const int m = m0 + row;
-    unsigned vm = 0;
-    int voff = OOB_VOFF;
-    if (p.lin_in) {   // 1x1, unit stride: the row's pixel index is the address, its only tap is always inside (uniform branch)
-      if (m < p.M) {
-        voff = ((m - n_first * p.Hin * p.Win) * p.ldin + (cpos ^ swz<BK>(row)) * 8) * 2;
-        vm = 1u;
-      }
-    } else if (m < p.M) {
-      const int t1 = (int)fdiv((unsigned)m, p.dMW), xx = m - t1 * p.MW;
-      const int n = (int)fdiv((unsigned)t1, p.dMH), yy = t1 - n * p.MH;
-      const int iy0 = yy * p.sin, ix0 = xx * p.sin;
-      voff = ((((n - n_first) * p.Hin + iy0) * p.Win + ix0) * p.ldin + (cpos ^ swz<BK>(row)) * 8) * 2;
-#pragma unroll
-      for (int t = 0; t < MAX_TAPS; ++t) {   // tap table unpacked from two scalar registers (no memory access)
-        if (t >= p.T) break;                 // uniform: the 1-, 2- and 4-tap classes of a stride-2 data gradient stop early
-        const int dyt = (int)((p.dy_pack >> (4 * t)) & 0xF) - 2, dxt = (int)((p.dx_pack >> (4 * t)) & 0xF) - 2;
-        const bool ok = (unsigned)(iy0 + dyt) < (unsigned)p.Hin && (unsigned)(ix0 + dxt) < (unsigned)p.Win;
-        vm |= ok ? (1u << t) : 0u;
-      }
-    }
-    a_voff[i] = voff;
-    a_valid[i] = vm;
+    const int row = (wid * A_PER + i) * R + lrow;
+    const RowSource rs = row_source<BK>(p, m0 + row, td.n_first, cpos, row);
+    a_voff[i] = rs.voff;
+    a_valid[i] = rs.valid;
   }
   if (PROF) asm volatile("s_nop 0" ::"v"(a_voff[0]), "v"(a_valid[A_PER - 1]));
   STAMP(t_p2);
@@ -150,7 +125,7 @@ __global__ __launch_bounds__(WM* WN * 64, (OCC > 0 ? OCC : (WM * WN >= 8 ? 2 : 1
   // k-steps walk (tap, channel chunk); a split-K block walks only its channel range [c0b, c0b + cin_steps*BK) of every tap
   const int cin_steps = __builtin_amdgcn_readfirstlane((p.ksplit > 1 ? p.Cin / p.ksplit : p.Cin) / BK);
   const int c0b = sp * cin_steps * (BK * 2);                     // byte offset of the split's first channel (0 without split-K)
-  const int ksteps = ABL == 5 ? 0 : p.T * cin_steps;            // ABL 5: prologue + epilogue only
+  const int ksteps = p.T * cin_steps;
   int pf_t = 0, pf_c = 0;   // (tap, cin-step) of the next stage to prefetch
 
   auto stage = [&](int s, int buf) {
@@ -172,27 +147,12 @@ __global__ __launch_bounds__(WM* WN * 64, (OCC > 0 ? OCC : (WM * WN >= 8 ? 2 : 1
     }
   };
 
-  // one LDS-DMA piece of the stage being prefetched (q < A_PER: activation rows, else weight rows)
-  auto issue_piece = [&](int q, int boff, int soff, int tap, int buf) {
-    char* sa = smem + buf * STAGE;
-    char* sb = sa + BM * ROWB;
-    if (q < A_PER) {
-      const int instr = wid * A_PER + q;
-      bufld16(rsrc_x, sa + instr * 1024, ((a_valid[q] >> tap) & 1u) ? a_voff[q] : OOB_VOFF, soff);
-    } else {
-      bufld16(rsrc_w, sb + b_instr[q - A_PER] * 1024, b_voff[q - A_PER], boff);
-    }
-  };
-
   f32x4_t acc[TN][TM];
-#pragma unroll
-  for (int i = 0; i < TN; ++i)
-#pragma unroll
-    for (int j = 0; j < TM; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+  clear_acc(acc);
 
 #pragma unroll
   for (int s = 0; s < D; ++s)
-    if (s < ksteps && ABL != 1) stage(s, s);
+    if (s < ksteps) stage(s, s);
 
   const int fr = lane & 15, fq = lane >> 4;
   int buf = 0;
@@ -212,18 +172,7 @@ __global__ __launch_bounds__(WM* WN * 64, (OCC > 0 ? OCC : (WM * WN >= 8 ? 2 : 1
     STAMP(t_c);
     const bool pf = s + D < ksteps;
     const int pbuf = buf == 0 ? NST - 1 : buf - 1;
-    int il_soff = 0, il_tap = 0, il_boff = 0;
-    if (!ILV) {
-      if (pf && ABL != 1) stage(s + D, pbuf);
-    } else if (pf) {
-      il_tap = pf_t;
-      il_soff = __builtin_amdgcn_readfirstlane(s_toff[pf_t]) + c0b + pf_c * (BK * 2);
-      il_boff = pf_t * (p.Cin * 2) + c0b + pf_c * (BK * 2);
-      if (++pf_c == cin_steps) {
-        pf_c = 0;
-        ++pf_t;
-      }
-    }
+    if (pf) stage(s + D, pbuf);
     STAMP(t_d);
     const char* sa = smem + buf * STAGE;
     const char* sb = sa + BM * ROWB;
@@ -233,33 +182,17 @@ __global__ __launch_bounds__(WM* WN * 64, (OCC > 0 ? OCC : (WM * WN >= 8 ? 2 : 1
 #pragma unroll
       for (int i = 0; i < TN; ++i) {
         const int row = wn * (TN * 16) + i * 16 + fr;
-        if (ABL == 2) { wf[i] = __builtin_bit_cast(st16x8_t, make_uint4(row, s, ks, i)); asm volatile("" : "+v"(wf[i])); }
-        else wf[i] = *(const st16x8_t*)(sb + row * ROWB + (((ks * 4 + fq) ^ swz<BK>(row)) << 4));
+        wf[i] = *(const st16x8_t*)(sb + row * ROWB + (((ks * 4 + fq) ^ swz<BK>(row)) << 4));
       }
 #pragma unroll
       for (int j = 0; j < TM; ++j) {
         const int row = wm * (TM * 16) + j * 16 + fr;
-        if (ABL == 2) { af[j] = __builtin_bit_cast(st16x8_t, make_uint4(row, s, ks, j)); asm volatile("" : "+v"(af[j])); }
-        else af[j] = *(const st16x8_t*)(sa + row * ROWB + (((ks * 4 + fq) ^ swz<BK>(row)) << 4));
+        af[j] = *(const st16x8_t*)(sa + row * ROWB + (((ks * 4 + fq) ^ swz<BK>(row)) << 4));
       }
-      constexpr int NMF = TN * TM * (BK / 32);            // MFMAs per k-step per wave
-      constexpr int G = NMF / PER > 0 ? NMF / PER : 1;     // MFMAs between two LDS-DMA pieces
 #pragma unroll
       for (int i = 0; i < TN; ++i)
 #pragma unroll
-        for (int j = 0; j < TM; ++j) {
-          if (ABL == 3) { asm volatile("" ::"v"(wf[i]), "v"(af[j])); acc[i][j][0] += 1.0f; }
-          else acc[i][j] = MI355_MFMA_16x16x32(wf[i], af[j], acc[i][j]);
-          if (ILV) {
-            // spread the next stage's LDS-DMA pieces between the MFMAs: a piece costs ~100+ issue cycles, which
-            // then overlap with this wave's own MFMAs still running in the matrix pipe
-            const int cnt = ks * TN * TM + i * TM + j + 1;
-            if (cnt % G == 0 && cnt / G - 1 < PER) {
-              if (pf) issue_piece(cnt / G - 1, il_boff, il_soff, il_tap, pbuf);
-              __builtin_amdgcn_sched_barrier(0);
-            }
-          }
-        }
+        for (int j = 0; j < TM; ++j) acc[i][j] = MI355_MFMA_16x16x32(wf[i], af[j], acc[i][j]);
     }
     buf = buf + 1 == NST ? 0 : buf + 1;
     if (PROF) {
@@ -319,26 +252,21 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN >= 8 || TM >= 8 || NSTB > 2 ?
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wid % WM, wn = wid / WM;
-  const int ntn = p.CoutPad / BN, nblk = gridDim.x;
-  int bid = blockIdx.x;
-  {
-    const int q = nblk / 8, r = nblk % 8, xcd = bid % 8, loc = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  }
+  const int ntn = p.CoutPad / BN;
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
   const int mt = bid / ntn, nt = bid - mt * ntn;
   const int m0 = mt * BM, n0 = nt * BN;
 
-  const int n_first = (int)fdiv(fdiv((unsigned)max(m0 - R, 0), p.dMW), p.dMH);
-  const int Ktot = 9 * p.Cin;
-  const srd_t rsrc_x = make_srd(p.x + (long long)n_first * p.Hin * p.Win * p.ldin - p.tap_pad, 0x7FFFFFF0u);
-  const srd_t rsrc_w = make_srd(p.w + (long long)n0 * Ktot, 0x7FFFFFF0u);
+  const TileDescriptors td = tile_descriptors(p, max(m0 - R, 0), n0, 9);      // the halo piece in front of the tile may lie in the previous image
+  const srd_t rsrc_x = td.rsrc_x, rsrc_w = td.rsrc_w;
+  const int n_first = td.n_first, Ktot = td.Ktot;
 
   // scalar tap geometry: kernel row g uses taps 3g..3g+2 (same dy); dx of position i is the same for every row
   int dyg[3], dxi[3];
 #pragma unroll
   for (int g = 0; g < 3; ++g) {
-    dyg[g] = (int)((p.dy_pack >> (12 * g)) & 0xF) - 2;
-    dxi[g] = (int)((p.dx_pack >> (4 * g)) & 0xF) - 2;
+    dyg[g] = tap_dy(p, 3 * g);
+    dxi[g] = tap_dx(p, g);
   }
 
   // ---- pixel-tile rows this lane stages: extended row e <-> lattice pixel m0 - R + e
@@ -353,11 +281,10 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN >= 8 || TM >= 8 || NSTB > 2 ?
     unsigned vm = 0;
     int voff = OOB_VOFF;
     if (instr < A_INSTR && m >= 0 && m < p.M) {
-      const int t1 = (int)fdiv((unsigned)m, p.dMW), xx = m - t1 * p.MW;
-      const int n = (int)fdiv((unsigned)t1, p.dMH), yy = t1 - n * p.MH;
-      voff = ((((n - n_first) * p.Hin + yy) * p.Win + xx) * p.ldin + (cpos ^ swz_shift<BK>(e)) * 8) * 2;
+      const LatticePixel q = lattice_pixel(p, m);
+      voff = ((((q.n - n_first) * p.Hin + q.yy) * p.Win + q.xx) * p.ldin + (cpos ^ swz_shift<BK>(e)) * 8) * 2;
 #pragma unroll
-      for (int g = 0; g < 3; ++g) vm |= ((unsigned)(yy + dyg[g]) < (unsigned)p.Hin) ? (1u << g) : 0u;
+      for (int g = 0; g < 3; ++g) vm |= ((unsigned)(q.yy + dyg[g]) < (unsigned)p.Hin) ? (1u << g) : 0u;
     }
     a_voff[i] = voff;
     a_valid[i] = vm;
@@ -379,8 +306,7 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN >= 8 || TM >= 8 || NSTB > 2 ?
 #pragma unroll
   for (int j = 0; j < TM; ++j) {
     const int r = wm * (TM * 16) + j * 16 + fr;
-    const int m = m0 + r;
-    const int t1 = (int)fdiv((unsigned)m, p.dMW), xx = m - t1 * p.MW;
+    const int xx = lattice_pixel(p, m0 + r).xx;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
       const int e = r + R + dxi[i];
@@ -396,17 +322,13 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN >= 8 || TM >= 8 || NSTB > 2 ?
   }
 
   f32x4_t acc[TN][TM];
-#pragma unroll
-  for (int i = 0; i < TN; ++i)
-#pragma unroll
-    for (int j = 0; j < TM; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+  clear_acc(acc);
 
   const int cin_steps = p.Cin / BK;
   const int NQ = 3 * cin_steps;             // groups: channel chunk outer, kernel row inner
-  const int rowpitch2 = p.Win * p.ldin * 2; // bytes per image row
 
-  // group q = (chunk c, kernel row g): scalar byte offset of its pixel tile; step (q, i): scalar offset of its weight tile
-  auto a_soff = [&](int c, int g) { return (dyg[g] * p.Win * p.ldin + p.tap_pad) * 2 + c * (BK * 2); };
+  // group q = (chunk c, kernel row g): scalar byte offset of its pixel tile (the row's dx = 0 tap); step (q, i): scalar offset of its weight tile
+  auto a_soff = [&](int c, int g) { return tap_byte_offset(p, dyg[g], 0) + c * (BK * 2); };
   auto issue_a = [&](int lo, int hi, int c, int g, char* ab) {
     const int soff = a_soff(c, g);
 #pragma unroll
@@ -418,7 +340,6 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN >= 8 || TM >= 8 || NSTB > 2 ?
 #pragma unroll
     for (int q = 0; q < B_PER; ++q) bufld16(rsrc_w, bb + (wid * B_PER + q) * 1024, b_voff[q], koff);
   };
-  (void)rowpitch2;
   // step index -> (chunk, kernel row, dx position) of the weight tile D steps ahead, kept incrementally
   const int NS = 3 * NQ;
   issue_a(0, A_PER, 0, 0, abuf0);
@@ -533,7 +454,7 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN >= 8 || TM >= 8 || NSTB > 2 ?
 // latency hides under the first half's MFMAs) and the next stage's LDS-DMA pieces are issued BRANCH-FREE between
 // groups of MFMAs (past the last stage the pieces carry an out-of-range offset and just zero-fill the idle buffer),
 // so a piece's ~100-cycle issue stall overlaps with this wave's own MFMAs still executing in the matrix pipe.
-template <int WM, int WN, int TM, int TN, int BK, int EPI, int SCHED>
+template <int WM, int WN, int TM, int TN, int BK, int EPI>
 __global__ __launch_bounds__(WM* WN * 64, (WM * WN >= 8 ? 2 : 1)) void igemm_il_kernel(const IgemmParams p) {
   constexpr int NT = WM * WN * 64, NW = WM * WN, NST = 2;
   constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
@@ -548,14 +469,12 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN >= 8 ? 2 : 1)) void igemm_il_
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wid % WM, wn = wid / WM;
-  const int ntn = p.CoutPad / BN, nblk = gridDim.x;
-  int bid = blockIdx.x;
-  {
-    const int q = nblk / 8, r = nblk % 8, xcd = bid % 8, loc = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  }
+  const int ntn = p.CoutPad / BN;
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
   const int mt = bid / ntn, nt = bid - mt * ntn;
   const int m0 = mt * BM, n0 = nt * BN;
+  // This kernel keeps its own prologue (no lin_in form, no early stop at p.T), as it was: with row_source / tile_descriptors it lost
+  // the timing rule on three of its ten 3x3 YOLO shapes (+0.7 .. +1.6 %, profiles/r34_igemm_family.md).
   if (tid == 0) {
 #pragma unroll
     for (int t = 0; t < MAX_TAPS; ++t)
@@ -602,10 +521,7 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN >= 8 ? 2 : 1)) void igemm_il_
   int pf_t = 0, pf_c = 0;
 
   f32x4_t acc[TN][TM];
-#pragma unroll
-  for (int i = 0; i < TN; ++i)
-#pragma unroll
-    for (int j = 0; j < TM; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+  clear_acc(acc);
 
   // one piece q of stage s into buffer `buf`; `live` false -> out-of-range offsets (zero fill, no memory traffic)
   auto piece = [&](int q, int s, int soff, int tap, int buf, bool live) {
@@ -665,15 +581,6 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN >= 8 ? 2 : 1)) void igemm_il_
           const int cnt = (ks * TN + i) * TM + j + 1;
           if (cnt % G == 0 && cnt / G - 1 < PER) piece(cnt / G - 1, s + 1, soff, tap, buf ^ 1, live);
         }
-    if (SCHED == 1) {
-      // ask the scheduler for: all DS reads first, then G MFMAs / 1 LDS-DMA piece alternating
-      __builtin_amdgcn_sched_group_barrier(0x100, KS * (TN + TM), 0);
-#pragma unroll
-      for (int q = 0; q < PER; ++q) {
-        __builtin_amdgcn_sched_group_barrier(0x8, G, 0);
-        __builtin_amdgcn_sched_group_barrier(0x20, 1, 0);
-      }
-    }
   }
   __builtin_amdgcn_s_waitcnt(0xC07F);
   wait_vmcnt<0>();
@@ -823,7 +730,7 @@ int ensure_zero_page() {
 
 unsigned long long* g_dbg = nullptr;
 
-template <int WM, int WN, int TM, int TN, int BK, int NST, int EPI, bool PROF = false, bool ILV = false, int OCC = 0, int ABL = 0>
+template <int WM, int WN, int TM, int TN, int BK, int NST, int EPI, bool PROF = false, int OCC = 0>
 int launch_cfg(const IgemmParams& p_in, hipStream_t st) {
   IgemmParams p = p_in;
   p.dbg = PROF ? g_dbg : nullptr;
@@ -832,7 +739,7 @@ int launch_cfg(const IgemmParams& p_in, hipStream_t st) {
   constexpr int lds_epi = EPI_LDS_OFF + WM * WN * (64 * (TN * 32 + 16) + 256);
   constexpr int lds = lds_ring > lds_epi ? lds_ring : lds_epi;
   const int gm = (p.M + BM - 1) / BM, gn = p.CoutPad / BN;
-  auto k = igemm_kernel<WM, WN, TM, TN, BK, NST, EPI, PROF, ILV, OCC, ABL>;
+  auto k = igemm_kernel<WM, WN, TM, TN, BK, NST, EPI, PROF, OCC>;
   static DeviceOnce attr_done;
   attr_done.once([&] {
     (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -841,14 +748,14 @@ int launch_cfg(const IgemmParams& p_in, hipStream_t st) {
   return check_launch("igemm");
 }
 
-template <int WM, int WN, int TM, int TN, int BK, int EPI, int SCHED>
+template <int WM, int WN, int TM, int TN, int BK, int EPI>
 int launch_il(const IgemmParams& p, hipStream_t st) {
   constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
   constexpr int lds_ring = 2 * (BM + BN) * BK * 2 + 64;
   constexpr int lds_epi = EPI_LDS_OFF + WM * WN * (64 * (TN * 32 + 16) + 256);
   constexpr int lds = lds_ring > lds_epi ? lds_ring : lds_epi;
   const int gm = (p.M + BM - 1) / BM, gn = p.CoutPad / BN;
-  auto k = igemm_il_kernel<WM, WN, TM, TN, BK, EPI, SCHED>;
+  auto k = igemm_il_kernel<WM, WN, TM, TN, BK, EPI>;
   static DeviceOnce attr_done;
   attr_done.once([&] {
     (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -956,8 +863,8 @@ const CfgRow* cfg_rows() {
     CFG_ROW( 2, eALL,                              REQ_WIDE,      128,   0, 1, 0, launch_cfg<2, 2, 8, 4, 32, 2, EPI>),                  // 256x128x32 x2, 4 waves of 128x64, 48 KB
     CFG_ROW( 3, eALL,                              REQ_WIDE,      256,   0, 1, 1, launch_cfg<2, 4, 8, 4, 64, 2, EPI>),                  // 256x256x64 x2, 8 waves of 128x64
     CFG_ROW( 4, eALL,                              REQ_WIDE,      128,   0, 1, 0, launch_cfg<2, 2, 4, 4, 32, 3, EPI>),                  // 128x128x32 x3, 3 workgroups/CU
-    CFG_ROW( 5, eALL,                              REQ_WIDE,      128,   0, 1, 0, launch_cfg<2, 2, 4, 4, 32, 2, EPI, false, false, 4>), // 128x128x32 x2: 32 KB LDS, <= 128 VGPR, 4 workgroups/CU
-    CFG_ROW( 6, eALL,                              REQ_WIDE,      256,   0, 1, 1, launch_il<2, 4, 8, 4, 64, EPI, 0>),                   // 256x256x64 with LDS-DMA pieces interleaved between MFMAs
+    CFG_ROW( 5, eALL,                              REQ_WIDE,      128,   0, 1, 0, launch_cfg<2, 2, 4, 4, 32, 2, EPI, false, 4>),        // 128x128x32 x2: 32 KB LDS, <= 128 VGPR, 4 workgroups/CU
+    CFG_ROW( 6, eALL,                              REQ_WIDE,      256,   0, 1, 1, launch_il<2, 4, 8, 4, 64, EPI>),                      // 256x256x64 with LDS-DMA pieces interleaved between MFMAs
     CFG_ROW(15, eALL,                              REQ_DX,        128,  64, 1, 0, launch_dx<2, 2, 4, 4, EPI>),                          // 3x3 s1: shared pixel tiles (dx reuse), 128x128
     CFG_ROW(16, eALL,                              REQ_DX,        128,  64, 1, 1, launch_dx<4, 2, 4, 4, EPI>),                          // dx reuse 256x128, 8 waves
     CFG_ROW(17, eALL,                              REQ_DX,        256,  64, 1, 1, launch_dx<2, 4, 4, 4, EPI>),                          // dx reuse 128x256, 8 waves
@@ -976,20 +883,10 @@ const CfgRow* cfg_rows() {
     CFG_ROW(29, eALL,                              REQ_NARROW_DX,  32,  64, 1, 0, launch_dx<4, 1, 4, 2, EPI>),
     CFG_ROW(30, eALL,                              REQ_NARROW_DX,  64,  64, 1, 0, launch_dx<4, 1, 4, 4, EPI>),
     CFG_ROW(31, eALL,                              REQ_NARROW_DX,  64,  32, 1, 0, launch_dx<4, 1, 4, 4, EPI, 2, false, 32>),
-    CFG_ROW(35, eALL,                              REQ_DX,        128,  32, 0, 0, launch_dx<2, 2, 4, 4, EPI, 2, false, 32>),            // dx reuse 128x128x32, 3 workgroups/CU: measured slower, not tried
-    // diagnostics (forward with statistics only, never tried).  50-56: deeper rings, measured slower than depth 2 once the LDS-DMA really
-    // stays in flight
-    CFG_ROW(50, eSTATS,                            REQ_WIDE,      256,   0, 0, 0, launch_cfg<2, 4, 8, 4, 32, 3, EPI>),                  // 256x256x32 ring 3 (96 KB)
-    CFG_ROW(51, eSTATS,                            REQ_WIDE,      256,   0, 0, 0, launch_cfg<2, 4, 8, 4, 32, 4, EPI>),                  // 256x256x32 ring 4 (128 KB)
-    CFG_ROW(52, eSTATS,                            REQ_WIDE,      128,   0, 0, 0, launch_cfg<2, 2, 8, 4, 32, 3, EPI>),                  // 256x128x32 ring 3 (72 KB, 2 workgroups/CU)
-    CFG_ROW(53, eSTATS,                            REQ_WIDE,      128,   0, 0, 0, launch_cfg<2, 2, 8, 4, 32, 4, EPI>),                  // 256x128x32 ring 4 (96 KB)
-    CFG_ROW(54, eSTATS,                            REQ_WIDE,      128,   0, 0, 0, launch_cfg<2, 2, 4, 4, 32, 4, EPI>),                  // 128x128x32 ring 4 (64 KB, 2 workgroups/CU)
-    CFG_ROW(55, eSTATS,                            REQ_WIDE,      128,   0, 0, 0, launch_cfg<2, 2, 4, 4, 64, 3, EPI>),                  // 128x128x64 ring 3 (96 KB, 1 workgroup/CU)
-    CFG_ROW(56, eSTATS,                            REQ_WIDE,      128,   0, 0, 0, launch_cfg<2, 2, 4, 4, 32, 6, EPI>),                  // 128x128x32 ring 6 (96 KB)
-    CFG_ROW(21, eSTATS,                            REQ_WIDE,      128,   0, 0, 0, launch_cfg<2, 2, 4, 4, 64, 2, EPI, false, false, 0, 1>),   // ablations of configuration 1
-    CFG_ROW(22, eSTATS,                            REQ_WIDE,      128,   0, 0, 0, launch_cfg<2, 2, 4, 4, 64, 2, EPI, false, false, 0, 2>),
-    CFG_ROW(23, eSTATS,                            REQ_WIDE,      128,   0, 0, 0, launch_cfg<2, 2, 4, 4, 64, 2, EPI, false, false, 0, 3>),
-    CFG_ROW(25, eSTATS,                            REQ_WIDE,      128,   0, 0, 0, launch_cfg<2, 2, 4, 4, 64, 2, EPI, false, false, 0, 5>),
+    // (measured slower, never tried by the tuner, removed: deeper rings - depth 3 / 4 / 6 against 2 - under the plain tiles, slower than depth 2
+    // once the LDS-DMA really stays in flight (former ids 50-56, template arguments in profiles/r07_conv_cfg_table.md), and the shared-pixel-tile
+    // kernel at 128x128 with a 32-deep k-step, 3 workgroups/CU (former id 35 = launch_dx<2, 2, 4, 4, EPI, 2, false, 32>))
+    // diagnostics (forward with statistics only, never tried): phase-stamp builds
     CFG_ROW(99, eSTATS,                            REQ_WIDE,      128,   0, 0, 0, launch_cfg<2, 2, 4, 4, 64, 2, EPI, true>),            // phase-stamp build of configuration 1
     CFG_ROW(98, eSTATS,                            REQ_DX,        128,  64, 0, 0, launch_dx<2, 2, 4, 4, EPI, 2, true>),                 // the same for the shared-pixel-tile kernel
     CFG_ROW(97, eSTATS,                            REQ_DX,        128,  64, 0, 0, launch_dx<4, 2, 4, 4, EPI, 3, true>),                 // 256x128, 8 waves, ring 3

@@ -12,12 +12,9 @@
 // tile are written as two whole output rows (2*TP consecutive pixels each) through an fp32 LDS transpose.
 // Replaces, for these shapes, the four mi355det_conv_dgrad class launches (reference: the autograd of nn.Conv2d in
 // nets/darknet.py:43-49, the stride-2 down-sampling convolutions).
-#include "common.h"
+#include "mfma_prims.h"
 
 using namespace mi355;
-
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-typedef __attribute__((ext_vector_type(4))) int srd_t;
 
 struct DgradS2Params {
   const bf16_t* dy;   // [n, Ho, Wo, K] pitch lddy
@@ -30,22 +27,11 @@ struct DgradS2Params {
 
 namespace {
 
-__device__ __forceinline__ srd_t make_srd(const void* base, unsigned num_records) {
-  const unsigned long long a = (unsigned long long)base;
-  srd_t r;
-  r[0] = (int)(unsigned)a;
-  r[1] = (int)((unsigned)(a >> 32) & 0xFFFFu);
-  r[2] = (int)num_records;
-  r[3] = 0x00020000;
-  return r;
+// bufld16 with both scalar operands passed through readfirstlane: they are uniform by construction, but the loops over `ii` and the integer
+// divisions of the tile index leave the LDS address and the offset in VGPRs
+__device__ __forceinline__ void bufld16_u(srd_t rsrc, const void* lds_dst_uniform, int voffset, int soffset) {
+  bufld16_at(rsrc, __builtin_amdgcn_readfirstlane(lds_addr(lds_dst_uniform)), voffset, __builtin_amdgcn_readfirstlane(soffset));
 }
-// inline assembly on purpose: see conv_kernels.hip (the compiler would drain vmcnt before every later LDS read)
-__device__ __forceinline__ void bufld16(srd_t rsrc, const void* lds_dst_uniform, int voffset, int soffset) {
-  const unsigned lds = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)(__attribute__((address_space(3))) const void*)lds_dst_uniform);
-  const int so = __builtin_amdgcn_readfirstlane(soffset);   // uniform by construction; integer divisions leave it in a VGPR
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds), "v"(voffset), "s"(rsrc), "s"(so) : "memory");
-}
-#define OOB_VOFF ((int)0x80000000)
 // workgroup barrier for LDS hand-offs: this wave's LDS traffic has completed, and the compiler moves no memory access across it
 // (a bare s_barrier builtin carries no memory semantics; __syncthreads() would also drain the global stores and the prefetch)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
@@ -88,7 +74,7 @@ __global__ __launch_bounds__(256, NCH == 1 ? 2 : 1) void dgrad_s2_kernel(const D
     const int ci = rb * 8 + lrow;
     const int c = kCls[t];
     const int voff = (kWbase[c] * p.cin_pad * K + (cobase + ci) * kT[c] * K + kJ[t] * K + q * 64 + ((cpos ^ ((ci >> 1) & 7)) << 3)) * 2;
-    bufld16(rsrc_w, wl + ((t * NCH + q) * 32 + rb * 8) * 128, voff, 0);
+    bufld16_u(rsrc_w, wl + ((t * NCH + q) * 32 + rb * 8) * 128, voff, 0);
   }
 
   // ---- pixel tile of one output tile: lane offsets are tile-independent, the tile enters through the scalar offset
@@ -103,7 +89,7 @@ __global__ __launch_bounds__(256, NCH == 1 ? 2 : 1) void dgrad_s2_kernel(const D
       const bool ok = r <= TP && !(r == TP && last_x) && !(plane == 1 && last_y);
       const int voff = (r * p.lddy + q * 64 + ((cpos ^ lrow) << 3)) * 2;      // swizzle phase r & 7 == lrow
       const int soff = (((n * p.Ho + yy + plane) * p.Wo + xt * TP) * p.lddy) * 2;
-      bufld16(rsrc_dy, ab + ((plane * NCH + q) * AR + rb * 8) * 128, ok ? voff : OOB_VOFF, (plane == 1 && last_y) ? 0 : soff);
+      bufld16_u(rsrc_dy, ab + ((plane * NCH + q) * AR + rb * 8) * 128, ok ? voff : OOB_VOFF, (plane == 1 && last_y) ? 0 : soff);
     }
   };
 
@@ -116,8 +102,8 @@ __global__ __launch_bounds__(256, NCH == 1 ? 2 : 1) void dgrad_s2_kernel(const D
     // the pixel tile was issued BEFORE the previous tile's output stores (vmcnt retires in order): those NST stores per thread may
     // stay in flight (with a residual the compiler's own waits for the residual loads have already drained the older DMA)
     constexpr int NST = 2 * 2 * TP * 4 / 256;
-    if (tile == (int)blockIdx.x) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NST) : "memory");
+    if (tile == (int)blockIdx.x) wait_vmcnt<0>();
+    else wait_vmcnt<NST>();
     lds_barrier();                                  // this tile (and the weights) landed; everyone is done with the other buffer
     const int next = tile + gridDim.x;
     if (next < p.ntiles) issue_tile(next, abase + (buf ^ 1) * ABUF);

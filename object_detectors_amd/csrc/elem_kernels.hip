@@ -5,6 +5,8 @@
 
 #include <cstdlib>
 
+#include "bn_formulas.h"
+
 using namespace mi355;
 
 namespace {
@@ -77,13 +79,9 @@ __device__ __forceinline__ f32x8 bn_act8(const f32x8& z, const float (&sc)[8], c
 __device__ __forceinline__ f32x8 bn_dy8(const f32x8& g, const f32x8& z, const float (&sc)[8], const float (&sh)[8], float slope) {
   f32x8 dy;
 #pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const float y = z.v[k] * sc[k] + sh[k];
-    dy.v[k] = y > 0.f ? g.v[k] : g.v[k] * slope;
-  }
+  for (int k = 0; k < 8; ++k) dy.v[k] = bn_dy(g.v[k], z.v[k], sc[k], sh[k], slope);
   return dy;
 }
-__device__ __forceinline__ float bn_xhat(float z, float mu, float is) { return (z - mu) * is; }
 // dz = scale * (dy - mean(dy) - xhat * mean(dy * xhat))
 __device__ __forceinline__ f32x8 bn_dz8(const f32x8& dy, const f32x8& z, const float (&sc)[8], const float (&mu)[8], const float (&is)[8],
                                         const float (&m1)[8], const float (&m2)[8]) {

@@ -12,12 +12,10 @@
 //                             workspace with plain stores; a second kernel adds the partials in split order and keeps the in-group
 //                             entries.  No atomics anywhere: two calls give the same bits.
 // Stores go through plain global pointers (no buffer stores: tests/test_isa_hazards.py).
-#include "common.h"
+#include "mfma_prims.h"
 
 namespace mi355 {
 namespace {
-
-typedef mi355_f32x4_t f32x4_t;
 
 constexpr int GC_TW = 16;      // output tile width = one MFMA column block
 constexpr int GC_LP = 8;       // LDS pixel pitch padding (elements): 80 / 144 byte pitches spread 16-byte reads over the banks

@@ -1,29 +1,15 @@
-// Shared pieces of the implicit-GEMM convolution kernels (gfx950): problem description, LDS-DMA helpers, LDS swizzles and the
-// common epilogue (BN statistics / fp32 head / residual / affine / fused BN-backward sums).  Included by conv_kernels.hip and
-// igemm8_kernels.hip; everything is internal linkage.
+// Shared pieces of the implicit-GEMM convolution kernels (gfx950): problem description, the tile prologue (lattice pixel, row source,
+// tap offset, buffer descriptors), LDS swizzles and the common epilogue (BN statistics / fp32 head / residual / affine / fused
+// BN-backward sums).  Included by conv_kernels.hip and igemm8_kernels.hip; everything is internal linkage.
 #pragma once
-#include "common.h"
+#include "bn_formulas.h"
+#include "mfma_prims.h"
 
 using namespace mi355;
 
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 typedef __attribute__((ext_vector_type(8))) unsigned short u16x8_t;
 
 #define MAX_TAPS 9
-
-// division by a launch-invariant divisor without the ~40-instruction integer divide (n < 2^31)
-struct FastDiv {
-  unsigned mul, shift;
-};
-static FastDiv make_fastdiv(unsigned d) {
-  FastDiv f;
-  unsigned l = 0;
-  while ((1ull << l) < d) ++l;
-  f.shift = l;
-  f.mul = (unsigned)(((1ull << 32) * ((1ull << l) - d)) / d + 1);
-  return f;
-}
-__device__ __forceinline__ unsigned fdiv(unsigned n, const FastDiv f) { return (__umulhi(f.mul, n) + n) >> f.shift; }
 
 struct IgemmParams {
   const bf16_t* x;       // input activations (fwd: x, dgrad: dy)
@@ -72,43 +58,6 @@ void igemm8_set_dbg_mode(int mode);
 
 namespace {
 
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst_uniform) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_dst_uniform, 16, 0, 0);
-}
-
-// LDS-DMA through a buffer descriptor: per-lane 32-bit byte offset + SCALAR offset (the tap / k-step part of the
-// address costs no vector instruction); a lane whose voffset is out of range gets zeros written to LDS, which is
-// exactly the convolution's zero padding.
-// Issued as inline assembly ON PURPOSE: for the builtin the compiler's wait-count pass assumes every later ds_read may alias
-// the DMA's LDS destination and puts s_waitcnt vmcnt(0) in front of the next fragment read, which turns every counted wait of
-// the ring into a full drain (no load/compute overlap inside a workgroup, whatever the ring depth).  The kernels order DMA and
-// reads themselves (counted vmcnt + barrier), so the compiler must not know about the LDS side of these loads.
-typedef __attribute__((ext_vector_type(4))) int srd_t;
-__device__ __forceinline__ srd_t make_srd(const void* base, unsigned num_records) {
-  const unsigned long long a = (unsigned long long)base;
-  srd_t r;
-  r[0] = (int)(unsigned)a;
-  r[1] = (int)((unsigned)(a >> 32) & 0xFFFFu);
-  r[2] = (int)num_records;
-  r[3] = 0x00020000;
-  return r;
-}
-__device__ __forceinline__ void bufld16(srd_t rsrc, const void* lds_dst_uniform, int voffset, int soffset) {
-  const unsigned lds = (unsigned)(unsigned long long)(__attribute__((address_space(3))) const void*)lds_dst_uniform;
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds), "v"(voffset), "s"(rsrc), "s"(soffset) : "memory");
-}
-#define OOB_VOFF ((int)0x80000000)
-
-// sum over the 16 lanes of a DPP row (lanes sharing lane>>4), result in every lane: 4 VALU+DPP ops, no LDS traffic
-__device__ __forceinline__ float row16_sum(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));   // row_half_mirror
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));   // row_mirror
-  return v;
-}
-
 template <int BK>
 __device__ __forceinline__ int swz(int row) {
   return BK == 64 ? ((row >> 1) & 7) : ((-(row >> 2)) & 3);
@@ -123,12 +72,76 @@ __device__ __forceinline__ int swz_shift(int row) {
   return BK == 64 ? (row & 7) : swz<BK>(row);
 }
 
-// WM x WN waves; each wave computes 64 pixels x (TN*16) channels.  NST-deep LDS ring: the LDS-DMA of
-// k-steps s+1 .. s+NST-1 stays in flight (counted vmcnt, raw s_barrier) while k-step s runs on the MFMAs —
-// with ~1.5-2 us of loaded-memory latency the bytes in flight per CU, not the MFMA rate, set the speed.
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+// ---- the tile prologue: what igemm_kernel, igemm_dx_kernel (conv_kernels.hip) and igemm8_kernel compute before their main loops
+//      (igemm_il_kernel keeps its own: see there).  Plain functions; a kernel keeps whatever it needs of the results in its own variables.
+
+// lattice pixel m -> (image, row, column) of the lattice
+struct LatticePixel {
+  int n, yy, xx;
+};
+__device__ __forceinline__ LatticePixel lattice_pixel(const IgemmParams& p, int m) {
+  const int t1 = (int)fdiv((unsigned)m, p.dMW), xx = m - t1 * p.MW;
+  const int n = (int)fdiv((unsigned)t1, p.dMH), yy = t1 - n * p.MH;
+  return {n, yy, xx};
+}
+
+// tap t of the table, unpacked from two scalar registers (no memory access)
+__device__ __forceinline__ int tap_dy(const IgemmParams& p, int t) { return (int)((p.dy_pack >> (4 * t)) & 0xF) - 2; }
+__device__ __forceinline__ int tap_dx(const IgemmParams& p, int t) { return (int)((p.dx_pack >> (4 * t)) & 0xF) - 2; }
+// scalar byte offset of a tap (dy, dx), made non-negative by tap_pad (which tile_descriptors moves into the descriptor base).  The caller
+// names the tap: p.dy[t] / p.dx[t] where t is a compile-time index (the s_toff tables), tap_dy / tap_dx where it is a run-time one.
+__device__ __forceinline__ int tap_byte_offset(const IgemmParams& p, int dy, int dx) { return ((dy * p.Win + dx) * p.ldin + p.tap_pad) * 2; }
+
+// buffer descriptors (wave-uniform) of a tile whose first lattice pixel is m_first and whose first output channel is n0: activations
+// relative to the first image the tile touches, weights relative to the tile's first row
+struct TileDescriptors {
+  srd_t rsrc_x, rsrc_w;
+  int n_first, Ktot;      // Ktot = ntaps * Cin: elements per weight row
+};
+__device__ __forceinline__ TileDescriptors tile_descriptors(const IgemmParams& p, int m_first, int n0, int ntaps) {
+  TileDescriptors d;
+  d.n_first = (int)fdiv(fdiv((unsigned)m_first, p.dMW), p.dMH);
+  d.Ktot = ntaps * p.Cin;
+  d.rsrc_x = make_srd(p.x + (long long)d.n_first * p.Hin * p.Win * p.ldin - p.tap_pad, 0x7FFFFFF0u);
+  d.rsrc_w = make_srd(p.w + (long long)n0 * d.Ktot, 0x7FFFFFF0u);
+  return d;
+}
+
+// Where a lane's 16-byte chunk of lattice pixel m comes from: byte offset behind rsrc_x (without the tap) and the mask of taps that lie
+// inside the image (bit t).  cpos = the lane's chunk of the row, lds_row = the LDS row it lands in (its swizzle).  A pixel past the
+// lattice (m >= p.M, or a row the tile does not have: any m >= 2^30) gets OOB_VOFF / 0: zeros, no memory traffic.
+struct RowSource {
+  int voff;
+  unsigned valid;
+};
+template <int BK>
+__device__ __forceinline__ RowSource row_source(const IgemmParams& p, int m, int n_first, int cpos, int lds_row) {
+  RowSource r{OOB_VOFF, 0u};
+  if (p.lin_in) {   // 1x1, unit stride: the row's pixel index is the address, its only tap is always inside (uniform branch)
+    if (m < p.M) {
+      r.voff = ((m - n_first * p.Hin * p.Win) * p.ldin + (cpos ^ swz<BK>(lds_row)) * 8) * 2;
+      r.valid = 1u;
+    }
+  } else if (m < p.M) {
+    const LatticePixel q = lattice_pixel(p, m);
+    const int iy0 = q.yy * p.sin, ix0 = q.xx * p.sin;
+    r.voff = ((((q.n - n_first) * p.Hin + iy0) * p.Win + ix0) * p.ldin + (cpos ^ swz<BK>(lds_row)) * 8) * 2;
+#pragma unroll
+    for (int t = 0; t < MAX_TAPS; ++t) {
+      if (t >= p.T) break;                 // uniform: the 1-, 2- and 4-tap classes of a stride-2 data gradient stop early
+      const bool ok = (unsigned)(iy0 + tap_dy(p, t)) < (unsigned)p.Hin && (unsigned)(ix0 + tap_dx(p, t)) < (unsigned)p.Win;
+      r.valid |= ok ? (1u << t) : 0u;
+    }
+  }
+  return r;
+}
+
+template <int TN, int TM>
+__device__ __forceinline__ void clear_acc(f32x4_t (&acc)[TN][TM]) {
+#pragma unroll
+  for (int i = 0; i < TN; ++i)
+#pragma unroll
+    for (int j = 0; j < TM; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
 }
 
 // Per-channel partial sums of one workgroup tile -> rows of the partial buffer [row][2][CoutPad].  A row always stands for
@@ -416,10 +429,9 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, f32x4_t (&a
               const int k = q * 2 + hsel;
               const float gv = s2f((bf16_t)(hsel ? gi[q] >> 16 : gi[q] & 0xFFFF));
               const float zv = s2f((bf16_t)(hsel ? zi[q] >> 16 : zi[q] & 0xFFFF));
-              const float yv = zv * bn_sc[k] + bn_sh[k];                  // dy, xhat: a copy of bn_dy8 / bn_xhat (elem_kernels.hip), held to them by tests
-              const float dy = yv > 0.f ? gv : gv * p.slope;
+              const float dy = bn_dy(gv, zv, bn_sc[k], bn_sh[k], p.slope);
               bn_a1[k] += dy;
-              bn_a2[k] += dy * ((zv - bn_mu[k]) * bn_is[k]);
+              bn_a2[k] += dy * bn_xhat(zv, bn_mu[k], bn_is[k]);
             }
           }
         }

@@ -9,14 +9,13 @@
 // FrozenBN scale / shift + ReLU epilogue writes bf16 NHWC with 16-byte stores.
 // Channel order trick (stem_kernels.hip): MFMA row r of weight fragment i stands for channel (r/4)*16 + i*4 + r%4, so that a lane's four
 // accumulator quads are the 16 consecutive channels fq*16 .. fq*16+15 of its pixel.
-#include "common.h"
+#include "mfma_prims.h"
 
 #include <type_traits>
 
 using namespace mi355;
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 
 namespace {
 

@@ -21,14 +21,13 @@
 // and a wave instruction covers 16 whole pixels (1 KB contiguous) without an LDS transpose.
 // Persistent workgroups (grid = 4 per CU), tiles dealt round-robin; the next tile's image halo and gradient tile are fetched into registers
 // while the current one is computed.  Everything is fixed-order (bit-reproducible), unlike the atomics of bn_act_bwd_reduce.
-#include "common.h"
+#include "mfma_prims.h"
 
 #include <type_traits>
 
 using namespace mi355;
 
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 
 namespace {
 
@@ -64,14 +63,6 @@ struct StemParams {
 // __syncthreads() also drains vmcnt, i.e. it waits for the prefetched image halo and for every output store of the tile (2-4 us of HBM
 // latency per barrier: the persistent loops ran at half their speed with it).
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-__device__ __forceinline__ float row16_sum(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));
-  return v;
-}
 
 __device__ __forceinline__ st16x4_t lds_tr(const char* p) {
   s16x4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)p);

@@ -12,11 +12,10 @@
 // output channels), so a tap costs one LDS read per 2 MFMAs.  The activation is written to HBM once, on the side, for the weight gradient
 // of the layer (each workgroup stores the 16 x 32 pixels only it owns); z1 leaves as 16-byte stores of 8 consecutive channels per lane.
 // Persistent workgroups, image halo of the next tile prefetched into registers; fixed-order statistics (one partial row per workgroup).
-#include "common.h"
+#include "mfma_prims.h"
 
 using namespace mi355;
 
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
 
 namespace {
@@ -57,14 +56,6 @@ struct StemL1Params {
 // __syncthreads() also drains vmcnt, i.e. it waits for the prefetched image halo and for every output store of the tile (2-4 us of HBM
 // latency per barrier: the persistent loops ran at half their speed with it).
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-__device__ __forceinline__ float row16_sum(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));
-  return v;
-}
 
 __global__ __launch_bounds__(256, 2) void stem_l1_kernel(const StemL1Params p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
